@@ -11,9 +11,16 @@ scaling : weak - every rank denoises its own clips; the only collective is the o
           broadcast of the packed weights (outside the timed region).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 
-Adds to the JSON line: "roofline" (dominant kernel = the MFMA GEMM/implicit-conv family, timed per launch
+A plain run does only what the headline needs: set up, warm up, time --steps clips, write the last timed clip's latents when
+--dump-outputs DIR is given (DIR/latents.npy, float32; DIR/latents_rank<r>.npy per rank when --gpus > 1), print the line.
+Inputs and weights are seeded: the same arguments give the same inputs in every run.
+
+With --full the line also carries "host_launch_ms_per_ddim_step" (a short extra run from an idle queue) and the legs below; each
+--no-* option drops one of them from a --full run.
+"roofline" (dominant kernel = the MFMA GEMM/implicit-conv family, timed per launch
 with HIP events in an instrumented extra pass; on every configuration's line), with --vae "roofline_vae"
 (the same family inside the VAE decode), "cpu_baseline" (whole-clip DDIM steps at the same resolution, one untimed +
 --cpu-steps timed, threads bound to one NUMA node; rank 0, N=1 only: kind "reference" = the unmodified reference's own CPU path from the
@@ -95,7 +102,7 @@ def cpu_baseline_reference(frames, size, ddim_steps, timed_steps, timeout_s):
     subprocess (`python -m oracle.gpu_reference --cpu-baseline`, test infrastructure), threads bound like the port's.  None when the reference
     files are not staged or the subprocess fails / times out - the caller then falls back to the port."""
     import subprocess
-    if not (os.path.exists(os.path.join(ROOT, "oracle", "_ref", "animatediff", "models", "unet.py")) or os.path.isdir("/root/reference/animatediff")):
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "animatediff", "models", "unet.py")):
         return None, "reference model files not staged under oracle/_ref/"
     cores, logical = numa_node_cores(0)
     node_cores = len(cores)
@@ -205,7 +212,7 @@ def gpu_reference(args):
     CFG-pair forwards of the benchmark shape, as a SUBPROCESS (oracle/gpu_reference.py, test infrastructure): a crash or a timeout
     there costs this field, never the line.  A reported baseline, not the target."""
     import subprocess
-    if not (os.path.exists(os.path.join(ROOT, "oracle", "_ref", "animatediff", "models", "unet.py")) or os.path.isdir("/root/reference/animatediff")):
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "animatediff", "models", "unet.py")):
         return {"value": None, "note": "reference model files not staged under oracle/_ref/ (python -m oracle.stage_ref_scripts, build container only)"}
     cmd = [sys.executable, "-m", "oracle.gpu_reference", "--json", "--frames", str(args.frames), "--size", str(args.size), "--ddim-steps", str(args.ddim_steps),
            "--dtype", args.dtype, "--attention", "sdpa", "--timed", "2"]
@@ -217,6 +224,21 @@ def gpu_reference(args):
         if line.startswith("GPU_REFERENCE "):
             return json.loads(line[len("GPU_REFERENCE "):])
     return {"value": None, "error": (r.stderr or r.stdout)[-300:]}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, name, t):
+    """t as float32 to out_dir/<name>.npy; above DUMP_MAX_BYTES a fixed, seeded sample of its elements (same indices for the same shape)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = t.detach().float().cpu()
+    n = DUMP_MAX_BYTES // 4
+    if a.numel() > n:
+        a = a.reshape(-1)[torch.randint(a.numel(), (n,), generator=torch.Generator().manual_seed(0))]
+        name += "_sample"
+    np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
 
 
 def workload_label(args):
@@ -262,6 +284,10 @@ def main(argv=None, emulation=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed clips per GPU (one step = one 25-step DDIM clip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs (host launch timing, roofline, VAE decode, parity, reference on the GPU, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed clip to DIR/latents.npy (float32) after the timed steps")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, default=512)
@@ -283,6 +309,8 @@ def main(argv=None, emulation=None):
                     help="skip the `gpu_reference` leg (the UNMODIFIED reference UNet3D, eager PyTorch-ROCm under torch.autocast, from the byte copies under oracle/_ref/)")
     ap.add_argument("--gpu-reference-timeout", type=int, default=420, help="seconds the gpu_reference subprocess may take")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     emulate = emulation is not None
 
     # `python bench.py --gpus N` with no launcher around it: become the launcher (one rank per GPU over RCCL, rendezvous on
@@ -350,17 +378,20 @@ def main(argv=None, emulation=None):
     if n_coll != world:
         raise SystemExit(f"[bench] an all-reduce of ones over the process group returned {n_coll}, expected {world} ranks")
     assert torch.isfinite(out).all(), "non-finite latents"
-    # Host side of a DDIM step (~900 ctypes launches), outside the timed region: a SHORT run from an idle queue, so that the
-    # host is timed queueing launches, not waiting for room in a full HIP queue (over a whole clip the call returns only a little
-    # ahead of the GPU whatever the host's own speed: round 3 first reported that back-pressure as "host time").  Slowest rank.
-    # Well below gpu_ms_per_ddim_step = the GPU is the bound and the launch path has headroom for N processes per node.
-    n_host = min(4, args.ddim_steps)
-    c = clips[-1]
-    th = time.time()
-    sampler.sample(c["latents"], c["text"], n_host, 8.0, c["first"], c["mask"], fps=[2], flow=[4], ip_tokens=ip)
-    th = time.time() - th
-    sync()
-    host_ms = D.max_over_ranks(1000.0 * th / n_host, device)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "latents" if world == 1 else f"latents_rank{rank}", out)
+    if args.full:
+        # Host side of a DDIM step (~900 ctypes launches), outside the timed region: a SHORT run from an idle queue, so that the
+        # host is timed queueing launches, not waiting for room in a full HIP queue (over a whole clip the call returns only a little
+        # ahead of the GPU whatever the host's own speed: round 3 first reported that back-pressure as "host time").  Slowest rank.
+        # Well below gpu_ms_per_ddim_step = the GPU is the bound and the launch path has headroom for N processes per node.
+        n_host = min(4, args.ddim_steps)
+        c = clips[-1]
+        th = time.time()
+        sampler.sample(c["latents"], c["text"], n_host, 8.0, c["first"], c["mask"], fps=[2], flow=[4], ip_tokens=ip)
+        th = time.time() - th
+        sync()
+        host_ms = D.max_over_ranks(1000.0 * th / n_host, device)
 
     result = None
     if rank == 0:
@@ -370,7 +401,7 @@ def main(argv=None, emulation=None):
             "n_gpus": world, "rccl_ranks": n_coll, "collective_backend": (torch.distributed.get_backend() if torch.distributed.is_initialized() else None), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * elapsed / args.steps, 2),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "emulated" if emulate else "synthetic",
             "clips_per_sec": round(world * args.steps / elapsed, 4),
-            "host_launch_ms_per_ddim_step": round(host_ms, 2), "gpu_ms_per_ddim_step": round(1000 * elapsed / (args.steps * args.ddim_steps), 2),
+            "gpu_ms_per_ddim_step": round(1000 * elapsed / (args.steps * args.ddim_steps), 2),
             "config": {"workload": f"{workload_label(args)}: AnimationPipeline DDIM loop, SD-1.5 UNet3D + mm_sd_v15-shaped motion modules "
                                    f"(random init), 1 clip/GPU of {args.frames} frames {args.size}x{args.size}, {args.ddim_steps} DDIM steps, "
                                    f"CFG 8.0, mask + first-frame concat, fps/flow conditioning"
@@ -378,9 +409,11 @@ def main(argv=None, emulation=None):
                        "frames": args.frames, "height": args.size, "width": args.size, "ddim_steps": args.ddim_steps, "ip_tokens": args.ip_tokens,
                        "parallelism": f"dp{world} (independent clips, weight broadcast {moved / 2**30:.2f} GiB in {t_b:.2f}s)"},
         }
+        if args.full:
+            result["host_launch_ms_per_ddim_step"] = round(host_ms, 2)
 
     # ---- roofline leg: one instrumented clip step, per-launch HIP-event timing (rank 0) ---------------
-    if rank == 0 and not args.no_roofline and not emulate:
+    if rank == 0 and args.full and not args.no_roofline and not emulate:
         timed = TimedOps(eng.ops)
         eng.ops = timed
         c = clips[-1]
@@ -473,7 +506,7 @@ def main(argv=None, emulation=None):
                                              "frac": round(at / PEAK_BF16_TFLOPS, 4), "launches_per_ddim_step": a["launches"] // n_inst,
                                              "avg_launch_us": round(1e3 * a["ms"] / a["launches"], 2)}
 
-    if rank == 0 and args.vae and not emulate:
+    if rank == 0 and args.full and args.vae and not emulate:
         from followyourclick_amd.engine import VAEDecoderConfig
         from followyourclick_amd.engine.schema import vae_decoder_schema
         from followyourclick_amd.engine.vae import VAEDecoderEngine
@@ -507,18 +540,18 @@ def main(argv=None, emulation=None):
                                       "kernel_families": {k: {"ms": round(v["ms"], 3), "launches": v["launches"]} for k, v in sorted(vs.items(), key=lambda kv: -kv[1]["ms"])}}
         assert torch.isfinite(vid).all()
 
-    if rank == 0 and not emulate and not args.no_parity and (args.frames, args.size, args.ddim_steps, args.ip_tokens) == (16, 512, 25, 0):
+    if rank == 0 and args.full and not emulate and not args.no_parity and (args.frames, args.size, args.ddim_steps, args.ip_tokens) == (16, 512, 25, 0):
         try:
             result["parity"] = parity_leg(args, dtype, device)
         except Exception as e:  # a reported extra, never a reason to lose the throughput number
             result["parity"] = {"value": None, "error": repr(e)[:200]}
 
-    if rank == 0 and world == 1 and not emulate and not args.no_gpu_reference and args.ip_tokens == 0:
+    if rank == 0 and args.full and world == 1 and not emulate and not args.no_gpu_reference and args.ip_tokens == 0:
         result["gpu_reference"] = gpu_reference(args)
         if result["gpu_reference"].get("value"):
             result["gpu_reference"]["engine_over_reference"] = round(result["value"] / result["gpu_reference"]["value"], 2)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not emulate and os.environ.get("FYC_BENCH_CPU", "1") != "0":
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and not emulate and os.environ.get("FYC_BENCH_CPU", "1") != "0":
         # the reference's OWN CPU path first (north_star: "the reference's own CPU path timed on the same box's host cores"); the oracle port
         # when the reference files are not there or its run fails
         ref, why = (None, "--cpu-port") if args.cpu_port else cpu_baseline_reference(args.frames, args.size, args.ddim_steps, args.cpu_steps, args.cpu_timeout)

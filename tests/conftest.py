@@ -158,7 +158,7 @@ def pytest_collection_finish(session):
     if not items or session.config.option.collectonly:
         return
     staged = os.path.join(ROOT, "oracle", "_ref", "animatediff", "models", "unet.py")
-    if not (os.path.exists(staged) or os.path.isdir("/root/reference/animatediff")):
+    if not os.path.exists(staged):
         return
     try:
         import torch
@@ -178,6 +178,7 @@ def pytest_collection_finish(session):
     # the reference's F.conv2d calls are run once or twice per shape, an exhaustive search per shape is the larger part of their time
     env.setdefault("OMP_NUM_THREADS", "16")
     env.setdefault("MIOPEN_FIND_MODE", "FAST")
+    env["FYC_REFERENCE_ROOT"] = os.path.join(ROOT, "oracle", "_ref")      # the staged byte copies, nothing outside the repository
     log = open(os.path.join(out_dir, "log.txt"), "w")
     proc = subprocess.Popen([sys.executable, "-m", "oracle.gpu_reference", "--dump", ",".join(what), "--out-dir", out_dir], cwd=ROOT, env=env,
                             stdout=log, stderr=subprocess.STDOUT)

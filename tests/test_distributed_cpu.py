@@ -146,7 +146,8 @@ def test_bench_entry_point_under_torch_distributed_run(tmp_path):
     import subprocess
     env = dict(os.environ, OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29771",
-           os.path.join(ROOT, "tests", "bench_emulated.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--frames", "2", "--size", "64", "--ddim-steps", "2", "--dtype", "f32"]
+           os.path.join(ROOT, "tests", "bench_emulated.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--frames", "2", "--size", "64", "--ddim-steps", "2", "--dtype", "f32",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -182,6 +183,33 @@ def test_bench_plain_invocation_launches_its_own_ranks(tmp_path):
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert "refusing" in r.stderr
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """a plain run (no --full) prints the headline fields only and, with --dump-outputs, writes the last timed clip's latents; the
+    inputs are seeded, so two runs with the same arguments dump the same array"""
+    import json
+    import subprocess
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_emulated.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "2",
+                            "--size", "64", "--ddim-steps", "2", "--dtype", "f32", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert "host_launch_ms_per_ddim_step" not in d
+        assert sorted(os.listdir(out)) == ["latents.npy"]
+        dumps.append(np.load(out / "latents.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1, 4, 2, 8, 8)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_bench_labels_follow_the_arguments():

@@ -10,7 +10,8 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HAVE_REF = os.path.isdir("/root/reference/animatediff") or os.path.exists(os.path.join(ROOT, "oracle", "_ref", "animatediff", "models", "unet.py"))
+STAGED = os.path.join(ROOT, "oracle", "_ref")          # byte copies staged by __graft_entry__.build() (oracle/stage_ref_scripts.py)
+HAVE_REF = os.path.exists(os.path.join(STAGED, "animatediff", "models", "unet.py"))
 
 SCRIPT = r"""
 import sys, torch
@@ -50,9 +51,10 @@ def test_chunked_sdpa_stand_in_equals_unchunked(monkeypatch):
     monkeypatch.delitem(sys.modules, "xformers.ops", raising=False)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree / staged copy not present")
+@pytest.mark.skipif(not HAVE_REF, reason="staged copy of the reference not present")
 def test_reference_trajectory_reproduces_the_oracle_loop():
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
+    env["FYC_REFERENCE_ROOT"] = STAGED
     r = subprocess.run([sys.executable, "-c", SCRIPT], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     rel = float([l for l in r.stdout.splitlines() if l.startswith("REL")][-1].split()[1])

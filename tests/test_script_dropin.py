@@ -26,7 +26,7 @@ import torch
 
 import script_env as E
 
-pytestmark = pytest.mark.skipif(not os.path.exists(E.REF_SCRIPT), reason="the reference tree (/root/reference) is not on this box")
+pytestmark = pytest.mark.skipif(not os.path.exists(E.REF_SCRIPT), reason="the reference's scripts are not staged under oracle/_ref/ (__graft_entry__.build() stages them)")
 
 PROMPT = "a corgi waving its tail"
 

@@ -4,7 +4,7 @@ O=gpurun_out/r6
 mkdir -p $O
 run() { # tag, env...
   tag=$1; shift
-  env "$@" FYC_BENCH_SHAPES=$O/shapes_env_$tag.txt timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $O/bench_env_$tag.json 2> $O/bench_env_$tag.err
+  env "$@" FYC_BENCH_SHAPES=$O/shapes_env_$tag.txt timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $O/bench_env_$tag.json 2> $O/bench_env_$tag.err
   python - $O/bench_env_$tag.json $tag <<'PY'
 import json,sys
 try:

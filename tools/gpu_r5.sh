@@ -20,8 +20,8 @@ for sec in "$@"; do
       tail -n +1 $OUT/probe_base.txt $OUT/probe_il_skew*.txt | cut -c1-110 ;;
     il_bench)     # whole-loop A/B inside one call
       for i in 1 2; do
-        timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_base_$i.json 2> $OUT/bench_base_$i.err
-        FYC_LIB_PATH=$IL timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_il_$i.json 2> $OUT/bench_il_$i.err
+        timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_base_$i.json 2> $OUT/bench_base_$i.err
+        FYC_LIB_PATH=$IL timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_il_$i.json 2> $OUT/bench_il_$i.err
       done
       for f in $OUT/bench_base_*.json $OUT/bench_il_*.json; do python - "$f" <<'PY'
 import json,sys
@@ -52,8 +52,8 @@ PY
       done | tee $OUT/attn_ab.txt ;;
     bench_ab)     # whole loop: base library vs the in-tree one, alternating
       for i in 1 2; do
-        FYC_LIB_PATH=tools/exp/libfyc_base.so timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_ab_base_$i.json 2> $OUT/bench_ab_base_$i.err
-        timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_ab_new_$i.json 2> $OUT/bench_ab_new_$i.err
+        FYC_LIB_PATH=tools/exp/libfyc_base.so timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_ab_base_$i.json 2> $OUT/bench_ab_base_$i.err
+        timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity > $OUT/bench_ab_new_$i.json 2> $OUT/bench_ab_new_$i.err
       done
       for f in $OUT/bench_ab_*.json; do python - "$f" <<'PY'
 import json,sys
@@ -71,7 +71,7 @@ PY
       timeout 600 python -m oracle.gpu_reference --json --attention sdpa --dtype f16 2>&1 | grep GPU_REFERENCE | tee -a $OUT/gpu_reference.txt
       cp gpurun_out/parity_report.txt $OUT/parity_report_ref.txt 2>/dev/null ;;
     bench)        # the driver's own command
-      timeout 1500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 3000 $OUT/bench_default.json ;;
+      timeout 1500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 3000 $OUT/bench_default.json ;;
     tests)        # the driver's GPU tier, with the slowest items listed
       timeout 1500 python -m pytest tests -m gpu -x -q --durations=40 2>&1 | tail -60 | tee $OUT/gpu_tests.txt ;;
     *) echo "unknown section $sec" ;;

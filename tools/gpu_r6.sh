@@ -27,13 +27,13 @@ for sec in "$@"; do
     tests_new)    # only the tests this round added / moved
       timeout 900 python -m pytest tests -x -q -m gpu -k "split_k or non_finite or clipped_model_output or reference_gpu" --durations=10 2>&1 | tail -30 | tee $OUT/tests_new.txt ;;
     bench)        # the driver's command
-      timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err; benchline $OUT/bench_default.json ;;
+      timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err; benchline $OUT/bench_default.json ;;
     bench_quick)
-      timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_quick.json 2> $OUT/bench_quick.err; benchline $OUT/bench_quick.json ;;
+      timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_quick.json 2> $OUT/bench_quick.err; benchline $OUT/bench_quick.json ;;
     bench_ab)     # whole loop: base library vs the in-tree one, alternating
       for i in 1 2; do
-        FYC_BENCH_SHAPES=$OUT/shapes_base_$i.txt FYC_LIB_PATH=$BASE timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_ab_base_$i.json 2> $OUT/bench_ab_base_$i.err
-        FYC_BENCH_SHAPES=$OUT/shapes_new_$i.txt timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_ab_new_$i.json 2> $OUT/bench_ab_new_$i.err
+        FYC_BENCH_SHAPES=$OUT/shapes_base_$i.txt FYC_LIB_PATH=$BASE timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_ab_base_$i.json 2> $OUT/bench_ab_base_$i.err
+        FYC_BENCH_SHAPES=$OUT/shapes_new_$i.txt timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_ab_new_$i.json 2> $OUT/bench_ab_new_$i.err
       done
       benchline $OUT/bench_ab_*.json | tee $OUT/bench_ab.txt
       python - $OUT <<'PY' | tee $OUT/shapes_ab.txt
@@ -119,13 +119,13 @@ PY
     libs_bench)   # whole loop, per-shape, alternating over LIBS (2 passes)
       for i in 1 2; do for lib in ${LIBS}; do
         tag=$(basename $lib .so)_$i
-        FYC_LIB_PATH=$lib FYC_BENCH_SHAPES=$OUT/shapes_lib_$tag.txt timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_lib_$tag.json 2> $OUT/bench_lib_$tag.err
+        FYC_LIB_PATH=$lib FYC_BENCH_SHAPES=$OUT/shapes_lib_$tag.txt timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_lib_$tag.json 2> $OUT/bench_lib_$tag.err
       done; done
       benchline $OUT/bench_lib_*.json | tee $OUT/bench_libs.txt ;;
     keys_ab)      # in-pipeline per-shape times of the in-tree library under tuning keys (KEYS="12=1 13=1 12=1,13=1")
       for k in "" ${KEYS:-12=1 13=1}; do
         tag=$(echo "x$k" | tr '=,' '__')
-        FYC_TUNING=$k FYC_BENCH_SHAPES=$OUT/shapes_keys_$tag.txt timeout 600 python bench.py --steps ${KEYS_STEPS:-2} --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_keys_$tag.json 2> $OUT/bench_keys_$tag.err
+        FYC_TUNING=$k FYC_BENCH_SHAPES=$OUT/shapes_keys_$tag.txt timeout 600 python bench.py --full --steps ${KEYS_STEPS:-2} --warmup 1 --no-cpu-baseline --no-gpu-reference --no-parity --no-vae > $OUT/bench_keys_$tag.json 2> $OUT/bench_keys_$tag.err
       done
       benchline $OUT/bench_keys_*.json
       python - $OUT <<'PY' | tee $OUT/shapes_keys.txt

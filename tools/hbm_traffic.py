@@ -3,7 +3,7 @@ launch -> profiles/rNN_hbm_traffic.json, which bench.py reports as roofline.traf
 `source_sha256` is the digest of the sources that library was built from (followyourclick_amd/_build.py::source_digest).
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_fetch -o f -- python bench.py --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline --no-roofline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_fetch -o f -- python bench.py --full --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline --no-roofline
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_write -o w -- python bench.py ... (same)
     python tools/hbm_traffic.py OUT/pmc_fetch OUT/pmc_write profiles/r02_hbm_traffic.json
 

@@ -1,4 +1,4 @@
-"""Where does the HOST spend a DDIM step?  (bench.py reports host_launch_ms_per_ddim_step close to the GPU's time per step.)
+"""Where does the HOST spend a DDIM step?  (bench.py --full reports host_launch_ms_per_ddim_step close to the GPU's time per step.)
 cProfile over a few steps of the bench workload + the same steps with the launches themselves stubbed out (pure Python cost)."""
 import cProfile, pstats, io, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
