@@ -36,7 +36,7 @@ class AttnArgs(C.Structure):
     _fields_ = [("q", vp), ("k", vp), ("vt", vp), ("o", vp),
                 ("batch", i32), ("heads", i32), ("n_q", i32), ("n_k", i32), ("d", i32),
                 ("ldo", i32), ("ldvt", i32), ("kv_batch_div", i32), ("o_accumulate", i32),
-                ("scale", f32), ("o_scale", f32), ("dtype", i32)]
+                ("scale", f32), ("o_scale", f32), ("dtype", i32), ("q_batch_mod", i32)]
 
 
 class TAttnArgs(C.Structure):
@@ -61,7 +61,8 @@ class ChanStatsReduceArgs(C.Structure):
 class GnApplyCsArgs(C.Structure):
     _fields_ = [("x1", vp), ("cs1", vp), ("x2", vp), ("cs2", vp), ("gamma", vp), ("beta", vp), ("y", vp),
                 ("C1", i32), ("C2", i32), ("rows", i32), ("groups", i32), ("rows_per_sample", i32), ("eps", f32), ("silu", i32),
-                ("dtype", i32), ("cs_rows", i32)]
+                ("dtype", i32), ("cs_rows", i32), ("parts1", vp), ("parts2", vp),
+                ("tile_rows1", i32), ("slots1", i32), ("tile_rows2", i32), ("slots2", i32), ("parts_cs_rows", i32)]
 
 
 class LayerNormArgs(C.Structure):
@@ -79,6 +80,10 @@ class SoftmaxArgs(C.Structure):
 
 class ConcatArgs(C.Structure):
     _fields_ = [("a", vp), ("b", vp), ("y", vp), ("rows", i64), ("c1", i32), ("c2", i32), ("dtype", i32)]
+
+
+class RepeatArgs(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("bytes", i64), ("times", i32)]
 
 
 class SiluArgs(C.Structure):
@@ -134,7 +139,7 @@ class FFBlockArgs(C.Structure):
 class PanelLinearArgs(C.Structure):
     _fields_ = [("x", vp), ("residual", vp), ("out", vp), ("wstream", vp), ("bias", vp), ("gn_cs", vp), ("gn_gamma", vp), ("gn_beta", vp),
                 ("gn_rows_per_sample", i32), ("gn_stat_samples", i32), ("gn_groups", i32), ("gn_eps", C.c_float),
-                ("rows", i32), ("N", i32), ("K", i32), ("dtype", i32)]
+                ("rows", i32), ("N", i32), ("K", i32), ("dtype", i32), ("gn_parts", vp), ("gn_tile_rows", i32), ("gn_slots", i32)]
 
 
 class PackConv3x3Args(C.Structure):
@@ -155,13 +160,13 @@ OPS = {
     "fyc_embed_tokens": EmbedArgs, "fyc_patchify": PatchifyArgs, "fyc_row_stats": RowStatsArgs,
     "fyc_gn_apply_cs": GnApplyCsArgs, "fyc_chan_stats_reduce": ChanStatsReduceArgs,
     "fyc_pack_conv3x3": PackConv3x3Args, "fyc_pack_geglu": PackGegluArgs, "fyc_temporal_block": TemporalBlockArgs,
-    "fyc_ff_block": FFBlockArgs, "fyc_panel_linear": PanelLinearArgs,
+    "fyc_ff_block": FFBlockArgs, "fyc_panel_linear": PanelLinearArgs, "fyc_repeat": RepeatArgs,
 }
 MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set_tuning", "fyc_gemm_row_parts", "fyc_gemm_stat_layout", "fyc_gemm_workspace_bytes", "fyc_gn_stats_workspace", "fyc_temporal_block_supported", "fyc_temporal_block_wstream_bytes",
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 301        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 302        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

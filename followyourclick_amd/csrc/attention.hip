@@ -11,10 +11,11 @@ extern "C" int fyc_attention(const fyc_attn_args* a, void* stream) {
   FYC_REQUIRE(a->ldvt % 8 == 0 && a->ldvt >= a->n_k, "fyc_attention: ldvt=%d must be a multiple of 8 and >= n_k", a->ldvt);
   FYC_REQUIRE(a->ldo % 4 == 0, "fyc_attention: ldo must be a multiple of 4");
   FYC_REQUIRE(a->kv_batch_div >= 1, "fyc_attention: kv_batch_div");
+  FYC_REQUIRE(a->q_batch_mod >= 0 && a->q_batch_mod <= a->batch, "fyc_attention: q_batch_mod %d (0 .. batch)", a->q_batch_mod);
   fyca::AttnP p;
   p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.vt = (const bf16_t*)a->vt; p.o = (bf16_t*)a->o;
   p.batch = a->batch; p.heads = a->heads; p.n_q = a->n_q; p.n_k = a->n_k; p.d = a->d; p.ldo = a->ldo; p.ldvt = a->ldvt;
-  p.kv_batch_div = a->kv_batch_div; p.o_accumulate = a->o_accumulate;
+  p.kv_batch_div = a->kv_batch_div; p.o_accumulate = a->o_accumulate; p.q_batch_mod = a->q_batch_mod;
   p.sl2e = a->scale * 1.44269504088896340736f; p.o_scale = a->o_scale;
   p.nqb = 0; p.zero = (const char*)g_fyc_zero_page;
   hipStream_t st = (hipStream_t)stream;

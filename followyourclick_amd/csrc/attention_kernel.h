@@ -34,6 +34,7 @@ namespace fyca {
 struct AttnP {
   const bf16_t* q; const bf16_t* k; const bf16_t* vt; bf16_t* o;   // 16-bit elements of the kernel's T (bf16 or f16: same pointer arithmetic)
   int batch, heads, n_q, n_k, d, ldo, ldvt, kv_batch_div, o_accumulate;
+  int q_batch_mod;       // > 0: the q of batch element b is read from b % q_batch_mod (K / V / O stay per b)
   float sl2e, o_scale;   // scale * log2(e)
   int nqb;               // query blocks per (b,h)
   const char* zero;
@@ -161,7 +162,8 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
   }
   const int b = bh / p.heads, h = bh - b * p.heads;
   const int kvb = (b / p.kv_batch_div) * p.heads + h;
-  const T* Q = reinterpret_cast<const T*>(p.q) + (long long)bh * p.n_q * p.d;
+  const int bh_q = p.q_batch_mod > 0 ? (b % p.q_batch_mod) * p.heads + h : bh;
+  const T* Q = reinterpret_cast<const T*>(p.q) + (long long)bh_q * p.n_q * p.d;
   const T* K = reinterpret_cast<const T*>(p.k) + (long long)kvb * p.n_k * p.d;
   const T* VT = reinterpret_cast<const T*>(p.vt) + (long long)kvb * p.d * p.ldvt;
   const char* zero = p.zero;

@@ -19,6 +19,14 @@ __global__ void __launch_bounds__(256) concat_kernel(const T* __restrict__ a, co
   }
 }
 
+// dst = `times` back-to-back copies of src: every 16-byte chunk is read once and stored `times` times
+__global__ void __launch_bounds__(256) repeat_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, long long chunks, int times) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (long long)gridDim.x * 256) {
+    const u32x4 v = src[i];
+    for (int t = 0; t < times; ++t) dst[t * chunks + i] = v;
+  }
+}
+
 __global__ void __launch_bounds__(256) silu_kernel(const float* __restrict__ x, float* __restrict__ y, long long n) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) y[i] = silu_f(x[i]);
 }
@@ -230,6 +238,19 @@ extern "C" int fyc_concat_channels(const fyc_concat_args* a, void* stream) {
          hipLaunchKernelGGL(concat_kernel<f16_t>, dim3(grid_for(chunks)), dim3(256), 0, st, (const f16_t*)a->a, (const f16_t*)a->b, (f16_t*)a->y, chunks, a->c1 / 8, a->c2 / 8),
          hipLaunchKernelGGL(concat_kernel<float>, dim3(grid_for(chunks)), dim3(256), 0, st, (const float*)a->a, (const float*)a->b, (float*)a->y, chunks, a->c1 / 8, a->c2 / 8));
   FYC_CHECK_LAUNCH("fyc_concat_channels");
+  return 0;
+}
+
+extern "C" int fyc_repeat(const fyc_repeat_args* a, void* stream) {
+  FYC_REQUIRE(a && a->src && a->dst, "fyc_repeat: null pointer");
+  FYC_REQUIRE(a->bytes > 0 && a->bytes % 16 == 0 && a->times >= 1, "fyc_repeat: bytes %lld (multiple of 16), times %d", (long long)a->bytes, a->times);
+  FYC_REQUIRE((((uintptr_t)a->src | (uintptr_t)a->dst) & 15) == 0, "fyc_repeat: src / dst must be 16-byte aligned");
+  const char* s = (const char*)a->src;
+  const char* d = (const char*)a->dst;
+  FYC_REQUIRE(s + a->bytes <= d || d + a->bytes * a->times <= s, "fyc_repeat: src and dst overlap");
+  const long long chunks = a->bytes / 16;
+  hipLaunchKernelGGL(repeat_kernel, dim3(grid_for(chunks)), dim3(256), 0, (hipStream_t)stream, (const u32x4*)a->src, (u32x4*)a->dst, chunks, (int)a->times);
+  FYC_CHECK_LAUNCH("fyc_repeat");
   return 0;
 }
 

@@ -1,5 +1,6 @@
 // HBM-bound normalisation kernels (channels-last activations): GroupNorm statistics + apply(+SiLU),
 // LayerNorm(+positional table), row softmax.  All statistics in f32/f64; 16-byte vector I/O.
+#include "chan_parts.h"
 #include "fyc_common.h"
 
 namespace {
@@ -167,21 +168,34 @@ __global__ void __launch_bounds__(256) chan_stats_reduce_kernel(const float* __r
 // The sums come from the epilogues of the GEMMs / convs that produced x1 (and x2): no statistics pass over the tensor.
 // grid = (row chunks, samples).  Prologue: 8 lanes per group fold the group's channels (f64), every thread then keeps
 // scale = rstd*gamma and shift = beta - mean*scale of ITS 8 channels in registers; the loop is load - fma - (silu) - store.
+// A source whose sums were not reduced (cp.parts != null) is folded from the producer's row-tile partials right here
+// (fold_chan_parts): one fyc_chan_stats_reduce launch less where a sample spans few tiles.
 template <typename T>
 __global__ void __launch_bounds__(512) gn_apply_cs_kernel(const T* __restrict__ x1, const double* __restrict__ cs1, int C1,
                                                           const T* __restrict__ x2, const double* __restrict__ cs2, int C2,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           T* __restrict__ y, int groups, int rows_per_sample, int rows_per_block,
-                                                          float eps, int silu, int stat_samples) {
+                                                          float eps, int silu, int stat_samples, const ChanParts cp1, const ChanParts cp2,
+                                                          int parts_samples) {
   extern __shared__ float sh[];   // [2][groups]: mean, rstd
   const int tid = threadIdx.x, nthr = blockDim.x, C = C1 + C2, C8 = C >> 3, cpg = C / groups;
   const int sample = blockIdx.y;
   {
     const double inv_cnt = 1.0 / ((double)rows_per_sample * cpg);
+    ChanPartsRange pr1 = {}, pr2 = {};
+    if (cp1.parts != nullptr) pr1 = chan_parts_range(cp1, sample, parts_samples);
+    if (cp2.parts != nullptr) pr2 = chan_parts_range(cp2, sample, parts_samples);
     for (int gi = tid >> 3; gi < groups; gi += nthr >> 3) {
       double s = 0.0, q = 0.0;
       // the sums come per statistics sample (a frame); a GroupNorm sample spans `stat_samples` of them (cross-frame norms: F)
       for (int c = gi * cpg + (tid & 7); c < (gi + 1) * cpg; c += 8) {
+        const ChanParts& cp = c < C1 ? cp1 : cp2;
+        if (cp.parts != nullptr) {
+          double ps, pq;
+          fold_chan_parts(cp, c < C1 ? pr1 : pr2, c < C1 ? C1 : C2, c < C1 ? c : c - C1, ps, pq);
+          s += ps; q += pq;
+          continue;
+        }
         for (int f = 0; f < stat_samples; ++f) {
           const long long ss = (long long)sample * stat_samples + f;
           const double* src = c < C1 ? cs1 + (ss * C1 + c) * 2 : cs2 + (ss * C2 + (c - C1)) * 2;
@@ -425,14 +439,25 @@ extern "C" int fyc_chan_stats_reduce(const fyc_chan_stats_reduce_args* a, void* 
 }
 
 extern "C" int fyc_gn_apply_cs(const fyc_gn_apply_cs_args* a, void* stream) {
-  FYC_REQUIRE(a && a->x1 && a->cs1 && a->gamma && a->beta && a->y, "fyc_gn_apply_cs: null pointer");
-  FYC_REQUIRE((a->x2 == nullptr) == (a->C2 == 0) && (a->x2 == nullptr) == (a->cs2 == nullptr), "fyc_gn_apply_cs: x2 / cs2 / C2 must come together");
+  FYC_REQUIRE(a && a->x1 && a->gamma && a->beta && a->y, "fyc_gn_apply_cs: null pointer");
+  FYC_REQUIRE((a->cs1 != nullptr) != (a->parts1 != nullptr), "fyc_gn_apply_cs: x1 needs cs1 or parts1 (one of them)");
+  FYC_REQUIRE((a->x2 == nullptr) == (a->C2 == 0) && (a->x2 != nullptr) == ((a->cs2 != nullptr) != (a->parts2 != nullptr)) && !(a->cs2 && a->parts2),
+              "fyc_gn_apply_cs: x2 / C2 / (cs2 or parts2) must come together");
   const int C = a->C1 + a->C2;
   FYC_REQUIRE(a->C1 > 0 && a->C1 % 8 == 0 && a->C2 % 8 == 0 && a->groups > 0 && C % a->groups == 0 && C / 8 <= 512, "fyc_gn_apply_cs: C1=%d C2=%d groups=%d", a->C1, a->C2, a->groups);
   FYC_REQUIRE(a->rows_per_sample > 0 && a->rows % a->rows_per_sample == 0, "fyc_gn_apply_cs: rows=%d rows_per_sample=%d", a->rows, a->rows_per_sample);
   const int cs_rows = a->cs_rows > 0 ? a->cs_rows : a->rows_per_sample;
   FYC_REQUIRE(a->rows_per_sample % cs_rows == 0, "fyc_gn_apply_cs: rows_per_sample=%d is not a multiple of cs_rows=%d", a->rows_per_sample, cs_rows);
   const int stat_samples = a->rows_per_sample / cs_rows;
+  ChanParts cp1 = {a->parts1, a->tile_rows1, a->slots1, a->parts_cs_rows, a->rows}, cp2 = {a->parts2, a->tile_rows2, a->slots2, a->parts_cs_rows, a->rows};
+  int parts_samples = 1;
+  if (a->parts1 != nullptr || a->parts2 != nullptr) {
+    FYC_REQUIRE(a->parts_cs_rows > 0 && a->rows_per_sample % a->parts_cs_rows == 0, "fyc_gn_apply_cs: rows_per_sample=%d is not a multiple of parts_cs_rows=%d",
+                a->rows_per_sample, a->parts_cs_rows);
+    FYC_REQUIRE((a->parts1 == nullptr || (a->tile_rows1 > 0 && a->slots1 >= 1 && a->slots1 <= 4)) && (a->parts2 == nullptr || (a->tile_rows2 > 0 && a->slots2 >= 1 && a->slots2 <= 4)),
+                "fyc_gn_apply_cs: tile_rows / slots (1..4) of the partials (fyc_gemm_stat_layout)");
+    parts_samples = a->rows_per_sample / a->parts_cs_rows;
+  }
   hipStream_t st = (hipStream_t)stream;
   const int samples = a->rows / a->rows_per_sample;
   const int c8 = C / 8;
@@ -447,13 +472,13 @@ extern "C" int fyc_gn_apply_cs(const fyc_gn_apply_cs_args* a, void* stream) {
   const size_t sh = sizeof(float) * 2 * a->groups;
   if (a->dtype == FYC_BF16)
     hipLaunchKernelGGL(gn_apply_cs_kernel<bf16_t>, grid, dim3(nthr), sh, st, (const bf16_t*)a->x1, a->cs1, a->C1, (const bf16_t*)a->x2, a->cs2, a->C2,
-                       a->gamma, a->beta, (bf16_t*)a->y, a->groups, a->rows_per_sample, rpb, a->eps, a->silu, stat_samples);
+                       a->gamma, a->beta, (bf16_t*)a->y, a->groups, a->rows_per_sample, rpb, a->eps, a->silu, stat_samples, cp1, cp2, parts_samples);
   else if (a->dtype == FYC_F16)
     hipLaunchKernelGGL(gn_apply_cs_kernel<f16_t>, grid, dim3(nthr), sh, st, (const f16_t*)a->x1, a->cs1, a->C1, (const f16_t*)a->x2, a->cs2, a->C2,
-                       a->gamma, a->beta, (f16_t*)a->y, a->groups, a->rows_per_sample, rpb, a->eps, a->silu, stat_samples);
+                       a->gamma, a->beta, (f16_t*)a->y, a->groups, a->rows_per_sample, rpb, a->eps, a->silu, stat_samples, cp1, cp2, parts_samples);
   else if (a->dtype == FYC_F32)
     hipLaunchKernelGGL(gn_apply_cs_kernel<float>, grid, dim3(nthr), sh, st, (const float*)a->x1, a->cs1, a->C1, (const float*)a->x2, a->cs2, a->C2,
-                       a->gamma, a->beta, (float*)a->y, a->groups, a->rows_per_sample, rpb, a->eps, a->silu, stat_samples);
+                       a->gamma, a->beta, (float*)a->y, a->groups, a->rows_per_sample, rpb, a->eps, a->silu, stat_samples, cp1, cp2, parts_samples);
   else FYC_FAIL(-2, "fyc_gn_apply_cs: bad dtype");
   FYC_CHECK_LAUNCH("fyc_gn_apply_cs");
   return 0;

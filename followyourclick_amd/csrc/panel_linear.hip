@@ -19,6 +19,7 @@
 // Built for bf16, rows % 128 == 0, (K, N) in {320, 640}^2; other shapes keep fyc_gemm.  AGPR accumulators (see _build.py).
 #include <mutex>
 
+#include "chan_parts.h"
 #include "fyc_common.h"
 
 namespace {
@@ -37,7 +38,8 @@ struct PLP {
   const bf16_t* x; const bf16_t* res; bf16_t* out;
   const char* ws;                 // packed weight stream: (N / 320) passes x (K / 64) stages x 40 KiB
   const float* bias;              // [N] or null
-  const double* gn_cs;            // [samples * gn_stat_samples][K][2] channel {sum, sum sq} of x, or null: no GroupNorm
+  const double* gn_cs;            // [samples * gn_stat_samples][K][2] channel {sum, sum sq} of x, or null
+  ChanParts gn_parts;             // ... or the producer's row-tile partials (parts != null), folded in the prologue; both null: no GroupNorm
   const float* gn_gamma; const float* gn_beta;
   int gn_rows_per_sample, gn_stat_samples, gn_groups;
   float gn_eps;
@@ -96,17 +98,23 @@ __global__ void __launch_bounds__(NT) panel_linear_kernel(const PLP p) {
 #pragma unroll
   for (int n = 0; n < 10; ++n) dma_piece(0, n);
 
-  if (p.gn_cs != nullptr) {
+  if (p.gn_cs != nullptr || p.gn_parts.parts != nullptr) {
     // GroupNorm of the input on the operand registers.  Per-channel {scale, shift} of the tile's sample -> LDS table (the tile
     // region is idle here): thread c folds the statistics samples (frames) of the norm's sample, the cpg threads of a group meet in LDS.
     double* dsum = reinterpret_cast<double*>(tile);                  // [K][2]
     float* tab = reinterpret_cast<float*>(tile + K * 16);            // [K][2] = {scale, shift}
     const int sample = (int)(row0 / p.gn_rows_per_sample), cpg = K / p.gn_groups;
+    ChanPartsRange pr = {};
+    if (p.gn_parts.parts != nullptr) pr = chan_parts_range(p.gn_parts, sample, p.gn_stat_samples);
     for (int c = tid; c < K; c += NT) {
       double s = 0.0, q = 0.0;
-      for (int f = 0; f < p.gn_stat_samples; ++f) {
-        const double* src = p.gn_cs + (((long long)sample * p.gn_stat_samples + f) * K + c) * 2;
-        s += src[0]; q += src[1];
+      if (p.gn_parts.parts != nullptr) {
+        fold_chan_parts(p.gn_parts, pr, K, c, s, q);
+      } else {
+        for (int f = 0; f < p.gn_stat_samples; ++f) {
+          const double* src = p.gn_cs + (((long long)sample * p.gn_stat_samples + f) * K + c) * 2;
+          s += src[0]; q += src[1];
+        }
       }
       dsum[2 * c] = s; dsum[2 * c + 1] = q;
     }
@@ -235,7 +243,9 @@ extern "C" int64_t fyc_panel_linear_wstream_bytes(int32_t N, int32_t K) {
 extern "C" int fyc_panel_linear_supported(const fyc_panel_linear_args* a) {
   if (a == nullptr || (a->dtype != FYC_BF16 && a->dtype != FYC_F16) || a->rows <= 0 || a->rows % ROWS != 0) return 0;
   if (!((a->K == 320 || a->K == 640) && (a->N == 320 || a->N == 640))) return 0;
-  if (a->gn_cs != nullptr && (a->gn_rows_per_sample <= 0 || a->gn_rows_per_sample % ROWS != 0 || a->rows % a->gn_rows_per_sample != 0 ||
+  if (a->gn_cs != nullptr && a->gn_parts != nullptr) return 0;
+  if (a->gn_parts != nullptr && (a->gn_tile_rows <= 0 || a->gn_slots < 1 || a->gn_slots > 4 || a->gn_stat_samples <= 0 || a->gn_rows_per_sample % a->gn_stat_samples != 0)) return 0;
+  if ((a->gn_cs != nullptr || a->gn_parts != nullptr) && (a->gn_rows_per_sample <= 0 || a->gn_rows_per_sample % ROWS != 0 || a->rows % a->gn_rows_per_sample != 0 ||
                               a->gn_groups <= 0 || a->K % a->gn_groups != 0 || a->gn_stat_samples <= 0)) return 0;
   static std::mutex mu;
   static int64_t lds_cap = -1;
@@ -253,14 +263,15 @@ extern "C" int fyc_panel_linear(const fyc_panel_linear_args* a, void* stream) {
   FYC_REQUIRE(a && a->x && a->out && a->wstream, "fyc_panel_linear: null pointer");
   FYC_REQUIRE(fyc_panel_linear_supported(a), "fyc_panel_linear: built for bf16 / f16, rows %% 128 == 0, K and N in {320, 640}, GroupNorm samples of whole 128-row tiles (got rows=%d K=%d N=%d gn_rows_per_sample=%d)",
               a->rows, a->K, a->N, a->gn_rows_per_sample);
-  FYC_REQUIRE(a->gn_cs == nullptr || (a->gn_gamma != nullptr && a->gn_beta != nullptr), "fyc_panel_linear: gn_cs needs gn_gamma / gn_beta");
+  FYC_REQUIRE((a->gn_cs == nullptr && a->gn_parts == nullptr) || (a->gn_gamma != nullptr && a->gn_beta != nullptr), "fyc_panel_linear: gn_cs / gn_parts need gn_gamma / gn_beta");
   FYC_REQUIRE(a->x != a->out && a->residual != a->x, "fyc_panel_linear: out must not alias x (residual may alias out)");
   FYC_REQUIRE(((uintptr_t)a->x % 16) == 0 && ((uintptr_t)a->out % 16) == 0 && ((uintptr_t)a->wstream % 16) == 0 && ((uintptr_t)a->bias % 16) == 0 &&
-              ((uintptr_t)a->residual % 16) == 0 && ((uintptr_t)a->gn_cs % 16) == 0, "fyc_panel_linear: operands must be 16-byte aligned");
+              ((uintptr_t)a->residual % 16) == 0 && ((uintptr_t)a->gn_cs % 16) == 0 && ((uintptr_t)a->gn_parts % 8) == 0, "fyc_panel_linear: operands must be 16-byte aligned");
   PLP p;
   p.x = (const bf16_t*)a->x; p.res = (const bf16_t*)a->residual; p.out = (bf16_t*)a->out; p.ws = (const char*)a->wstream; p.bias = a->bias;
   p.gn_cs = a->gn_cs; p.gn_gamma = a->gn_gamma; p.gn_beta = a->gn_beta; p.gn_rows_per_sample = a->gn_rows_per_sample;
   p.gn_stat_samples = a->gn_stat_samples; p.gn_groups = a->gn_groups; p.gn_eps = a->gn_eps; p.N = a->N;
+  p.gn_parts = ChanParts{a->gn_parts, a->gn_tile_rows, a->gn_slots, a->gn_parts != nullptr ? a->gn_rows_per_sample / a->gn_stat_samples : 1, a->rows};
   hipStream_t st = (hipStream_t)stream;
   if (a->dtype == FYC_F16) {
     if (a->K == 320) return a->N == 320 ? launch<f16_t, 10, 1>(p, a->rows, st) : launch<f16_t, 10, 2>(p, a->rows, st);

@@ -86,7 +86,11 @@ class DDIMSampler:
         B, CL, F, H, W = latents.shape
         cp = pad_channels(u.cfg.conv_in_channels)
         dupn = 2 if st["cfg"] else 1
-        x = u.new(dupn * B * F * H * W, cp)
+        # the CFG halves differ in their text states only (`prepare` duplicates fps / flow / camera): where the engine can run the UNet
+        # up to the first cross-attention once, the input holds the B distinct clips and nothing is duplicated here
+        share = st["cfg"] and u.shares_prefix(dupn * B, st.get("temb_first"))
+        dupx = 1 if share else dupn
+        x = u.new(dupx * B * F * H * W, cp)
         if "temb_first" in st:
             latents[:, :, 0] = first_image_latents.reshape(B, CL, H, W)
         # (same precedence as UNet3DConfig.conv_in_channels / pack_unet and the reference's constructor, unet.py:114-126: the 8-channel
@@ -94,17 +98,20 @@ class DDIMSampler:
         if u.cfg.use_first_frame_condition_concat:
             # the reference's UNet concatenates `reference_images_latent` (the clean first-frame latents) beside EVERY frame's latents
             # (unet.py:580-586; pipeline_animation.py:705-706 passes the plain latents); conv_in's `/ 2` lives in its packed weights
-            o.unet_input(latents, None, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupn, mode=1)
+            o.unet_input(latents, None, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx, mode=1)
         elif u.cfg.use_first_frame_mask_condition_concat:
-            o.unet_input(latents, mask, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupn,
+            o.unet_input(latents, mask, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx,
                          mask_frames=1)
         else:
             # plain latents (the 2-D Stable Diffusion first-image path, reference pipeline_stable_diffusion.py:527-528)
             n = B * F * H * W
             frames = latents.permute(0, 2, 1, 3, 4).reshape(B * F, CL, H * W).contiguous()
-            for d in range(dupn):
+            for d in range(dupx):
                 o.nchw_to_nhwc(frames, x[d * n:(d + 1) * n], N=B * F, C_=CL, HW=H * W, c_pad=cp, scale=1.0)
-        pred = u.forward(x, st["temb"][i], dupn * B, F, H, W, temb_first=st.get("temb_first"))
+        if share:
+            pred = u.forward(x, st["temb"][i], dupn * B, F, H, W, shared_prefix=2)
+        else:
+            pred = u.forward(x, st["temb"][i], dupn * B, F, H, W, temb_first=st.get("temb_first"))
         single = None
         if "ctx_single" in st:      # per-frame unconditional pass: the first (unconditional) half of x as B*F one-frame clips
             u.ctx_cache = st["ctx_single"]

@@ -7,6 +7,10 @@ unet_blocks.py:342-360/482-529/604-632/749-809/880-905, resnet.py:296-342, atten
   * activations live as [B*F*H*W][C] (channels-last == token-major), so every `rearrange`/`permute`
     of the reference is free; only the 9-channel model input and the 4-channel prediction cross the
     (b,c,f,h,w) boundary (ops.unet_input / ops.cfg_ddim_step);
+  * the two halves of a classifier-free-guidance pair differ in their text states only, and text first enters at attn2 of the
+    first transformer: with `shared_prefix=2` everything in front of that (conv_in, the first ResNet, proj_in, the spatial
+    self-attention, attn2's q projection) runs once on the B/2 distinct clips; three activations (conv_in's output, the ResNet's
+    output, attn1's output) are broadcast to the full batch by fyc_repeat and attn2 reads the shared queries (q_batch_mod);
   * text (and IP) keys/values do not depend on the timestep or the frame: they are projected once
     per clip (`prepare_context`) instead of F*steps times (reference attention.py:264 repeats them);
   * all time-embedding work (3 sinusoid MLPs + the 22 ResnetBlock3D.time_emb_proj) is done for every
@@ -40,16 +44,31 @@ FUSE_PANEL = os.environ.get("FYC_FUSE_PANEL", "1") != "0"         # fyc_panel_li
 # the plain / residual K <= 640 projections through fyc_panel_linear as well: measured equal to fyc_gemm (98 vs 91 us at the 64x64
 # level, 60 vs 61 at 32x32: one workgroup per CU leaves its memory phases exposed, profiles/r03_panel_linear_probe.txt) - off
 PANEL_ALL = os.environ.get("FYC_PANEL_ALL", "0") != "0"
+# the CFG pair runs the UNet up to the first cross-attention once (forward(shared_prefix=2)); FYC_CFG_SHARE=0: everything at the full batch
+CFG_SHARE = os.environ.get("FYC_CFG_SHARE", "1") != "0"
+# a GroupNorm consumer (fyc_gn_apply_cs, fyc_panel_linear) folds the row-tile partials of its producer in its own prologue instead of
+# reading sums a fyc_chan_stats_reduce launch prepared - where one block re-reads at most DIRECT_STATS_BYTES of partials (cut-off measured,
+# profiles/direct_stats_cutoff.txt).  Measured level in the pipeline (+0.02 frames/s, profiles/cfg_share_ab.txt): off unless FYC_DIRECT_STATS=1
+DIRECT_STATS = os.environ.get("FYC_DIRECT_STATS", "0") != "0"
+DIRECT_STATS_BYTES = int(os.environ.get("FYC_DIRECT_STATS_BYTES", str(24 << 10)))
 FUSE_ROWS = os.environ.get("FYC_FUSE_ROWS", "0") != "0"      # the LayerNorm half (row_parts): measured slower than the separate fyc_row_stats pass (profiles/r02_stats_fusion_ab.txt), off by default
 
 
 class Act:
-    """an activation [rows][C] plus what its producer already knows about it: `cs` = per-(frame, channel) {sum, sum of
-    squares} ([rows / cs_rows][C][2] f64), `rp` = per-row partial {sum, sum sq} ([rows][rp_n][2] f32)"""
-    __slots__ = ("t", "C", "cs", "cs_rows", "rp", "rp_n")
+    """an activation [rows][C] plus what its producer already knows about it: `plan` = (parts, tile_rows, slots, rows, stat_rows), the
+    row-tile partial {sum, sum of squares} per channel its epilogue wrote with stat_rows rows per statistics sample (a frame);
+    `cs` = the same folded to per-(sample of cs_rows rows, channel) f64 sums ([rows / cs_rows][C][2]) - made from the plan only when a
+    consumer asks for it (UNet3DEngine._stats), many consumers fold the partials themselves; `rp` = per-row partial {sum, sum sq}
+    ([rows][rp_n][2] f32)"""
+    __slots__ = ("t", "C", "cs", "cs_rows", "rp", "rp_n", "plan")
 
-    def __init__(self, t: Tensor, C: int, cs: Optional[Tensor] = None, cs_rows: int = 0, rp: Optional[Tensor] = None, rp_n: int = 0):
-        self.t, self.C, self.cs, self.cs_rows, self.rp, self.rp_n = t, C, cs, cs_rows, rp, rp_n
+    def __init__(self, t: Tensor, C: int, cs: Optional[Tensor] = None, cs_rows: int = 0, rp: Optional[Tensor] = None, rp_n: int = 0,
+                 plan=None):
+        self.t, self.C, self.cs, self.cs_rows, self.rp, self.rp_n, self.plan = t, C, cs, cs_rows, rp, rp_n, plan
+
+    @property
+    def has_stats(self) -> bool:
+        return self.cs is not None or self.plan is not None
 
 
 def sinusoid_host(values: Sequence[float], dim: int) -> Tensor:
@@ -83,6 +102,7 @@ class UNet3DEngine(EngineBase):
         self.ctx_cache = None
         self.fuse_stats = FUSE_STATS
         self.fuse_rows = FUSE_STATS and FUSE_ROWS
+        self.direct_stats = DIRECT_STATS and bool(getattr(self.ops, "direct_stats_supported", False))
         self.ops.ensure_init(self.device)
 
     # ---- once per clip ---------------------------------------------------------------------
@@ -159,10 +179,15 @@ class UNet3DEngine(EngineBase):
 
     # ---- attention cores -----------------------------------------------------------------------
     def _attend(self, q: Tensor, k: Tensor, vt: Tensor, out: Tensor, *, batch: int, n_q: int, n_k: int, d: int, ldvt: int,
-                C: int, kv_div: int, accumulate: bool = False, o_scale: float = 1.0) -> None:
+                C: int, kv_div: int, accumulate: bool = False, o_scale: float = 1.0, q_mod: int = 0) -> None:
+        """q_mod > 0: q holds q_mod batch elements, element b attends with the queries of b % q_mod (shared CFG prefix)"""
         H, o = self.heads, self.ops
         scale = d ** -0.5
         if not self.mat_attn:
+            if q_mod:
+                o.attention(q, k, vt, out, batch=batch, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldvt, scale=scale,
+                            kv_batch_div=kv_div, accumulate=accumulate, o_scale=o_scale, q_batch_mod=q_mod)
+                return
             o.attention(q, k, vt, out, batch=batch, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldvt, scale=scale,
                         kv_batch_div=kv_div, accumulate=accumulate, o_scale=o_scale)
             return
@@ -172,7 +197,7 @@ class UNet3DEngine(EngineBase):
         for b in range(batch):
             kb = b // kv_div
             S = self.zeros(H, n_q, ldS)
-            o.gemm(q[b], k[kb], S, M=n_q, N=n_k, K=d, lda=d, ldw=d, ldo=ldS, batch=H, stride_a=n_q * d, stride_w=n_k * d,
+            o.gemm(q[b % q_mod if q_mod else b], k[kb], S, M=n_q, N=n_k, K=d, lda=d, ldw=d, ldo=ldS, batch=H, stride_a=n_q * d, stride_w=n_k * d,
                    stride_o=n_q * ldS, out_scale=scale)
             o.softmax_rows(S, rows=H * n_q, cols=n_k, ld=ldS)
             dst = out[b * n_q:(b + 1) * n_q]
@@ -198,21 +223,56 @@ class UNet3DEngine(EngineBase):
         reference unet_blocks.py:763,885).  Returns (normalised tensor, materialised concat or None)."""
         o = self.ops
         if isinstance(x, Act):
-            if x.cs is not None and rows_per_sample % x.cs_rows == 0:
+            if x.has_stats and rows_per_sample % x.cs_rows == 0:
                 y = self.new(rows, x.C)
-                o.gn_apply_cs(x.t, x.cs, gamma, beta, y, rows=rows, C1=x.C, groups=self.groups, rows_per_sample=rows_per_sample,
+                d = self._direct((x,), rows_per_sample)
+                if d is not None:
+                    parts, tr, sl, _, srows = x.plan
+                    o.gn_apply_cs(x.t, None, gamma, beta, y, rows=rows, C1=x.C, groups=self.groups, rows_per_sample=rows_per_sample,
+                                  eps=eps, silu=silu, parts1=parts, tile_rows1=tr, slots1=sl, parts_cs_rows=srows)
+                    return y, None
+                o.gn_apply_cs(x.t, self._stats(x), gamma, beta, y, rows=rows, C1=x.C, groups=self.groups, rows_per_sample=rows_per_sample,
                               eps=eps, silu=silu, cs_rows=x.cs_rows)
                 return y, None
             return self.group_norm(x.t, gamma, beta, rows, x.C, rows_per_sample, eps, silu), None
         a, b = x
-        if a.cs is not None and b.cs is not None and a.cs_rows == b.cs_rows and rows_per_sample % a.cs_rows == 0:
+        if a.has_stats and b.has_stats and a.cs_rows == b.cs_rows and rows_per_sample % a.cs_rows == 0:
             y = self.new(rows, a.C + b.C)
-            o.gn_apply_cs(a.t, a.cs, gamma, beta, y, rows=rows, C1=a.C, groups=self.groups, rows_per_sample=rows_per_sample,
-                          eps=eps, silu=silu, x2=b.t, cs2=b.cs, C2=b.C, cs_rows=a.cs_rows)
+            if self._direct((a, b), rows_per_sample) is not None:      # both sources from their partials (same rows per statistics sample)
+                (p1, tr1, sl1, _, srows), (p2, tr2, sl2, _, _) = a.plan, b.plan
+                o.gn_apply_cs(a.t, None, gamma, beta, y, rows=rows, C1=a.C, groups=self.groups, rows_per_sample=rows_per_sample,
+                              eps=eps, silu=silu, x2=b.t, C2=b.C, parts1=p1, tile_rows1=tr1, slots1=sl1, parts2=p2, tile_rows2=tr2,
+                              slots2=sl2, parts_cs_rows=srows)
+                return y, None
+            o.gn_apply_cs(a.t, self._stats(a), gamma, beta, y, rows=rows, C1=a.C, groups=self.groups, rows_per_sample=rows_per_sample,
+                          eps=eps, silu=silu, x2=b.t, cs2=self._stats(b), C2=b.C, cs_rows=a.cs_rows)
             return y, None
         cat = self.new(rows, a.C + b.C)
         o.concat_channels(a.t, b.t, cat, rows=rows, c1=a.C, c2=b.C)
         return self.group_norm(cat, gamma, beta, rows, a.C + b.C, rows_per_sample, eps, silu), cat
+
+    def _stats(self, x: Act) -> Tensor:
+        """the reduced f64 sums of x at its consumer's granularity: one fyc_chan_stats_reduce launch, on first use"""
+        if x.cs is None:
+            parts, tile_rows, slots, rows, stat_rows = x.plan
+            x.cs = self._cs_finish((parts, tile_rows, slots), rows, stat_rows, x.C, x.cs_rows)
+        return x.cs
+
+    def _direct(self, xs: Tuple[Act, ...], rows_per_sample: int) -> Optional[int]:
+        """bytes of partials one consumer block reads when it folds the row-tile partials of `xs` itself, or None where it should not:
+        sums already reduced, sources with different statistics samples, or more than DIRECT_STATS_BYTES per block (the wide clip-level
+        norms of the 64x64 and 32x32 levels: hundreds of KB per block against one small launch)"""
+        if not self.direct_stats or any(x.plan is None or x.cs is not None for x in xs):
+            return None
+        srows = xs[0].plan[4]
+        if any(x.plan[4] != srows for x in xs) or rows_per_sample % srows:
+            return None
+        nbytes = 0
+        for x in xs:
+            _, tile_rows, slots, _, _ = x.plan
+            tiles = rows_per_sample // tile_rows if rows_per_sample % tile_rows == 0 else (rows_per_sample - 1) // tile_rows + 2
+            nbytes += max(tiles, 1) * slots * x.C * 8
+        return nbytes if nbytes <= DIRECT_STATS_BYTES else None
 
     def _lin_rp(self, x: Tensor, w: Tensor, rows: int, bias=None, residual=None) -> Act:
         """Linear whose output feeds a (folded) LayerNorm: the epilogue also writes the per-row partial sums"""
@@ -241,9 +301,17 @@ class UNet3DEngine(EngineBase):
         """GroupNorm -> proj_in of a transformer / motion module (reference attention.py:269-270, motion_module.py:188-191).  With the
         producer's channel sums at hand the norm is applied to fyc_panel_linear's operand registers: no normalised tensor in HBM."""
         C = node.C
-        if (FUSE_PANEL and isinstance(x, Act) and x.cs is not None and not self.fuse_rows and rows_per_sample % x.cs_rows == 0
+        if (FUSE_PANEL and isinstance(x, Act) and x.has_stats and not self.fuse_rows and rows_per_sample % x.cs_rows == 0
                 and self.ops.panel_linear_supported(self.dtype, rows=rows, N=C, K=C, gn_rows_per_sample=rows_per_sample, gn_groups=self.groups)):
             out = self.new(rows, C)
+            if self._direct((x,), rows_per_sample) is not None:
+                parts, tr, sl, _, srows = x.plan
+                self.ops.panel_linear(x.t, out, wstream=self._panel_stream(node.pin_w), rows=rows, N=C, K=C, bias=node.pin_b, gn_parts=parts,
+                                      gn_tile_rows=tr, gn_slots=sl, gn_gamma=node.norm_g, gn_beta=node.norm_b,
+                                      gn_rows_per_sample=rows_per_sample, gn_stat_samples=rows_per_sample // srows, gn_groups=self.groups,
+                                      gn_eps=1e-6)
+                return Act(out, C)
+            self._stats(x)
             self.ops.panel_linear(x.t, out, wstream=self._panel_stream(node.pin_w), rows=rows, N=C, K=C, bias=node.pin_b, gn_cs=x.cs,
                                   gn_gamma=node.norm_g, gn_beta=node.norm_b, gn_rows_per_sample=rows_per_sample,
                                   gn_stat_samples=rows_per_sample // x.cs_rows, gn_groups=self.groups, gn_eps=1e-6)
@@ -290,7 +358,16 @@ class UNet3DEngine(EngineBase):
         rows = frames * Ho * Wo
         plan = self._cs_plan(rows, nxt[0], Cout, K, L.GEMM_CONV3X3_UP2 if kw.get("up2") else L.GEMM_CONV3X3) if nxt else None
         out = self.conv(x, w, b, frames, Hin, Win, chan_parts=None if plan is None else plan[0], cs_rows=nxt[0] if plan is not None else 0, **kw)
-        return Act(out, Cout, None if plan is None else self._cs_finish(plan, rows, nxt[0], Cout, nxt[1]), nxt[1] if nxt else 0)
+        return self._act(out, Cout, plan, rows, nxt)
+
+    def _act(self, out: Tensor, C: int, plan, rows: int, nxt, rp=None, rp_n: int = 0) -> Act:
+        """the output of a producer that wrote row-tile partials `plan` (EngineBase._cs_plan, or None) for the norm `nxt` describes"""
+        if plan is None:
+            return Act(out, C, None, nxt[1] if nxt else 0, rp, rp_n)
+        a = Act(out, C, None, nxt[1], rp, rp_n, plan=(plan[0], plan[1], plan[2], rows, nxt[0]))
+        if not self.direct_stats:
+            self._stats(a)          # the reduce launch right behind its producer, as before
+        return a
 
     def resnet(self, r: Packed, x: Union[Act, Tuple[Act, Act]], temb: Tensor, g: dict, nxt: Tuple[int, int]) -> Act:
         """ResnetBlock3D (reference resnet.py:296-342): cross-frame GroupNorm statistics.  x may be the (hidden, skip) pair of an
@@ -330,8 +407,7 @@ class UNet3DEngine(EngineBase):
             parts = self.new(rows // 128 * C * 2, dtype=torch.float32) if cs_rows else None
             self.ops.ff_block(tok.t, residual, out, wstream=ff["_wstream"], b_out=ff.po_b, rows=rows, C_=C, hidden=hidden,
                               chan_parts=parts, cs_rows=cs_rows)
-            cs = self._cs_finish((parts, 128, 1), rows, nxt[0], C, nxt[1]) if cs_rows else None
-            return Act(out, C, cs, nxt[1] if cs_rows else 0)
+            return self._act(out, C, (parts, 128, 1) if cs_rows else None, rows, nxt if cs_rows else None)
         if ff.cs1 is not None:      # LayerNorm folded into FF1: statistics from the producer of tok (or one statistics pass)
             N1 = ff.w1.shape[0]
             hmid = self.new(rows, N1 // 2)
@@ -350,12 +426,21 @@ class UNet3DEngine(EngineBase):
         self.ops.gemm(tok.t, ff.po_w, out, M=rows, N=C, K=K, lda=C, ldw=K, ldo=C, bias=ff.po_b, residual=residual, ldr=C,
                       a2=hmid, k_split=C, lda2=K - C, chan_parts=None if plan is None else plan[0], cs_rows=nxt[0] if plan is not None else 0,
                       row_parts=rp, row_nparts=rp_n)
-        return Act(out, C, None if plan is None else self._cs_finish(plan, rows, nxt[0], C, nxt[1]), nxt[1] if nxt else 0, rp, rp_n)
+        return self._act(out, C, plan, rows, nxt, rp, rp_n)
 
-    def transformer(self, t: Packed, x: Act, g: dict, nxt: Tuple[int, int]) -> Act:
-        """Transformer3DModel + BasicTransformerBlock (reference attention.py:217-308, 489-564)."""
-        rows, C, H, o = g["rows"], t.C, self.heads, self.ops
-        BF, N = g["B"] * g["F"], g["H"] * g["W"]
+    def _repeat(self, t: Tensor, times: int) -> Tensor:
+        """`times` copies of t along its first axis (the shared CFG prefix, broadcast to the full batch)"""
+        out = self.new(times * t.shape[0], *t.shape[1:], dtype=t.dtype)
+        self.ops.repeat(t, out, times=times)
+        return out
+
+    def transformer(self, t: Packed, x: Act, g: dict, nxt: Tuple[int, int], share: int = 1) -> Act:
+        """Transformer3DModel + BasicTransformerBlock (reference attention.py:217-308, 489-564).
+        share = 2: x holds the first 1 / share of the batch `g` describes, the rest being copies of it (the CFG pair).  Everything in
+        front of the cross-attention core runs on that part alone; attn2 reads the shared queries for every batch element."""
+        rows_full, C, H, o = g["rows"], t.C, self.heads, self.ops
+        BF_full, N = g["B"] * g["F"], g["H"] * g["W"]
+        rows, BF = rows_full // share, BF_full // share
         d = C // H
         tok = self._norm_proj_in(x, t, rows, N)
         # --- attn1: spatial self-attention
@@ -384,12 +469,16 @@ class UNet3DEngine(EngineBase):
             o.gemm(n2, t.q2_w, None, M=rows, N=C, K=C, lda=C, ldw=C, epilogue=L.EPI_HEADS, heads=hd2)
         cache = self.ctx_cache[t.idx]
         kt, vtt, ldt = cache["text"]
+        q_mod = 0
+        if share > 1:       # from here on the halves differ (text K / V): the two residual streams at the full batch, q2 stays shared
+            tok, x = Act(self._repeat(tok.t, share), C), Act(self._repeat(x.t, share), C)
+            rows, BF, q_mod = rows_full, BF_full, BF
         att2 = self.new(rows, C)
-        self._attend(q2, kt, vtt, att2, batch=BF, n_q=N, n_k=cache["n_text"], d=d, ldvt=ldt, C=C, kv_div=g["F"])
+        self._attend(q2, kt, vtt, att2, batch=BF, n_q=N, n_k=cache["n_text"], d=d, ldvt=ldt, C=C, kv_div=g["F"], q_mod=q_mod)
         if cache["ip"] is not None:
             ki, vti, ldi = cache["ip"]
             self._attend(q2, ki, vti, att2, batch=BF, n_q=N, n_k=cache["n_ip"], d=d, ldvt=ldi, C=C, kv_div=g["F"],
-                         accumulate=True, o_scale=self.cfg.ip_scale)
+                         accumulate=True, o_scale=self.cfg.ip_scale, q_mod=q_mod)
         tok = self._lin_rp(att2, t.o2_w, rows, bias=t.o2_b, residual=tok.t)
         return self.feed_forward_out(t.ff, t.ln3, tok, x.t, rows, C, nxt)
 
@@ -429,13 +518,32 @@ class UNet3DEngine(EngineBase):
         return tok
 
     # ---- forward -------------------------------------------------------------------------------
-    def forward(self, x: Tensor, temb: Tensor, B: int, F: int, H: int, W: int, temb_first: Optional[Tensor] = None) -> Tensor:
+    def shares_prefix(self, B: int, temb_first: Optional[Tensor] = None) -> bool:
+        """whether forward(shared_prefix=2) at batch B (CFG duplicate included) runs the shared-prefix schedule"""
+        l0 = self.P.down[0].layers[0] if self.P.down and self.P.down[0].layers else None
+        o = self.ops
+        return bool(CFG_SHARE and B % 2 == 0 and temb_first is None and l0 is not None and l0.attn is not None and not self.fuse_rows
+                    and hasattr(o, "repeat") and hasattr(o, "attention_q_batch_mod_supported") and o.attention_q_batch_mod_supported())
+
+    def forward(self, x: Tensor, temb: Tensor, B: int, F: int, H: int, W: int, temb_first: Optional[Tensor] = None,
+                shared_prefix: int = 1) -> Tensor:
         """x: channels-last model input [B*F*H*W][pad64(conv_in_channels)] (B already includes the CFG
         duplicate); temb: [B, temb_total] f32 rows of the current step.  Returns [B*F*H*W][out_channels].
+        shared_prefix = 2: batch elements B/2 .. B-1 are copies of 0 .. B/2-1 in everything but their text states (the CFG pair: same
+        latents, mask, timestep, fps / flow / camera rows of temb); x then holds the B/2 distinct clips only, and the UNet up to the
+        first cross-attention runs on them once (`shares_prefix` says whether it does, otherwise x is duplicated and the plain schedule runs).
         temb_first ([1, temb_total], optional): time-embedding row of timestep 0 that every ResNet adds to FRAME 0 instead of
         the clip's own row (reference `use_first_frame_condition`, unet.py:523-524, resnet.py:310-317)."""
         assert self.ctx_cache is not None, "call prepare_context() first"
         cfg, P = self.cfg, self.P
+        if shared_prefix not in (1, 2):
+            raise ValueError(f"shared_prefix must be 1 or 2, got {shared_prefix}")
+        share = shared_prefix == 2 and self.shares_prefix(B, temb_first)
+        if shared_prefix == 2 and not share:
+            if B % 2:
+                raise ValueError(f"shared_prefix=2 needs an even batch, got {B}")
+            x = torch.cat([x, x])
+        self.last_schedule = "shared" if share else "plain"
         g = dict(B=B, F=F, H=H, W=W, rows=B * F * H * W)
         if temb_first is not None:
             temb = temb.repeat_interleave(F, dim=0)            # one row per (clip, frame)
@@ -463,11 +571,26 @@ class UNet3DEngine(EngineBase):
                 y = self.motion(l.motion, y, gg, clip(gg))
             return y
 
-        x = self._conv_act(x, P.conv_in_w, P.conv_in_b, frames, H, W, clip(g))
-        skips = [x]
+        first = None
+        if share:
+            # the CFG-shared prefix: conv_in, the first ResNet and the first transformer up to attn2's q projection at B / 2
+            first = P.down[0].layers[0]
+            gh = dict(g, B=B // 2, rows=g["rows"] // 2)
+            x = self._conv_act(x, P.conv_in_w, P.conv_in_b, frames // 2, H, W, clip(g))
+            skips = [Act(self._repeat(x.t, 2), x.C, self._repeat(self._stats(x), 2) if x.has_stats else None, x.cs_rows)]
+            x = self.resnet(first.resnet, x, temb[:B // 2], gh, frame(g))
+            x = self.transformer(first.attn, x, g, frame(g) if first.motion is not None else clip(g), share=2)
+            if first.motion is not None:
+                x = self.motion(first.motion, x, g, clip(g))
+            skips.append(x)
+        else:
+            x = self._conv_act(x, P.conv_in_w, P.conv_in_b, frames, H, W, clip(g))
+            skips = [x]
         sizes = [(H, W)]                       # spatial size per resolution level (odd sizes: ceil-halving on the way down)
         for blk in P.down:
             for l in blk.layers:
+                if l is first:
+                    continue
                 x = layer(l, x, g)
                 skips.append(x)
             if blk.down is not None:

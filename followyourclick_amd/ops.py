@@ -211,13 +211,28 @@ class HipOps:
     # -- attention ---------------------------------------------------------------------------
     def attention(self, q: Tensor, k: Tensor, vt: Tensor, o: Tensor, *, batch: int, heads: int, n_q: int, n_k: int,
                   d: int, ldo: int, ldvt: int, scale: float, kv_batch_div: int = 1, accumulate: bool = False,
-                  o_scale: float = 1.0) -> None:
+                  o_scale: float = 1.0, q_batch_mod: int = 0) -> None:
+        """q_batch_mod > 0: q holds q_batch_mod batch elements, element b attends with the q of b % q_batch_mod"""
         self.ensure_init(q.device)
         a = L.AttnArgs()
         a.q, a.k, a.vt, a.o = _p(q), _p(k), _p(vt), _p(o)
         a.batch, a.heads, a.n_q, a.n_k, a.d, a.ldo, a.ldvt = batch, heads, n_q, n_k, d, ldo, ldvt
         a.kv_batch_div, a.o_accumulate, a.scale, a.o_scale, a.dtype = kv_batch_div, int(accumulate), scale, o_scale, _dt(q)
+        a.q_batch_mod = q_batch_mod
         self._call("fyc_attention", a)
+
+    def attention_q_batch_mod_supported(self) -> bool:
+        return True
+
+    def repeat(self, src: Tensor, dst: Tensor, *, times: int) -> None:
+        """dst = `times` back-to-back copies of src (both contiguous, any dtype)"""
+        self.ensure_init(src.device)
+        nbytes = src.numel() * src.element_size()
+        if src.dtype != dst.dtype or dst.numel() != times * src.numel() or not (src.is_contiguous() and dst.is_contiguous()):
+            raise ValueError("repeat: dst must be a contiguous tensor of src's dtype holding `times` copies of src")
+        a = L.RepeatArgs()
+        a.src, a.dst, a.bytes, a.times = src.data_ptr(), dst.data_ptr(), nbytes, times
+        self._call("fyc_repeat", a)
 
     def temporal_attention(self, qkv: Tensor, o: Tensor, *, clips: int, frames: int, pixels: int, heads: int, d: int,
                            scale: float) -> None:
@@ -309,9 +324,10 @@ class HipOps:
     def panel_linear(self, x: Tensor, out: Tensor, *, wstream: Tensor, rows: int, N: int, K: int, bias: Optional[Tensor] = None,
                      residual: Optional[Tensor] = None, gn_cs: Optional[Tensor] = None, gn_gamma: Optional[Tensor] = None,
                      gn_beta: Optional[Tensor] = None, gn_rows_per_sample: int = 0, gn_stat_samples: int = 1, gn_groups: int = 32,
-                     gn_eps: float = 1e-6) -> None:
+                     gn_eps: float = 1e-6, gn_parts: Optional[Tensor] = None, gn_tile_rows: int = 0, gn_slots: int = 0) -> None:
         """out = [GroupNorm](x) W^T + bias (+ residual) in one kernel (csrc/panel_linear.hip); `wstream` from
-        engine/weights.py::pack_panel_linear; gn_cs = the f64 per-(statistics sample, channel) sums of x"""
+        engine/weights.py::pack_panel_linear; gn_cs = the f64 per-(statistics sample, channel) sums of x, or gn_parts = the row-tile
+        partials of x's producer (gn_tile_rows / gn_slots from gemm_stat_layout), folded by the kernel itself"""
         self.ensure_init(x.device)
         key = ("plw", N, K)
         if key not in self._q_cache:
@@ -326,6 +342,7 @@ class HipOps:
         a.gn_cs, a.gn_gamma, a.gn_beta = _p(gn_cs), _f32(gn_gamma, "gn_gamma"), _f32(gn_beta, "gn_beta")
         a.gn_rows_per_sample, a.gn_stat_samples, a.gn_groups, a.gn_eps = gn_rows_per_sample, gn_stat_samples, gn_groups, gn_eps
         a.rows, a.N, a.K, a.dtype = rows, N, K, _dt(x)
+        a.gn_parts, a.gn_tile_rows, a.gn_slots = _f32(gn_parts, "gn_parts"), gn_tile_rows, gn_slots
         self._call("fyc_panel_linear", a)
 
     # -- normalisation -----------------------------------------------------------------------
@@ -352,9 +369,14 @@ class HipOps:
         a.rows, a.C, a.groups, a.rows_per_sample, a.eps, a.silu, a.dtype = rows, C_, groups, rows_per_sample, eps, int(silu), _dt(x)
         self._call("fyc_gn_apply", a)
 
-    def gn_apply_cs(self, x1: Tensor, cs1: Tensor, gamma: Tensor, beta: Tensor, y: Tensor, *, rows: int, C1: int, groups: int,
+    direct_stats_supported = True      # gn_apply_cs / panel_linear take the producer's raw partials (parts1 / parts2 / gn_parts)
+
+    def gn_apply_cs(self, x1: Tensor, cs1: Optional[Tensor], gamma: Tensor, beta: Tensor, y: Tensor, *, rows: int, C1: int, groups: int,
                     rows_per_sample: int, eps: float, silu: bool, x2: Optional[Tensor] = None, cs2: Optional[Tensor] = None,
-                    C2: int = 0, cs_rows: int = 0) -> None:
+                    C2: int = 0, cs_rows: int = 0, parts1: Optional[Tensor] = None, parts2: Optional[Tensor] = None,
+                    tile_rows1: int = 0, slots1: int = 0, tile_rows2: int = 0, slots2: int = 0, parts_cs_rows: int = 0) -> None:
+        """per source either the reduced f64 sums (cs) or the producer's row-tile partials (parts + tile_rows / slots from
+        gemm_stat_layout, parts_cs_rows rows per statistics sample), which the kernel folds itself"""
         a = L.GnApplyCsArgs()
         for t in (cs1, cs2):
             if t is not None and t.dtype != torch.float64:
@@ -363,6 +385,8 @@ class HipOps:
         a.gamma, a.beta, a.y = _f32(gamma, "gamma"), _f32(beta, "beta"), _p(y)
         a.C1, a.C2, a.rows, a.groups, a.rows_per_sample, a.eps, a.silu, a.dtype = C1, C2, rows, groups, rows_per_sample, eps, int(silu), _dt(x1)
         a.cs_rows = cs_rows
+        a.parts1, a.parts2 = _f32(parts1, "parts1"), _f32(parts2, "parts2")
+        a.tile_rows1, a.slots1, a.tile_rows2, a.slots2, a.parts_cs_rows = tile_rows1, slots1, tile_rows2, slots2, parts_cs_rows
         self._call("fyc_gn_apply_cs", a)
 
     def layernorm(self, x: Tensor, gamma: Tensor, beta: Tensor, y: Tensor, *, rows: int, C_: int, eps: float = 1e-5,

@@ -68,9 +68,18 @@ class TimedOps:
         B, H, nq, nk, d = kw["batch"], kw["heads"], kw["n_q"], kw["n_k"], kw["d"]
         flops = 4.0 * B * H * nq * nk * d
         kvb = (B + kw.get("kv_batch_div", 1) - 1) // kw.get("kv_batch_div", 1)
-        nbytes = (2 * B * H * nq * d + 2 * kvb * H * nk * d) * 2
+        qb = kw.get("q_batch_mod", 0) or B          # distinct query batch elements (the CFG halves share theirs)
+        nbytes = ((B + qb) * H * nq * d + 2 * kvb * H * nk * d) * 2
         fam = "attn_self" if nq == nk else "attn_cross"
         return self._timed(fam, flops, nbytes, self.inner.attention, q, k, vt, o, _key=f"{fam} B={B} H={H} nq={nq} nk={nk} d={d}", **kw)
+
+    def attention_q_batch_mod_supported(self):
+        fn = getattr(self.inner, "attention_q_batch_mod_supported", None)
+        return bool(fn and fn())
+
+    def repeat(self, src, dst, **kw):
+        n = src.numel() * src.element_size()
+        return self._timed("repeat", 0.0, (1.0 + kw["times"]) * n, self.inner.repeat, src, dst, **kw)
 
     def temporal_attention(self, qkv, o, **kw):
         n = kw["clips"] * kw["frames"] * kw["pixels"] * kw["heads"] * kw["d"]

@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13. */
-#define FYC_VERSION 301
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off. */
+#define FYC_VERSION 302
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -151,6 +151,8 @@ int fyc_chan_stats_reduce(const fyc_chan_stats_reduce_args* a, void* stream);
  * scaled by o_scale (out = attn_text + scale * attn_ip).
  * q,k: [BH][N][d]; vt: [BH][d][ldvt] (transposed V written by the HEADS epilogue). kv_batch_div: K/V batch
  * index = (b / kv_batch_div) * heads + h  (text K/V are shared by the F frames of a clip).
+ * q_batch_mod > 0: the q of batch element b is read from batch element b % q_batch_mod (q holds q_batch_mod elements): the two
+ * halves of a classifier-free-guidance pair share their queries up to the first cross-attention and differ in the text K / V only.
  */
 typedef struct {
   const void* q; const void* k; const void* vt; void* o;
@@ -160,7 +162,8 @@ typedef struct {
   int32_t kv_batch_div;
   int32_t o_accumulate;
   float scale, o_scale;
-  int32_t dtype;         /* FYC_BF16 only */
+  int32_t dtype;         /* FYC_BF16 / FYC_F16 */
+  int32_t q_batch_mod;   /* (version 302) 0 = off */
 } fyc_attn_args;
 int fyc_attention(const fyc_attn_args* a, void* stream);
 
@@ -219,6 +222,13 @@ typedef struct {
   int32_t cs_rows;       /* rows per statistics sample of cs1 / cs2 (0 = rows_per_sample): the producers accumulate per frame (H*W
                           * rows) so that their atomics spread over F times more addresses; a cross-frame norm (rows_per_sample =
                           * F*H*W) adds up the F frame sums here */
+  /* (version 302) instead of cs1 / cs2 a source may hand over the row-tile partials its producer wrote (fyc_gemm chan_parts,
+   * [tile][slot][C][2] f32 with tile_rows / slots from fyc_gemm_stat_layout and parts_cs_rows rows per statistics sample): the kernel
+   * folds them in its prologue - tiles ascending, slots ascending, f64, what fyc_chan_stats_reduce would have written - and the reduce
+   * launch is saved.  Every block re-reads (tiles of its sample) x slots x C x 8 bytes: for samples of few tiles.  Per source
+   * exactly one of cs / parts. */
+  const float* parts1; const float* parts2;
+  int32_t tile_rows1, slots1, tile_rows2, slots2, parts_cs_rows;
 } fyc_gn_apply_cs_args;
 int fyc_gn_apply_cs(const fyc_gn_apply_cs_args* a, void* stream);
 
@@ -247,6 +257,11 @@ int fyc_softmax_rows(const fyc_softmax_args* a, void* stream);
 /* y[r][0:c1] = a[r][:], y[r][c1:c1+c2] = b[r][:]  (torch.cat(dim=1) of unet_blocks.py:763,885) */
 typedef struct { const void* a; const void* b; void* y; int64_t rows; int32_t c1, c2; int32_t dtype; } fyc_concat_args;
 int fyc_concat_channels(const fyc_concat_args* a, void* stream);
+
+/* dst = `times` back-to-back copies of the `bytes` bytes at src (any element type; bytes % 16 == 0, both 16-byte aligned, no overlap):
+ * broadcasts what the CFG-shared UNet prefix computed once to the full batch (engine/unet3d.py) */
+typedef struct { const void* src; void* dst; int64_t bytes; int32_t times; } fyc_repeat_args;
+int fyc_repeat(const fyc_repeat_args* a, void* stream);
 
 /* y = silu(x) (f32, small: time embeddings) */
 typedef struct { const float* x; float* y; int64_t n; } fyc_silu_args;
@@ -399,6 +414,9 @@ typedef struct {
   float gn_eps;
   int32_t rows, N, K;
   int32_t dtype;
+  /* (version 302) instead of gn_cs: the row-tile partials of x's producer (fyc_gemm chan_parts layout, gn_rows_per_sample /
+   * gn_stat_samples rows per statistics sample), folded in the kernel's prologue like fyc_gn_apply_cs's parts1 */
+  const float* gn_parts; int32_t gn_tile_rows, gn_slots;
 } fyc_panel_linear_args;
 int fyc_panel_linear(const fyc_panel_linear_args* a, void* stream);
 int fyc_panel_linear_supported(const fyc_panel_linear_args* a);
