@@ -28,7 +28,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops as ops_mod
-from .base import EngineBase
+from .base import ChanStats, EngineBase
 from .config import UNet3DConfig
 from .weights import Packed, pack_ff_block, pack_panel_linear, pack_temporal_block
 
@@ -55,20 +55,13 @@ FUSE_ROWS = os.environ.get("FYC_FUSE_ROWS", "0") != "0"      # the LayerNorm hal
 
 
 class Act:
-    """an activation [rows][C] plus what its producer already knows about it: `plan` = (parts, tile_rows, slots, rows, stat_rows), the
-    row-tile partial {sum, sum of squares} per channel its epilogue wrote with stat_rows rows per statistics sample (a frame);
-    `cs` = the same folded to per-(sample of cs_rows rows, channel) f64 sums ([rows / cs_rows][C][2]) - made from the plan only when a
-    consumer asks for it (UNet3DEngine._stats), many consumers fold the partials themselves; `rp` = per-row partial {sum, sum sq}
-    ([rows][rp_n][2] f32)"""
-    __slots__ = ("t", "C", "cs", "cs_rows", "rp", "rp_n", "plan")
+    """an activation [rows][C] plus what its producer already knows about it: `st` = its channel sums for the GroupNorm that
+    consumes it (base.ChanStats, or None: that norm runs its own statistics pass); `rp` = per-row partial {sum, sum sq}
+    ([rows][rp_n][2] f32) for a LayerNorm"""
+    __slots__ = ("t", "C", "st", "rp", "rp_n")
 
-    def __init__(self, t: Tensor, C: int, cs: Optional[Tensor] = None, cs_rows: int = 0, rp: Optional[Tensor] = None, rp_n: int = 0,
-                 plan=None):
-        self.t, self.C, self.cs, self.cs_rows, self.rp, self.rp_n, self.plan = t, C, cs, cs_rows, rp, rp_n, plan
-
-    @property
-    def has_stats(self) -> bool:
-        return self.cs is not None or self.plan is not None
+    def __init__(self, t: Tensor, C: int, st: Optional[ChanStats] = None, rp: Optional[Tensor] = None, rp_n: int = 0):
+        self.t, self.C, self.st, self.rp, self.rp_n = t, C, st, rp, rp_n
 
 
 def sinusoid_host(values: Sequence[float], dim: int) -> Tensor:
@@ -184,12 +177,8 @@ class UNet3DEngine(EngineBase):
         H, o = self.heads, self.ops
         scale = d ** -0.5
         if not self.mat_attn:
-            if q_mod:
-                o.attention(q, k, vt, out, batch=batch, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldvt, scale=scale,
-                            kv_batch_div=kv_div, accumulate=accumulate, o_scale=o_scale, q_batch_mod=q_mod)
-                return
             o.attention(q, k, vt, out, batch=batch, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldvt, scale=scale,
-                        kv_batch_div=kv_div, accumulate=accumulate, o_scale=o_scale)
+                        kv_batch_div=kv_div, accumulate=accumulate, o_scale=o_scale, **({"q_batch_mod": q_mod} if q_mod else {}))
             return
         # f32 parity mode: softmax(q k^T * scale) v materialised per batch element through the GEMM
         # (reference CrossAttention._attention, diffusers/models/attention.py:649-678)
@@ -216,63 +205,24 @@ class UNet3DEngine(EngineBase):
         self.ops.row_stats(x, st, rows=rows, C_=C, eps=eps)
         return st
 
-    # ---- fused statistics: _cs_plan / _cs_finish live in EngineBase (the VAE engines use them too) ----------------------------------------
+    # ---- fused statistics: the plumbing (ChanStats, _cs_plan, _produced, _stats, gn_from_stats, conv_stats) lives in EngineBase ----------------
+    def _direct_limit(self) -> int:
+        return DIRECT_STATS_BYTES
+
     def _gn(self, x: Union[Act, Tuple[Act, Act]], gamma: Tensor, beta: Tensor, rows: int, rows_per_sample: int, eps: float,
             silu: bool) -> Tuple[Tensor, Optional[Tensor]]:
         """GroupNorm (+SiLU) of an activation or of the channel concat of two (up blocks: cat([hidden, skip], dim=1),
         reference unet_blocks.py:763,885).  Returns (normalised tensor, materialised concat or None)."""
-        o = self.ops
-        if isinstance(x, Act):
-            if x.has_stats and rows_per_sample % x.cs_rows == 0:
-                y = self.new(rows, x.C)
-                d = self._direct((x,), rows_per_sample)
-                if d is not None:
-                    parts, tr, sl, _, srows = x.plan
-                    o.gn_apply_cs(x.t, None, gamma, beta, y, rows=rows, C1=x.C, groups=self.groups, rows_per_sample=rows_per_sample,
-                                  eps=eps, silu=silu, parts1=parts, tile_rows1=tr, slots1=sl, parts_cs_rows=srows)
-                    return y, None
-                o.gn_apply_cs(x.t, self._stats(x), gamma, beta, y, rows=rows, C1=x.C, groups=self.groups, rows_per_sample=rows_per_sample,
-                              eps=eps, silu=silu, cs_rows=x.cs_rows)
-                return y, None
-            return self.group_norm(x.t, gamma, beta, rows, x.C, rows_per_sample, eps, silu), None
-        a, b = x
-        if a.has_stats and b.has_stats and a.cs_rows == b.cs_rows and rows_per_sample % a.cs_rows == 0:
-            y = self.new(rows, a.C + b.C)
-            if self._direct((a, b), rows_per_sample) is not None:      # both sources from their partials (same rows per statistics sample)
-                (p1, tr1, sl1, _, srows), (p2, tr2, sl2, _, _) = a.plan, b.plan
-                o.gn_apply_cs(a.t, None, gamma, beta, y, rows=rows, C1=a.C, groups=self.groups, rows_per_sample=rows_per_sample,
-                              eps=eps, silu=silu, x2=b.t, C2=b.C, parts1=p1, tile_rows1=tr1, slots1=sl1, parts2=p2, tile_rows2=tr2,
-                              slots2=sl2, parts_cs_rows=srows)
-                return y, None
-            o.gn_apply_cs(a.t, self._stats(a), gamma, beta, y, rows=rows, C1=a.C, groups=self.groups, rows_per_sample=rows_per_sample,
-                          eps=eps, silu=silu, x2=b.t, cs2=self._stats(b), C2=b.C, cs_rows=a.cs_rows)
+        xs = (x,) if isinstance(x, Act) else x
+        y = self.gn_from_stats([(a.t, a.st) for a in xs], gamma, beta, rows, rows_per_sample, eps, silu)
+        if y is not None:
             return y, None
+        if len(xs) == 1:
+            return self.group_norm(x.t, gamma, beta, rows, x.C, rows_per_sample, eps, silu), None
+        a, b = xs
         cat = self.new(rows, a.C + b.C)
-        o.concat_channels(a.t, b.t, cat, rows=rows, c1=a.C, c2=b.C)
+        self.ops.concat_channels(a.t, b.t, cat, rows=rows, c1=a.C, c2=b.C)
         return self.group_norm(cat, gamma, beta, rows, a.C + b.C, rows_per_sample, eps, silu), cat
-
-    def _stats(self, x: Act) -> Tensor:
-        """the reduced f64 sums of x at its consumer's granularity: one fyc_chan_stats_reduce launch, on first use"""
-        if x.cs is None:
-            parts, tile_rows, slots, rows, stat_rows = x.plan
-            x.cs = self._cs_finish((parts, tile_rows, slots), rows, stat_rows, x.C, x.cs_rows)
-        return x.cs
-
-    def _direct(self, xs: Tuple[Act, ...], rows_per_sample: int) -> Optional[int]:
-        """bytes of partials one consumer block reads when it folds the row-tile partials of `xs` itself, or None where it should not:
-        sums already reduced, sources with different statistics samples, or more than DIRECT_STATS_BYTES per block (the wide clip-level
-        norms of the 64x64 and 32x32 levels: hundreds of KB per block against one small launch)"""
-        if not self.direct_stats or any(x.plan is None or x.cs is not None for x in xs):
-            return None
-        srows = xs[0].plan[4]
-        if any(x.plan[4] != srows for x in xs) or rows_per_sample % srows:
-            return None
-        nbytes = 0
-        for x in xs:
-            _, tile_rows, slots, _, _ = x.plan
-            tiles = rows_per_sample // tile_rows if rows_per_sample % tile_rows == 0 else (rows_per_sample - 1) // tile_rows + 2
-            nbytes += max(tiles, 1) * slots * x.C * 8
-        return nbytes if nbytes <= DIRECT_STATS_BYTES else None
 
     def _lin_rp(self, x: Tensor, w: Tensor, rows: int, bias=None, residual=None) -> Act:
         """Linear whose output feeds a (folded) LayerNorm: the epilogue also writes the per-row partial sums"""
@@ -300,21 +250,17 @@ class UNet3DEngine(EngineBase):
     def _norm_proj_in(self, x: Act, node: Packed, rows: int, rows_per_sample: int) -> Act:
         """GroupNorm -> proj_in of a transformer / motion module (reference attention.py:269-270, motion_module.py:188-191).  With the
         producer's channel sums at hand the norm is applied to fyc_panel_linear's operand registers: no normalised tensor in HBM."""
-        C = node.C
-        if (FUSE_PANEL and isinstance(x, Act) and x.has_stats and not self.fuse_rows and rows_per_sample % x.cs_rows == 0
+        C, st = node.C, x.st
+        if (FUSE_PANEL and st is not None and not self.fuse_rows and rows_per_sample % st.out_rows == 0
                 and self.ops.panel_linear_supported(self.dtype, rows=rows, N=C, K=C, gn_rows_per_sample=rows_per_sample, gn_groups=self.groups)):
             out = self.new(rows, C)
-            if self._direct((x,), rows_per_sample) is not None:
-                parts, tr, sl, _, srows = x.plan
-                self.ops.panel_linear(x.t, out, wstream=self._panel_stream(node.pin_w), rows=rows, N=C, K=C, bias=node.pin_b, gn_parts=parts,
-                                      gn_tile_rows=tr, gn_slots=sl, gn_gamma=node.norm_g, gn_beta=node.norm_b,
-                                      gn_rows_per_sample=rows_per_sample, gn_stat_samples=rows_per_sample // srows, gn_groups=self.groups,
-                                      gn_eps=1e-6)
-                return Act(out, C)
-            self._stats(x)
-            self.ops.panel_linear(x.t, out, wstream=self._panel_stream(node.pin_w), rows=rows, N=C, K=C, bias=node.pin_b, gn_cs=x.cs,
+            if self._direct((st,), rows_per_sample) is not None:
+                srows, kw = st.stat_rows, dict(gn_parts=st.parts, gn_tile_rows=st.tile_rows, gn_slots=st.slots)
+            else:
+                srows, kw = st.out_rows, dict(gn_cs=self._stats(st))
+            self.ops.panel_linear(x.t, out, wstream=self._panel_stream(node.pin_w), rows=rows, N=C, K=C, bias=node.pin_b,
                                   gn_gamma=node.norm_g, gn_beta=node.norm_b, gn_rows_per_sample=rows_per_sample,
-                                  gn_stat_samples=rows_per_sample // x.cs_rows, gn_groups=self.groups, gn_eps=1e-6)
+                                  gn_stat_samples=rows_per_sample // srows, gn_groups=self.groups, gn_eps=1e-6, **kw)
             return Act(out, C)
         h, _ = self._gn(x, node.norm_g, node.norm_b, rows, rows_per_sample, 1e-6, False)
         return self._lin_rp(h, node.pin_w, rows, bias=node.pin_b)
@@ -349,25 +295,12 @@ class UNet3DEngine(EngineBase):
     # the block's output: one frame for the per-frame norm of a transformer / motion module, F frames for the cross-frame norm
     # of a ResNet / conv_norm_out); fyc_chan_stats_reduce folds the row-tile partials to the consumer's granularity.
     def _conv_act(self, x: Tensor, w: Tensor, b: Tensor, frames: int, Hin: int, Win: int, nxt: Tuple[int, int], **kw) -> Act:
-        Cout, K = w.shape
-        if kw.get("up2"):
-            Ho, Wo = kw["up_size"]
-        else:
-            st = kw.get("stride", 1)
-            Ho, Wo = (Hin - 1) // st + 1, (Win - 1) // st + 1
-        rows = frames * Ho * Wo
-        plan = self._cs_plan(rows, nxt[0], Cout, K, L.GEMM_CONV3X3_UP2 if kw.get("up2") else L.GEMM_CONV3X3) if nxt else None
-        out = self.conv(x, w, b, frames, Hin, Win, chan_parts=None if plan is None else plan[0], cs_rows=nxt[0] if plan is not None else 0, **kw)
-        return self._act(out, Cout, plan, rows, nxt)
+        out, st = self.conv_stats(x, w, b, frames, Hin, Win, nxt, **kw)
+        return Act(out, w.shape[0], st)
 
-    def _act(self, out: Tensor, C: int, plan, rows: int, nxt, rp=None, rp_n: int = 0) -> Act:
-        """the output of a producer that wrote row-tile partials `plan` (EngineBase._cs_plan, or None) for the norm `nxt` describes"""
-        if plan is None:
-            return Act(out, C, None, nxt[1] if nxt else 0, rp, rp_n)
-        a = Act(out, C, None, nxt[1], rp, rp_n, plan=(plan[0], plan[1], plan[2], rows, nxt[0]))
-        if not self.direct_stats:
-            self._stats(a)          # the reduce launch right behind its producer, as before
-        return a
+    def _act(self, out: Tensor, C: int, st: Optional[ChanStats], rp=None, rp_n: int = 0) -> Act:
+        """the output of a producer that wrote the row-tile partials of `st` (EngineBase._cs_plan, or None)"""
+        return Act(out, C, self._produced(st), rp, rp_n)
 
     def resnet(self, r: Packed, x: Union[Act, Tuple[Act, Act]], temb: Tensor, g: dict, nxt: Tuple[int, int]) -> Act:
         """ResnetBlock3D (reference resnet.py:296-342): cross-frame GroupNorm statistics.  x may be the (hidden, skip) pair of an
@@ -407,7 +340,8 @@ class UNet3DEngine(EngineBase):
             parts = self.new(rows // 128 * C * 2, dtype=torch.float32) if cs_rows else None
             self.ops.ff_block(tok.t, residual, out, wstream=ff["_wstream"], b_out=ff.po_b, rows=rows, C_=C, hidden=hidden,
                               chan_parts=parts, cs_rows=cs_rows)
-            return self._act(out, C, (parts, 128, 1) if cs_rows else None, rows, nxt if cs_rows else None)
+            st = ChanStats(C, out_rows=nxt[1], parts=parts, tile_rows=128, slots=1, rows=rows, stat_rows=cs_rows) if cs_rows else None
+            return self._act(out, C, st)
         if ff.cs1 is not None:      # LayerNorm folded into FF1: statistics from the producer of tok (or one statistics pass)
             N1 = ff.w1.shape[0]
             hmid = self.new(rows, N1 // 2)
@@ -418,15 +352,15 @@ class UNet3DEngine(EngineBase):
             hmid = self.lin(n, ff.w1, rows, bias=ff.b1, geglu=True)
         out = self.new(rows, C)
         K = ff.po_w.shape[1]
-        plan = self._cs_plan(rows, nxt[0], C, K, L.GEMM_PLAIN) if nxt else None
+        st = self._cs_plan(rows, nxt[0], C, K, L.GEMM_PLAIN, nxt[1]) if nxt else None
         rp, rp_n = None, 0
         if residual is None and self.fuse_rows:      # inner motion blocks: the output is the next block's token stream (LayerNorm input)
             rp_n = self.ops.gemm_row_parts(tok.t.dtype, M=rows, N=C, K=K)
             rp = self.new(rows, rp_n, 2, dtype=torch.float32)
         self.ops.gemm(tok.t, ff.po_w, out, M=rows, N=C, K=K, lda=C, ldw=K, ldo=C, bias=ff.po_b, residual=residual, ldr=C,
-                      a2=hmid, k_split=C, lda2=K - C, chan_parts=None if plan is None else plan[0], cs_rows=nxt[0] if plan is not None else 0,
+                      a2=hmid, k_split=C, lda2=K - C, chan_parts=None if st is None else st.parts, cs_rows=0 if st is None else st.stat_rows,
                       row_parts=rp, row_nparts=rp_n)
-        return self._act(out, C, plan, rows, nxt, rp, rp_n)
+        return self._act(out, C, st, rp, rp_n)
 
     def _repeat(self, t: Tensor, times: int) -> Tensor:
         """`times` copies of t along its first axis (the shared CFG prefix, broadcast to the full batch)"""
@@ -577,7 +511,8 @@ class UNet3DEngine(EngineBase):
             first = P.down[0].layers[0]
             gh = dict(g, B=B // 2, rows=g["rows"] // 2)
             x = self._conv_act(x, P.conv_in_w, P.conv_in_b, frames // 2, H, W, clip(g))
-            skips = [Act(self._repeat(x.t, 2), x.C, self._repeat(self._stats(x), 2) if x.has_stats else None, x.cs_rows)]
+            skip = self._repeat(x.t, 2)       # the skip connection at the full batch, with its sums (reduced: two copies of the half's)
+            skips = [Act(skip, x.C, ChanStats(x.C, x.st.out_rows, cs=self._repeat(self._stats(x.st), 2)) if x.st is not None else None)]
             x = self.resnet(first.resnet, x, temb[:B // 2], gh, frame(g))
             x = self.transformer(first.attn, x, g, frame(g) if first.motion is not None else clip(g), share=2)
             if first.motion is not None:

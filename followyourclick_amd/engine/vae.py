@@ -33,27 +33,18 @@ class VAEDecoderEngine(EngineBase):
         self.groups = self.cfg.norm_num_groups
         self.ops.ensure_init(self.device)
 
-    # ---- GroupNorm statistics from the producing convolution's epilogue (round 6: the decode used to run a statistics pass over every
-    # GroupNorm input - 30 passes, 3.3 of 49 ms per 16-frame chunk at 512^2; the UNet engine has taken them from the epilogues since round 2) ----
+    # ---- GroupNorm statistics from the producing convolution's epilogue (the decode used to run a statistics pass over every
+    # GroupNorm input - 30 passes, 3.3 of 49 ms per 16-frame chunk at 512^2): EngineBase.conv_stats / gn_from_stats, shared with the UNet ----
     def conv_cs(self, x: Tensor, w: Tensor, b: Tensor, frames: int, Hin: int, Win: int, **kw):
-        """a 3x3 convolution whose output feeds a per-frame GroupNorm -> (output, per-(frame, channel) sums or None)"""
-        Cout, K = w.shape
-        up2, stride, pad = kw.get("up2", False), kw.get("stride", 1), kw.get("pad", 1)
-        Ho, Wo = (2 * Hin, 2 * Win) if up2 else ((Hin + pad - 2) // stride + 1, (Win + pad - 2) // stride + 1)
-        rows, hw = frames * Ho * Wo, Ho * Wo
-        plan = self._cs_plan(rows, hw, Cout, K, L.GEMM_CONV3X3_UP2 if up2 else L.GEMM_CONV3X3) if FUSE_STATS else None
-        out = self.conv(x, w, b, frames, Hin, Win, chan_parts=None if plan is None else plan[0], cs_rows=hw if plan is not None else 0, **kw)
-        return out, (None if plan is None else self._cs_finish(plan, rows, hw, Cout, hw))
+        """a 3x3 convolution whose output feeds a per-frame GroupNorm -> (output, its ChanStats or None)"""
+        return self.conv_stats(x, w, b, frames, Hin, Win, per_frame=FUSE_STATS, **kw)
 
     def gn(self, x: Tensor, cs, g: Tensor, b: Tensor, rows: int, C: int, hw: int, silu: bool) -> Tensor:
-        if cs is None:
-            return self.group_norm(x, g, b, rows, C, hw, 1e-6, silu)
-        y = self.new(rows, C)
-        self.ops.gn_apply_cs(x, cs, g, b, y, rows=rows, C1=C, groups=self.groups, rows_per_sample=hw, eps=1e-6, silu=silu, cs_rows=hw)
-        return y
+        y = self.gn_from_stats([(x, cs)], g, b, rows, hw, 1e-6, silu)
+        return y if y is not None else self.group_norm(x, g, b, rows, C, hw, 1e-6, silu)
 
     def resnet(self, r: Packed, x: Tensor, frames: int, H: int, W: int, cs=None):
-        """-> (output, its per-(frame, channel) sums or None); `cs`: the sums of x when its producer wrote them"""
+        """-> (output, its ChanStats or None); `cs`: the ChanStats of x when its producer wrote them"""
         rows, hw = frames * H * W, H * W
         h = self.gn(x, cs, r.n1_g, r.n1_b, rows, r.cin, hw, True)
         h, cs1 = self.conv_cs(h, r.c1_w, r.c1_b, frames, H, W)

@@ -60,6 +60,7 @@ class HipOps:
 
     def __init__(self):
         self.lib = L.load()
+        self.abi_version = int(self.lib.fyc_version())        # (differs from _lib.FYC_VERSION only for an A/B library, FYC_LIB_PATH)
         self._zero = None
         self._ws = None              # scratch for split-K GEMMs: one buffer, grown on demand (all work is on one stream)
         self._ws_need = {}           # (shape, flags) -> split-K scratch bytes (fyc_gemm_workspace_bytes), see gemm()
@@ -82,7 +83,6 @@ class HipOps:
             raise L.FycError(f"followyourclick_amd is bound to cuda:{self._inited_dev}; use one process per GPU (asked for cuda:{idx})")
         self._zero = torch.zeros(4096, dtype=torch.uint8, device=torch.device("cuda", idx))
         L.check(self.lib.fyc_init(self._zero.data_ptr()), "fyc_init")
-        self.abi_version = int(self.lib.fyc_version())        # (differs from _lib.FYC_VERSION only for an A/B library, FYC_LIB_PATH)
         self._inited_dev = idx
         for kv in filter(None, os.environ.get("FYC_TUNING", "").split(",")):   # A/B runs: FYC_TUNING="5=1,4=8" (fyc_set_tuning keys)
             k, v = kv.split("=")

@@ -14,7 +14,6 @@ import torch
 from emu_ops import EmuOps
 from followyourclick_amd import _lib as L
 from followyourclick_amd.engine import unet3d
-from followyourclick_amd.engine.base import EngineBase
 from followyourclick_amd.engine.unet3d import UNet3DEngine
 
 pytestmark = pytest.mark.gpu
@@ -41,9 +40,8 @@ class Recorder:
         return call
 
 
-class MiniEngine(EngineBase):
+class MiniEngine(UNet3DEngine):
     """the statistics plumbing of UNet3DEngine without a model"""
-    _gn, _stats, _direct, _act = UNet3DEngine._gn, UNet3DEngine._stats, UNet3DEngine._direct, UNet3DEngine._act
 
     def __init__(self, ops, dtype, direct):
         self.ops, self.dtype, self.device, self.groups = ops, dtype, torch.device(DEV), 32
@@ -52,11 +50,11 @@ class MiniEngine(EngineBase):
     def produce(self, a, w, stat_rows, out_rows):
         """x = a w^T by fyc_gemm, with the row-tile partial sums for a norm over `out_rows` rows wherever the plan allows them"""
         rows, (N, K) = a.shape[0], w.shape
-        plan = self._cs_plan(rows, stat_rows, N, K, L.GEMM_PLAIN)
+        st = self._cs_plan(rows, stat_rows, N, K, L.GEMM_PLAIN, out_rows)
         out = self.new(rows, N)
-        self.ops.gemm(a, w, out, M=rows, N=N, K=K, lda=K, ldw=K, ldo=N, chan_parts=None if plan is None else plan[0],
-                      cs_rows=stat_rows if plan is not None else 0)
-        return self._act(out, N, plan, rows, (stat_rows, out_rows))
+        self.ops.gemm(a, w, out, M=rows, N=N, K=K, lda=K, ldw=K, ldo=N, chan_parts=None if st is None else st.parts,
+                      cs_rows=stat_rows if st is not None else 0)
+        return self._act(out, N, st)
 
 
 @pytest.fixture(scope="module")
@@ -116,9 +114,9 @@ def test_gn_apply_cs_folds_the_producers_partials(hip, monkeypatch, dt, case):
             rec = Recorder(hip)
             eng = MiniEngine(rec, T, direct)
             acts = [eng.produce(a, w, frame, rps) for a, w in ops_in]
-            assert all(a.plan is not None for a in acts)
+            assert all(a.st is not None and a.st.parts is not None for a in acts)
             if dt == "bf16":
-                assert all(a.plan[1:3] == layout for a in acts), [a.plan[1:3] for a in acts]
+                assert all((a.st.tile_rows, a.st.slots) == layout for a in acts), [(a.st.tile_rows, a.st.slots) for a in acts]
             y, cat = eng._gn(acts[0] if len(acts) == 1 else tuple(acts), gamma.to(DEV), beta.to(DEV), rows, rps, 1e-5, True)
             torch.cuda.synchronize()
             assert cat is None
@@ -156,7 +154,7 @@ def test_frames_of_75_rows_take_the_statistics_pass(hip, dt):
     rec = Recorder(hip)
     eng = MiniEngine(rec, T, True)
     act = eng.produce(rnd((rows, K), T, 1, 1.3).to(DEV), rnd((C, K), T, 2, 1 / math.sqrt(K)).to(DEV), frame, frame)
-    assert act.plan is None and act.cs is None and not act.has_stats
+    assert act.st is None
     y, _ = eng._gn(act, gamma.to(DEV), beta.to(DEV), rows, frame, 1e-5, True)
     torch.cuda.synchronize()
     assert rec.names == ["gemm", "gn_stats", "gn_apply"], rec.names

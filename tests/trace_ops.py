@@ -1,0 +1,223 @@
+"""An ops backend that does no arithmetic and records the launch sequence (TEST INFRASTRUCTURE, never imported by the product).
+
+Every launch becomes one `Launch(op, args)`: the scalar arguments as they were passed, every tensor argument as a
+`Buf(storage, offset, shape, stride, dtype)` where `storage` numbers the distinct storages in order of first appearance.  Two engines
+that produce the same log ask for the same kernels with the same scalars and move the same data between them: the log is the
+schedule *and* its dataflow.  The backend keeps every tensor it has seen, so that an address can never come back for another buffer.
+
+The host queries (which the engines plan with) answer by fixed rules: 128-row tiles with the library's slot rule, 2 row parts, no
+split-K, and the three fused kernels either on every shape that is whole 128-row tiles (`fused=True`) or nowhere."""
+import functools
+from collections import namedtuple
+
+import torch
+
+Buf = namedtuple("Buf", "storage offset shape stride dtype")
+Launch = namedtuple("Launch", "op args")
+
+# positional tensor arguments per op, and which arguments an op writes (`heads.outs`: the output list inside gemm's `heads`)
+POSITIONAL = dict(
+    gemm=("a", "w", "out"), chan_stats_reduce=("parts", "cs"), attention=("q", "k", "vt", "o"), repeat=("src", "dst"),
+    temporal_attention=("qkv", "o"), temporal_block=("x", "out"), ff_block=("x", "residual", "out"), panel_linear=("x", "out"),
+    gn_stats=("x", "stats"), gn_apply=("x", "stats", "gamma", "beta", "y"), gn_apply_cs=("x1", "cs1", "gamma", "beta", "y"),
+    layernorm=("x", "gamma", "beta", "y"), row_stats=("x", "stats"), softmax_rows=("x",), concat_channels=("a", "b", "y"),
+    silu_f32=("x", "y"), cast_from_f32=("x", "y"), cast_to_f32=("x", "y"), unet_input=("latents", "mask", "first", "x"),
+    cfg_ddim_step=("pred", "latents", "coef"), nchw_to_nhwc=("z", "x"), nhwc_to_nchw=("x", "y"))
+WRITES = dict(
+    gemm=("out", "chan_parts", "row_parts", "heads.outs"), chan_stats_reduce=("cs",), attention=("o",), repeat=("dst",),
+    temporal_attention=("o",), temporal_block=("out",), ff_block=("out", "chan_parts"), panel_linear=("out",), gn_stats=("stats",),
+    gn_apply=("y",), gn_apply_cs=("y",), layernorm=("y",), row_stats=("stats",), softmax_rows=("x",), concat_channels=("y",),
+    silu_f32=("y",), cast_from_f32=("y",), cast_to_f32=("y",), unet_input=("x",), cfg_ddim_step=("latents",), nchw_to_nhwc=("x",),
+    nhwc_to_nchw=("y",))
+
+
+def stat_slots(tile_rows: int, cs_rows: int) -> int:
+    """sample slots a row tile can touch (csrc/gemm.hip::stat_slots)"""
+    if cs_rows % tile_rows == 0:
+        return 1
+    if tile_rows % cs_rows == 0:
+        return tile_rows // cs_rows
+    return (tile_rows - 1) // cs_rows + 2
+
+
+class TraceOps:
+    name = "trace"
+    direct_stats_supported = True
+
+    def __init__(self, fused: bool = True):
+        self.fused = fused
+        self.reset()
+
+    def reset(self) -> None:
+        self.log, self._serial, self._keep = [], {}, []
+
+    # ---- recording -------------------------------------------------------------------------------
+    def _describe(self, v):
+        if isinstance(v, torch.Tensor):
+            self._keep.append(v)
+            n = self._serial.setdefault(v.untyped_storage().data_ptr(), len(self._serial))
+            return Buf(n, v.storage_offset(), tuple(v.shape), tuple(v.stride()), str(v.dtype))
+        if isinstance(v, dict):
+            return {k: self._describe(x) for k, x in v.items()}
+        if isinstance(v, (list, tuple)):
+            return [self._describe(x) for x in v]
+        return str(v) if isinstance(v, torch.dtype) else v
+
+    def __getattr__(self, op):
+        if op not in POSITIONAL:
+            raise AttributeError(op)
+
+        def launch(*a, **kw):
+            assert len(a) <= len(POSITIONAL[op]) and not set(POSITIONAL[op][:len(a)]) & set(kw), (op, len(a), sorted(kw))
+            args = dict(zip(POSITIONAL[op], a), **kw)
+            self.log.append(Launch(op, {k: self._describe(args[k]) for k in sorted(args)}))
+        return launch
+
+    def lines(self):
+        """the log as text, one launch per line"""
+        return [f"{l.op} " + " ".join(f"{k}={_fmt(v)}" for k, v in l.args.items()) for l in self.log]
+
+    # ---- host side -------------------------------------------------------------------------------
+    def ensure_init(self, device) -> None:
+        pass
+
+    def set_tuning(self, key, value) -> None:
+        pass
+
+    def gemm_stat_layout(self, dtype, *, M, N, K, cs_rows, mode=0, batch=1, tile=0):
+        return (M + 127) // 128, 128, stat_slots(128, cs_rows)
+
+    def gemm_row_parts(self, dtype, *, M, N, K, mode=0, batch=1, tile=0):
+        return 2
+
+    def gemm_split_bytes(self, dtype, *, M, N, K, mode=0):
+        return 0
+
+    def ff_block_supported(self, dtype, *, rows, C_, hidden, cs_rows=0):
+        return self.fused and rows % 128 == 0 and cs_rows % 128 == 0
+
+    def panel_linear_supported(self, dtype, *, rows, N, K, gn_rows_per_sample=0, gn_groups=32):
+        return self.fused and rows % 128 == 0
+
+    def temporal_block_supported(self, dtype, *, clips, frames, pixels, heads, d):
+        return self.fused
+
+    def attention_q_batch_mod_supported(self):
+        return True
+
+
+def _fmt(v):
+    if isinstance(v, Buf):
+        return f"T{v.storage}+{v.offset}{list(v.shape)}/{list(v.stride)}:{v.dtype.replace('torch.', '')}"
+    if isinstance(v, dict):
+        return "{" + ",".join(f"{k}:{_fmt(x)}" for k, x in v.items()) + "}"
+    if isinstance(v, list):
+        return "[" + ",".join(_fmt(x) for x in v) + "]"
+    return repr(v)
+
+
+def buffers(v):
+    """every Buf inside a recorded argument value"""
+    if isinstance(v, Buf):
+        yield v
+    elif isinstance(v, dict):
+        for x in v.values():
+            yield from buffers(x)
+    elif isinstance(v, list):
+        for x in v:
+            yield from buffers(x)
+
+
+def written(l: Launch):
+    """the Bufs a launch writes"""
+    for name in WRITES[l.op]:
+        v = l.args.get("heads") and l.args["heads"].get("outs") if name == "heads.outs" else l.args.get(name)
+        if v is not None:
+            yield from buffers(v)
+
+
+# ---- the trace matrix: tools/schedule_trace.py prints it, tests/test_schedule_dataflow.py checks its dataflow ------------------------
+# Only the engines' public surface is used (constructors, forward / decode / encode_moments, the module-level switches), so the
+# same matrix runs against any tree that has them.
+UNET_SHAPES = [(2, 4, 32, 32), (2, 2, 12, 8), (4, 2, 16, 16)]          # (B, F, H, W): frames of 1024 ... 4 rows, whole and straddled tiles
+
+
+def unet_cases():
+    """(id, shape, switches, shared_prefix, fused, temb_first)"""
+    out = []
+    for shape in UNET_SHAPES:
+        for direct in (False, True):
+            for share in (1, 2):
+                for fused in (False, True):
+                    tag = "x".join(map(str, shape)) + f"-direct{int(direct)}-share{share}-fused{int(fused)}"
+                    out.append((tag, shape, dict(DIRECT_STATS=direct), share, fused, False))
+    s = UNET_SHAPES[0]
+    out.append(("x".join(map(str, s)) + "-nofuse_stats", s, dict(FUSE_STATS=False), 1, True, False))
+    out.append(("x".join(map(str, s)) + "-fuse_rows-fused0", s, dict(FUSE_ROWS=True), 1, False, False))
+    out.append(("x".join(map(str, s)) + "-fuse_rows-fused1", s, dict(FUSE_ROWS=True), 1, True, False))
+    out.append(("x".join(map(str, s)) + "-temb_first", s, dict(DIRECT_STATS=True), 2, True, True))
+    return out
+
+
+def vae_cases():
+    """(id, 'decode' | 'encode', latent (h, w), FUSE_STATS)"""
+    return [(f"{kind}-{h}x{w}-fuse{int(fuse)}", kind, (h, w), fuse)
+            for kind in ("decode", "encode") for h, w in ((4, 4), (6, 2), (8, 8)) for fuse in (True, False)]
+
+
+def _patched(module, switches):
+    old = {k: getattr(module, k) for k in switches}
+    for k, v in switches.items():
+        setattr(module, k, v)
+    return old
+
+
+@functools.lru_cache(maxsize=None)
+def _packed(kind):
+    """the tiny models of tests/test_engine_emulated.py in bf16, packed once (the weight streams the engines cache inside are the
+    same for every case)"""
+    from followyourclick_amd.engine import UNet3DConfig, VAEDecoderConfig
+    from followyourclick_amd.engine import weights as EW
+    from oracle import functional as Fn
+    from oracle import weights as W
+    if kind == "unet":
+        cfg = UNet3DConfig(block_out_channels=(64, 128, 256, 256), cross_attention_dim=64, sample_size=8)
+        return EW.pack_unet(W.make_weights(W.unet_state_shapes(Fn.tiny_unet_config()), 0), cfg, torch.bfloat16, "cpu")
+    cfg, ocfg = VAEDecoderConfig(block_out_channels=(64, 128, 128, 128)), Fn.VAEConfig(block_out_channels=(64, 128, 128, 128))
+    if kind == "decode":
+        return EW.pack_vae_decoder(W.make_weights(W.vae_decoder_state_shapes(ocfg), 0), cfg, torch.bfloat16, "cpu")
+    return EW.pack_vae_encoder(W.make_weights(W.vae_encoder_state_shapes(ocfg), 0), cfg, torch.bfloat16, "cpu")
+
+
+def run_unet(case) -> TraceOps:
+    """one forward of the tiny UNet; the log holds the forward alone"""
+    from followyourclick_amd.engine import unet3d
+    _, (B, F, H, Wd), switches, share, fused, temb_first = case
+    ops = TraceOps(fused=fused)
+    old = _patched(unet3d, switches)
+    try:
+        eng = unet3d.UNet3DEngine(_packed("unet"), ops=ops)
+        eng.prepare_context(torch.zeros(B, 77, 64))
+        _, temb = eng.prepare_time_embeddings([500], [2] * B, [4] * B, B)
+        first = eng.prepare_time_embeddings([0], [2], [4], 1)[1] if temb_first else None
+        x = torch.zeros(B // share * F * H * Wd, 64, dtype=torch.bfloat16)      # shared_prefix=2: the distinct half of the CFG pair
+        ops.reset()
+        eng.forward(x, temb, B, F, H, Wd, temb_first=first, shared_prefix=share)
+    finally:
+        _patched(unet3d, old)
+    return ops
+
+
+def run_vae(case) -> TraceOps:
+    from followyourclick_amd.engine import vae
+    _, kind, (h, w), fuse = case
+    ops = TraceOps()
+    old = _patched(vae, dict(FUSE_STATS=fuse))
+    try:
+        if kind == "decode":
+            vae.VAEDecoderEngine(_packed(kind), ops=ops).decode(torch.zeros(3, 4, h, w))
+        else:
+            vae.VAEEncoderEngine(_packed(kind), ops=ops).encode_moments(torch.zeros(2, 3, 8 * h, 8 * w))
+    finally:
+        _patched(vae, old)
+    return ops
