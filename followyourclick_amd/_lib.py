@@ -41,7 +41,7 @@ class AttnArgs(C.Structure):
 
 class TAttnArgs(C.Structure):
     _fields_ = [("qkv", vp), ("o", vp), ("clips", i32), ("frames", i32), ("pixels", i32), ("heads", i32), ("d", i32),
-                ("scale", f32), ("dtype", i32)]
+                ("scale", f32), ("dtype", i32), ("rope_cos", vp), ("rope_sin", vp)]
 
 
 class GnStatsArgs(C.Structure):
@@ -166,7 +166,7 @@ MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 302        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 303        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

@@ -6,10 +6,16 @@
 // pure index arithmetic here: one wave64 owns one (clip b, pixel p, head h) task and gathers the
 // F rows of that pixel (row stride P*3C) straight into MFMA operand registers.
 //
-// 16-bit path (v_mfma_f32_16x16x32_bf16 / _f16: template parameter T), F <= 32:
+// 16-bit path (v_mfma_f32_16x16x32_bf16 / _f16: template parameter T), F <= 64:
 //   S^T = K Q^T (rows = key frames, cols = query frames), full softmax in registers (all keys of a
-//   query are in 4 lanes x 4..8 regs), O^T = V^T P^T with the keys as the 32 MFMA k-slots.
+//   query are in 4 lanes x 4..16 regs), O^T = V^T P^T with the keys as the 32 MFMA k-slots (two such
+//   MFMAs per output tile for F > 32).
 // f32 path: scalar reference-precision kernel (parity mode only).
+//
+// ROPE (template parameter; rope_cos / rope_sin of fyc_tattn_args, f32 [F][d/2]): q and k are rotated per
+// frame before the score product - x'[c] = x[c] cos[f][c mod h] -/+ x[c +/- h] sin[f][c mod h], h = d/2, the
+// rotate_half pairing of the reference's RoPE (rope.py:102-116) - in f32 on the loaded values and rounded
+// once to the operand type.  V is untouched.  The ROPE = false instantiations are the kernels without it.
 #include "fyc_common.h"
 
 namespace {
@@ -19,16 +25,63 @@ struct TAttnP {
   int clips, frames, pixels, heads, d;
   float scale;
   const char* zero;
+  const float* rope_cos; const float* rope_sin;
 };
 
 template <typename T> struct TMma;
 template <> struct TMma<bf16_t> { __device__ static __forceinline__ f32x4 k32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); } };
 template <> struct TMma<f16_t> { __device__ static __forceinline__ f32x4 k32(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); } };
 
-template <typename T, int DP, int DVT, int NFT>
+// rotate_half on the 8 head channels dd .. dd+7 of one frame's q or k row (`row` = the head's first channel of that row).  h = d/2 is
+// a multiple of 4, so each 4-channel run of the fragment lies wholly below or above h and its partner run starts h channels away: at
+// d = 8 inside this fragment, at d = 40 across two others.  The partners come from a second, 8-byte load of the same row (same cache
+// lines, no HBM traffic).  Lanes outside the problem read the zero page for values, partners and tables alike and keep their zeros.
+template <typename T>
+__device__ __forceinline__ typename Pair16<T>::Vec8 rope8(typename Pair16<T>::Vec8 x, const T* row, int dd, int hh, const float* ct,
+                                                          const float* st, bool ok, const T* zero) {
+  const u32x4 xb = __builtin_bit_cast(u32x4, x);
+  u32x4 xo;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int c0 = dd + 4 * r;
+    const bool low = c0 < hh;
+    const int cp = low ? c0 + hh : c0 - hh, cm = low ? c0 : c0 - hh;
+    float xp[4];
+    ElemIO<T>::ld4(ok ? row + cp : zero, xp);
+    const f32x4 cs = *reinterpret_cast<const f32x4*>(ok ? ct + cm : reinterpret_cast<const float*>(zero));
+    const f32x4 sn = *reinterpret_cast<const f32x4*>(ok ? st + cm : reinterpret_cast<const float*>(zero));
+    const float xv[4] = {Pair16<T>::lo(xb[2 * r]), Pair16<T>::hi(xb[2 * r]), Pair16<T>::lo(xb[2 * r + 1]), Pair16<T>::hi(xb[2 * r + 1])};
+    float y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = xv[i] * cs[i] + (low ? -xp[i] : xp[i]) * sn[i];
+    xo[2 * r] = Pair16<T>::pack(y[0], y[1]);
+    xo[2 * r + 1] = Pair16<T>::pack(y[2], y[3]);
+  }
+  return __builtin_bit_cast(typename Pair16<T>::Vec8, xo);
+}
+
+// V^T operand of output tile t for key-tile pair pp, gathered from the wave's LDS tile (layout: at the tile's declaration)
+template <typename T, int DP, int NFT>
+__device__ __forceinline__ typename Pair16<T>::Vec8 vfrag(const unsigned short (*vt)[DP + 8], int pp, int t, int g, int r16) {
+  const int dv = t * 16 + r16;
+  unsigned short e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int fr = 32 * pp + ((j < 4) ? 4 * g + j : 16 + 4 * g + (j - 4));
+    const bool ok = dv < DP && (j < 4 || 2 * pp + 1 < NFT);     // rows >= F and channels >= d hold zeros
+    e[j] = ok ? vt[fr][dv] : (unsigned short)0;
+  }
+  u32x4 pk;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) pk[i] = (unsigned)e[2 * i] | ((unsigned)e[2 * i + 1] << 16);
+  return __builtin_bit_cast(typename Pair16<T>::Vec8, pk);
+}
+
+template <typename T, int DP, int DVT, int NFT, bool ROPE>
 __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
   typedef typename Pair16<T>::Vec8 Frag;
   constexpr int KS = DP / 32;
+  constexpr int NP = (NFT + 1) / 2;   // k = 32 MFMAs per output tile of P V: one per pair of 16-frame key tiles
   const int lane = threadIdx.x & 63, g = lane >> 4, r16 = lane & 15;
   const long long task = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const long long ntask = (long long)p.clips * p.pixels * p.heads;
@@ -41,8 +94,13 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
   const long long fstride = (long long)p.pixels * ld;  // elements between consecutive frames of a pixel
   const T* zero = reinterpret_cast<const T*>(p.zero);
 
-  // Q / K fragments: lane (frame = 16*tile + r16, quad g) holds 8 consecutive head channels
-  Frag qf[NFT][KS], kf[NFT][KS];
+  // Q / K fragments: lane (frame = 16*tile + r16, quad g) holds 8 consecutive head channels.  LAZY (F > 32): the MFMA operands of all
+  // tiles (K, Q and V^T: 240 registers at d = 160, F = 64) do not fit the 256 architectural registers beside anything else, so only K
+  // stays resident; the Q tile of a pass is loaded at its top and the V^T fragments are gathered from the LDS tile where they are used.
+  // The same at F > 16 under ROPE, whose rotations hold partners and tables beside the operands (d = 160, F = 32: 264 -> 252 registers).
+  constexpr bool LAZY = NFT > 2 || (ROPE && NFT > 1);
+  const int hh = p.d >> 1;
+  Frag qf[LAZY ? 1 : NFT][KS], kf[NFT][KS];
 #pragma unroll
   for (int ft = 0; ft < NFT; ++ft) {
     const int fr = ft * 16 + r16;
@@ -50,11 +108,15 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
     for (int ks = 0; ks < KS; ++ks) {
       const int dd = 32 * ks + 8 * g;
       const bool ok = fr < F && dd < p.d;
-      qf[ft][ks] = *reinterpret_cast<const Frag*>(ok ? base + fr * fstride + dd : zero);
+      if constexpr (!LAZY) qf[ft][ks] = *reinterpret_cast<const Frag*>(ok ? base + fr * fstride + dd : zero);
       kf[ft][ks] = *reinterpret_cast<const Frag*>(ok ? base + fr * fstride + C + dd : zero);
+      if constexpr (ROPE) {
+        if constexpr (!LAZY) qf[ft][ks] = rope8<T>(qf[ft][ks], base + fr * fstride, dd, hh, p.rope_cos + fr * hh, p.rope_sin + fr * hh, ok, zero);
+        kf[ft][ks] = rope8<T>(kf[ft][ks], base + fr * fstride + C, dd, hh, p.rope_cos + fr * hh, p.rope_sin + fr * hh, ok, zero);
+      }
     }
   }
-  // V^T fragments: lane (dv = 16*t + r16, quad g): k-slot j<4 <-> frame 4g+j, j>=4 <-> frame 16+4g+(j-4).  The operand wants
+  // V^T fragments: lane (dv = 16*t + r16, quad g) of key-tile pair pp: k-slot j<4 <-> frame 32pp+4g+j, j>=4 <-> frame 32pp+16+4g+(j-4).  The operand wants
   // the FRAMES of one channel in a lane while memory has the channels of one frame contiguous: V rows are fetched like Q / K
   // (16 B per lane) and transposed through a wave-private LDS tile (2-byte gathers straight from global memory were 12-24
   // narrow requests per lane and held the kernel at 3.0 TB/s).  Row pitch DP + 8 elements: the four frame groups of a read
@@ -72,21 +134,23 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
     }
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // same wave wrote and reads: LDS ops of a wave complete in order
-  Frag vf[DVT];
+  Frag vf[LAZY ? 1 : NP][DVT];
+  if constexpr (!LAZY) {
 #pragma unroll
-  for (int t = 0; t < DVT; ++t) {
-    const int dv = t * 16 + r16;
-    unsigned short e[8];
+    for (int t = 0; t < DVT; ++t) {
+      const int dv = t * 16 + r16;
+      unsigned short e[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int fr = (j < 4) ? 4 * g + j : 16 + 4 * g + (j - 4);
-      const bool ok = dv < DP && (j < 4 || NFT > 1);     // rows >= F and channels >= d hold zeros
-      e[j] = ok ? vt[fr][dv] : (unsigned short)0;
+      for (int j = 0; j < 8; ++j) {
+        const int fr = (j < 4) ? 4 * g + j : 16 + 4 * g + (j - 4);
+        const bool ok = dv < DP && (j < 4 || NFT > 1);     // rows >= F and channels >= d hold zeros
+        e[j] = ok ? vt[fr][dv] : (unsigned short)0;
+      }
+      u32x4 pk;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pk[i] = (unsigned)e[2 * i] | ((unsigned)e[2 * i + 1] << 16);
+      vf[0][t] = __builtin_bit_cast(Frag, pk);
     }
-    u32x4 pk;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pk[i] = (unsigned)e[2 * i] | ((unsigned)e[2 * i + 1] << 16);
-    vf[t] = __builtin_bit_cast(Frag, pk);
   }
 
   const float sl2e = p.scale * 1.44269504088896340736f;
@@ -95,13 +159,23 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
 
 #pragma unroll
   for (int qt = 0; qt < NFT; ++qt) {
+    if constexpr (LAZY) {
+      const int fr = qt * 16 + r16;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const int dd = 32 * ks + 8 * g;
+        const bool ok = fr < F && dd < p.d;
+        qf[0][ks] = *reinterpret_cast<const Frag*>(ok ? base + fr * fstride + dd : zero);
+        if constexpr (ROPE) qf[0][ks] = rope8<T>(qf[0][ks], base + fr * fstride, dd, hh, p.rope_cos + fr * hh, p.rope_sin + fr * hh, ok, zero);
+      }
+    }
     // scores of query frame (qt*16 + r16) against key frames kt*16 + 4g + r
     f32x4 s[NFT];
 #pragma unroll
     for (int kt = 0; kt < NFT; ++kt) {
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) a = TMma<T>::k32(kf[kt][ks], qf[qt][ks], a);
+      for (int ks = 0; ks < KS; ++ks) a = TMma<T>::k32(kf[kt][ks], qf[LAZY ? 0 : qt][ks], a);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (kt * 16 + 4 * g + r >= F) a[r] = -INFINITY;
@@ -112,9 +186,9 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
     for (int kt = 0; kt < NFT; ++kt) mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    float pv[8], sum = 0.f;
+    float pv[8 * NP], sum = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) pv[j] = 0.f;
+    for (int j = 0; j < 8 * NP; ++j) pv[j] = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NFT; ++kt)
 #pragma unroll
@@ -126,16 +200,24 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
     const float inv = 1.0f / sum;
-    u32x4 pk;
+    Frag pf[NP];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      pk[i] = (unsigned)Pair16<T>::to_bits(pv[2 * i] * inv) | ((unsigned)Pair16<T>::to_bits(pv[2 * i + 1] * inv) << 16);
-    const Frag pf = __builtin_bit_cast(Frag, pk);
+    for (int pp = 0; pp < NP; ++pp) {
+      u32x4 pk;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        pk[i] = (unsigned)Pair16<T>::to_bits(pv[8 * pp + 2 * i] * inv) | ((unsigned)Pair16<T>::to_bits(pv[8 * pp + 2 * i + 1] * inv) << 16);
+      pf[pp] = __builtin_bit_cast(Frag, pk);
+    }
     const int fq = qt * 16 + r16;
 #pragma unroll
     for (int t = 0; t < DVT; ++t) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = TMma<T>::k32(vf[t], pf, acc);
+#pragma unroll
+      for (int pp = 0; pp < NP; ++pp) {
+        if constexpr (LAZY) acc = TMma<T>::k32(vfrag<T, DP, NFT>(vt, pp, t, g, r16), pf[pp], acc);
+        else acc = TMma<T>::k32(vf[pp][t], pf[pp], acc);
+      }
       const int dd = t * 16 + 4 * g;
       if (fq < F && dd < p.d) {
         float v[4] = {acc[0], acc[1], acc[2], acc[3]};
@@ -146,6 +228,7 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
 }
 
 // parity-mode kernel: one thread per (b, pixel, head, query frame); f32 throughout.
+template <bool ROPE>
 __global__ void __launch_bounds__(256) tattn_f32_kernel(const TAttnP p) {
   const long long total = (long long)p.clips * p.pixels * p.heads * p.frames;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -159,12 +242,23 @@ __global__ void __launch_bounds__(256) tattn_f32_kernel(const TAttnP p) {
   const float* base = reinterpret_cast<const float*>(p.qkv) + ((long long)b * F * p.pixels + pix) * ld + h * p.d;
   const long long fs = (long long)p.pixels * ld;
   const float* q = base + fq * fs;
-  float sc[32];
+  float sc[64];
   float mx = -INFINITY;
   for (int fk = 0; fk < F; ++fk) {
     const float* k = base + fk * fs + C;
     float a = 0.f;
-    for (int c = 0; c < p.d; ++c) a = fmaf(q[c], k[c], a);
+    if constexpr (ROPE) {
+      const int hh = p.d >> 1;
+      const float *cq = p.rope_cos + fq * hh, *sq = p.rope_sin + fq * hh, *ck = p.rope_cos + fk * hh, *sk = p.rope_sin + fk * hh;
+      for (int c = 0; c < p.d; ++c) {
+        const bool low = c < hh;
+        const int cp = low ? c + hh : c - hh, cm = low ? c : c - hh;
+        const float qr = q[c] * cq[cm] + (low ? -q[cp] : q[cp]) * sq[cm];
+        const float kr = k[c] * ck[cm] + (low ? -k[cp] : k[cp]) * sk[cm];
+        a = fmaf(qr, kr, a);
+      }
+    } else
+      for (int c = 0; c < p.d; ++c) a = fmaf(q[c], k[c], a);
     sc[fk] = a * p.scale;
     mx = fmaxf(mx, sc[fk]);
   }
@@ -179,25 +273,27 @@ __global__ void __launch_bounds__(256) tattn_f32_kernel(const TAttnP p) {
   }
 }
 
-template <typename T, int DP, int DVT>
+template <typename T, int DP, int DVT, bool ROPE>
 int launch_t(const TAttnP& p, hipStream_t st) {
   const long long ntask = (long long)p.clips * p.pixels * p.heads;
   dim3 grid((unsigned)((ntask + 3) / 4));
-  if (p.frames <= 16) hipLaunchKernelGGL((tattn_bf16_kernel<T, DP, DVT, 1>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((tattn_bf16_kernel<T, DP, DVT, 2>), grid, dim3(256), 0, st, p);
+  if (p.frames <= 16) hipLaunchKernelGGL((tattn_bf16_kernel<T, DP, DVT, 1, ROPE>), grid, dim3(256), 0, st, p);
+  else if (p.frames <= 32) hipLaunchKernelGGL((tattn_bf16_kernel<T, DP, DVT, 2, ROPE>), grid, dim3(256), 0, st, p);
+  else if (p.frames <= 48) hipLaunchKernelGGL((tattn_bf16_kernel<T, DP, DVT, 3, ROPE>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((tattn_bf16_kernel<T, DP, DVT, 4, ROPE>), grid, dim3(256), 0, st, p);
   FYC_CHECK_LAUNCH("fyc_temporal_attention");
   return 0;
 }
 
-template <typename T>
+template <typename T, bool ROPE>
 int launch_d(const TAttnP& p, hipStream_t st) {
-  if (p.d <= 32) return launch_t<T, 32, 2>(p, st);
-  if (p.d <= 48) return launch_t<T, 64, 3>(p, st);
-  if (p.d <= 64) return launch_t<T, 64, 4>(p, st);
-  if (p.d <= 80) return launch_t<T, 96, 5>(p, st);
-  if (p.d <= 96) return launch_t<T, 96, 6>(p, st);
-  if (p.d <= 128) return launch_t<T, 128, 8>(p, st);
-  return launch_t<T, 160, 10>(p, st);
+  if (p.d <= 32) return launch_t<T, 32, 2, ROPE>(p, st);
+  if (p.d <= 48) return launch_t<T, 64, 3, ROPE>(p, st);
+  if (p.d <= 64) return launch_t<T, 64, 4, ROPE>(p, st);
+  if (p.d <= 80) return launch_t<T, 96, 5, ROPE>(p, st);
+  if (p.d <= 96) return launch_t<T, 96, 6, ROPE>(p, st);
+  if (p.d <= 128) return launch_t<T, 128, 8, ROPE>(p, st);
+  return launch_t<T, 160, 10, ROPE>(p, st);
 }
 
 }  // namespace
@@ -206,18 +302,25 @@ extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
   FYC_REQUIRE(a && a->qkv && a->o, "fyc_temporal_attention: null pointer");
   FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_temporal_attention: fyc_init() not called");
   FYC_REQUIRE(a->clips > 0 && a->frames > 0 && a->pixels > 0 && a->heads > 0, "fyc_temporal_attention: bad sizes");
-  FYC_REQUIRE(a->frames <= 32, "fyc_temporal_attention: frames=%d > 32 unsupported", a->frames);
+  FYC_REQUIRE(a->frames <= 64, "fyc_temporal_attention: frames=%d > 64 unsupported", a->frames);
+  FYC_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), "fyc_temporal_attention: rope_cos and rope_sin must both be set or both be NULL");
+  FYC_REQUIRE((((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) & 15) == 0, "fyc_temporal_attention: rope tables must be 16-byte aligned");
   FYC_REQUIRE(a->d % 8 == 0 && a->d >= 8 && a->d <= 160, "fyc_temporal_attention: head dim %d", a->d);
   TAttnP p;
   p.qkv = a->qkv; p.o = a->o; p.clips = a->clips; p.frames = a->frames; p.pixels = a->pixels; p.heads = a->heads; p.d = a->d;
   p.scale = a->scale; p.zero = (const char*)g_fyc_zero_page;
+  p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
+  const bool rope = a->rope_cos != nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (a->dtype == FYC_F32) {
     const long long total = (long long)p.clips * p.pixels * p.heads * p.frames;
-    hipLaunchKernelGGL(tattn_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (rope) hipLaunchKernelGGL(tattn_f32_kernel<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(tattn_f32_kernel<false>, grid, dim3(256), 0, st, p);
     FYC_CHECK_LAUNCH("fyc_temporal_attention(f32)");
     return 0;
   }
   FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16, "fyc_temporal_attention: bad dtype");
-  return a->dtype == FYC_F16 ? launch_d<f16_t>(p, st) : launch_d<bf16_t>(p, st);
+  if (rope) return a->dtype == FYC_F16 ? launch_d<f16_t, true>(p, st) : launch_d<bf16_t, true>(p, st);
+  return a->dtype == FYC_F16 ? launch_d<f16_t, false>(p, st) : launch_d<bf16_t, false>(p, st);
 }

@@ -24,7 +24,7 @@ from followyourclick_amd import default_compute_dtype, ops as ops_mod
 from followyourclick_amd.engine import UNet3DConfig
 from followyourclick_amd.engine.schema import unet_schema
 from followyourclick_amd.engine.unet3d import UNet3DEngine
-from followyourclick_amd.engine.weights import pack_unet, pad_channels, sinusoidal_pe
+from followyourclick_amd.engine.weights import pack_unet, pad_channels, rope_inv_freq, sinusoidal_pe
 
 
 @dataclass
@@ -46,7 +46,9 @@ def _attach(root: nn.Module, name: str, shape, buffer: bool) -> None:
         if part not in node._modules:
             node.add_module(part, _Node())
         node = node._modules[part]
-    if buffer:
+    if buffer and leaf == "inv_freq":      # rotary embedding of a RoPE motion module (reference rope.py:66-67)
+        node.register_buffer(leaf, rope_inv_freq(2 * shape[0]), persistent=True)
+    elif buffer:
         node.register_buffer(leaf, sinusoidal_pe(shape[2], shape[1])[None].clone(), persistent=True)
     else:
         node.register_parameter(leaf, nn.Parameter(torch.empty(shape), requires_grad=False))
@@ -82,7 +84,7 @@ class UNet3DConditionModel(nn.Module):
             "use_pseudo_conv3d": use_pseudo_conv3d,
             "use_text_encoder_2": use_text_encoder_2, "use_inflated_groupnorm": use_inflated_groupnorm,
             "use_temporal_conv": use_temporal_conv, "motion_module_decoder_only": motion_module_decoder_only,
-            "use_rope_postion_encoding": mm.get("use_rope_postion_encoding", False), "add_temporal_lora": mm.get("add_temporal_lora", False),
+            "add_temporal_lora": mm.get("add_temporal_lora", False),
         }
         bad = [k for k, v in unsupported.items() if v]
         if bad:
@@ -104,7 +106,10 @@ class UNet3DConditionModel(nn.Module):
             motion_module_resolutions=tuple(motion_module_resolutions), motion_module_mid_block=bool(motion_module_mid_block),
             motion_num_attention_heads=mm.get("num_attention_heads", 8), motion_num_transformer_block=mm.get("num_transformer_block", 2),
             motion_attention_blocks=len(blocks), temporal_position_encoding=bool(mm.get("temporal_position_encoding", False)),
-            temporal_position_encoding_max_len=mm.get("temporal_position_encoding_max_len", 24), use_fps_condition=bool(use_fps_condition),
+            temporal_position_encoding_max_len=mm.get("temporal_position_encoding_max_len", 24),
+            use_rope_position_encoding=bool(mm.get("use_rope_postion_encoding", False)),       # (sic: the reference's spelling)
+            rope_video_length=int(mm.get("video_length", 16)), rope_train_video_length=int(mm.get("train_video_length", 16)),
+            use_fps_condition=bool(use_fps_condition),
             use_first_frame_mask_condition_concat=bool(use_first_frame_mask_condition_concat),
             use_first_frame_condition_concat=bool(use_first_frame_condition_concat), use_camera_motion_condition=bool(use_camera_motion_condition),
             use_ip_cross_attention=bool(use_ip_cross_attention),
@@ -118,7 +123,7 @@ class UNet3DConditionModel(nn.Module):
         self.config = SimpleNamespace(**kwargs)
         self.compute_dtype = compute_dtype if compute_dtype is not None else default_compute_dtype()
         for name, shape in unet_schema(self.engine_config).items():
-            _attach(self, name, shape, buffer=name.endswith("pos_encoder.pe"))
+            _attach(self, name, shape, buffer=name.endswith(("pos_encoder.pe", "rope.em.inv_freq")))
         self.image_proj_model = None   # set by scripts/inference.py:167 (`unet.image_proj_model = ip_adapter.init_proj()`)
         self._engine: Optional[UNet3DEngine] = None
         self._engine_key = None

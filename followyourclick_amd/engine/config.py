@@ -28,6 +28,12 @@ class UNet3DConfig:
     motion_attention_blocks: int = 2
     temporal_position_encoding: bool = True
     temporal_position_encoding_max_len: int = 24
+    # motion_module_kwargs.use_rope_postion_encoding / video_length / train_video_length (reference motion_module.py:335-353, rope.py:120-173):
+    # q and k of the temporal attention are rotated per frame instead of adding the sinusoidal table to the tokens; the queries of a model
+    # built for rope_video_length > rope_train_video_length carry the factor ln(train) / ln(video)
+    use_rope_position_encoding: bool = False
+    rope_video_length: int = 16
+    rope_train_video_length: int = 16
     use_fps_condition: bool = True
     use_camera_motion_condition: bool = False      # camera_motion_embedding added to the time embedding (reference unet.py:134-137, 538-544)
     use_first_frame_mask_condition_concat: bool = True
@@ -54,6 +60,8 @@ class UNet3DConfig:
                 raise ValueError(f"block_out_channels must be multiples of 64 (got {c}): K tiles of the MFMA GEMM are 64 bf16")
             if c % self.attention_head_dim or (c // self.attention_head_dim) % 8:
                 raise ValueError(f"head dim {c}/{self.attention_head_dim} must be a multiple of 8")
+        if self.use_rope_position_encoding and (self.rope_video_length < 2 or self.rope_train_video_length < 1):
+            raise ValueError("rope_video_length must be >= 2 and rope_train_video_length >= 1 (the query factor is ln(train) / ln(video))")
         if self.cross_attention_dim % 8:
             raise ValueError("cross_attention_dim must be a multiple of 8")
 

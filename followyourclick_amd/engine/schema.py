@@ -17,7 +17,7 @@ from typing import Dict, Tuple
 import torch
 
 from .config import UNet3DConfig, VAEDecoderConfig
-from .weights import sinusoidal_pe
+from .weights import rope_inv_freq, sinusoidal_pe
 
 Schema = "OrderedDict[str, Tuple[int, ...]]"
 
@@ -79,7 +79,9 @@ class _S(OrderedDict):
             t = f"{p}.transformer_blocks.{b}"
             for a in range(cfg.motion_attention_blocks):
                 self.attn(f"{t}.attention_blocks.{a}", c, c)
-                if cfg.temporal_position_encoding:
+                if cfg.use_rope_position_encoding:       # no pos_encoder; the rotary embedding's persistent buffer (reference rope.py:66-67)
+                    self[f"{t}.attention_blocks.{a}.rope.em.inv_freq"] = (c // cfg.motion_num_attention_heads // 2,)
+                elif cfg.temporal_position_encoding:
                     self[f"{t}.attention_blocks.{a}.pos_encoder.pe"] = (1, cfg.temporal_position_encoding_max_len, c)
             for a in range(cfg.motion_attention_blocks):
                 self.norm(f"{t}.norms.{a}", c)
@@ -184,13 +186,15 @@ def vae_encoder_schema(cfg: VAEDecoderConfig, in_channels: int = 3) -> "OrderedD
 
 def random_state_dict(schema: "OrderedDict[str, Tuple[int, ...]]", seed: int, materialize: bool = True) -> Dict[str, torch.Tensor]:
     """Random-initialised weights of the architecture (no checkpoints exist offline): N(0, 1/fan_in)
-    kernels, norm gains 1 + 0.1 N, small biases; `pos_encoder.pe` buffers analytic.  With
+    kernels, norm gains 1 + 0.1 N, small biases; `pos_encoder.pe` / `rope.em.inv_freq` buffers analytic.  With
     materialize=False tensors are left uninitialised (ranks that receive the weights by broadcast)."""
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = OrderedDict()
     for name, shape in schema.items():
         if name.endswith("pos_encoder.pe"):
             sd[name] = sinusoidal_pe(shape[2], shape[1])[None].clone()
+        elif name.endswith("rope.em.inv_freq"):
+            sd[name] = rope_inv_freq(2 * shape[0])
         elif not materialize:
             sd[name] = torch.empty(shape, dtype=torch.float32)
         else:

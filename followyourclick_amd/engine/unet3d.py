@@ -30,7 +30,7 @@ from .. import _lib as L
 from .. import ops as ops_mod
 from .base import ChanStats, EngineBase
 from .config import UNet3DConfig
-from .weights import Packed, pack_ff_block, pack_panel_linear, pack_temporal_block
+from .weights import Packed, pack_ff_block, pack_panel_linear, pack_temporal_block, rope_tables
 
 Tensor = torch.Tensor
 
@@ -281,6 +281,15 @@ class UNet3DEngine(EngineBase):
             cache[key] = a.pe_w[:F].repeat(B, 1).contiguous()
         return cache[key]
 
+    def _rope(self, d: int, F: int) -> Tuple[Tensor, Tensor]:
+        """(cos, sin) device tables of the rotary temporal attention, built once per (head dim, clip length)"""
+        if F > 64:
+            raise ValueError(f"video_length {F}: the rotary temporal attention covers clips of up to 64 frames")
+        cache = self.__dict__.setdefault("_rope_tables", {})
+        if (d, F) not in cache:
+            cache[(d, F)] = tuple(t.to(self.device) for t in rope_tables(d, F))
+        return cache[(d, F)]
+
     def _axpy(self, x: Tensor, y: Tensor, rows: int, C: int, alpha: float) -> None:
         """y = y + alpha * x via the GEMM epilogue (parity mode only): (x @ (alpha*I)) + y."""
         key = ("axpy", C, alpha)
@@ -422,9 +431,17 @@ class UNet3DEngine(EngineBase):
         N, Hm = g["H"] * g["W"], self.cfg.motion_num_attention_heads
         d = C // Hm
         tok = self._norm_proj_in(x, m, rows, N)
+        scale, rope_kw = d ** -0.5, {}
+        if self.cfg.use_rope_position_encoding:
+            # q and k are rotated inside fyc_temporal_attention (the fused sub-block kernels have no rotation: never taken here).  The
+            # query factor of a model built for clips longer than its training length is the CONSTRUCTOR's video_length against
+            # train_video_length, whatever F this call runs (reference rope.py:169-172); it rides on the softmax scale.
+            rope_kw = dict(rope=self._rope(d, g["F"]))
+            if self.cfg.rope_video_length > self.cfg.rope_train_video_length:
+                scale *= math.log(self.cfg.rope_train_video_length) / math.log(self.cfg.rope_video_length)
         for bi, blk in enumerate(m.blocks):
             for a in blk.attns:
-                if FUSE_TEMPORAL and a.qkv_f is not None and o.temporal_block_supported(self.dtype, clips=g["B"], frames=g["F"], pixels=N, heads=Hm, d=d):
+                if not rope_kw and FUSE_TEMPORAL and a.qkv_f is not None and o.temporal_block_supported(self.dtype, clips=g["B"], frames=g["F"], pixels=N, heads=Hm, d=d):
                     cache = a.setdefault("_tblock", {})      # per-head operands, packed once per clip length
                     if g["F"] not in cache:
                         cache[g["F"]] = pack_temporal_block(a, Hm, g["F"])
@@ -445,7 +462,7 @@ class UNet3DEngine(EngineBase):
                     n = self.layer_norm(tok.t, a.ln, rows, C, pe=a.pe, pe_div=N, pe_rows=g["F"])
                     qkv = self.lin(n, a.qkv_w, rows)
                 att = self.new(rows, C)
-                o.temporal_attention(qkv, att, clips=g["B"], frames=g["F"], pixels=N, heads=Hm, d=d, scale=d ** -0.5)
+                o.temporal_attention(qkv, att, clips=g["B"], frames=g["F"], pixels=N, heads=Hm, d=d, scale=scale, **rope_kw)
                 tok = self._lin_rp(att, a.o_w, rows, bias=a.o_b, residual=tok.t)
             last = bi == len(m.blocks) - 1
             tok = self.feed_forward_out(blk.ff, blk.ff_ln, tok, x.t if last else None, rows, C, nxt if last else None)   # inner blocks: identity projection

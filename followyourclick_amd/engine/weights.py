@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import os
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -164,7 +164,7 @@ def _motion(sd, p: str, cfg: UNet3DConfig, dtype, device) -> Packed:
         for a in range(cfg.motion_attention_blocks):
             ab = f"{t}.attention_blocks.{a}"
             pe = None
-            if cfg.temporal_position_encoding:
+            if cfg.temporal_position_encoding and not cfg.use_rope_position_encoding:      # RoPE: nothing is added to the tokens
                 # analytic table (== the persistent `pos_encoder.pe` buffer, reference motion_module.py:286-304);
                 # regenerated so that clips longer than a checkpoint's max_len still work
                 pe = sinusoidal_pe(C, max(cfg.temporal_position_encoding_max_len, 32)).to(device)
@@ -364,6 +364,20 @@ def sinusoidal_pe(channels: int, length: int) -> Tensor:
     pe[:, 0::2] = torch.sin(pos * div)
     pe[:, 1::2] = torch.cos(pos * div)
     return pe.contiguous()
+
+
+def rope_inv_freq(d: int, base: float = 10000.0) -> Tensor:
+    """inv_freq[i] = base^(-2i/d), i < d/2, in f32 as the reference's rotary embedding builds it (rope.py:66)"""
+    return 1.0 / (base ** (torch.arange(0, d, 2).float() / d))
+
+
+def rope_tables(d: int, frames: int) -> Tuple[Tensor, Tensor]:
+    """(cos, sin) f32 [frames][d/2] of angle[f][i] = f * inv_freq[i]: the operand of temporal_attention(rope=...).  From the formula,
+    not from a checkpoint's `rope.em.inv_freq`: the reference fills cos_cached / sin_cached in the constructor, before any
+    load_state_dict, and does not rebuild them from the loaded buffer (rope.py:63-99).  Its tables repeat these d/2 columns twice
+    (`cat((freqs, freqs))`) and are cast to the activation dtype; these stay f32."""
+    ang = torch.einsum("i,j->ij", torch.arange(frames, dtype=torch.float32), rope_inv_freq(d))
+    return ang.cos().contiguous(), ang.sin().contiguous()
 
 
 def pack_unet(sd: Dict[str, Tensor], cfg: UNet3DConfig, dtype, device) -> Packed:

@@ -11,7 +11,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -235,11 +235,18 @@ class HipOps:
         self._call("fyc_repeat", a)
 
     def temporal_attention(self, qkv: Tensor, o: Tensor, *, clips: int, frames: int, pixels: int, heads: int, d: int,
-                           scale: float) -> None:
+                           scale: float, rope: Optional[Tuple[Tensor, Tensor]] = None) -> None:
+        """rope = (cos, sin): f32 device tables [frames][d/2]; q and k are rotated per frame before the score product (include/fyc.h)"""
         self.ensure_init(qkv.device)
         a = L.TAttnArgs()
         a.qkv, a.o, a.clips, a.frames, a.pixels, a.heads, a.d, a.scale, a.dtype = (_p(qkv), _p(o), clips, frames, pixels,
                                                                                   heads, d, scale, _dt(qkv))
+        if rope is not None:
+            cos, sin = rope
+            for t in (cos, sin):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != qkv.device or tuple(t.shape) != (frames, d // 2):
+                    raise ValueError(f"temporal_attention: rope tables must be contiguous f32 [{frames}][{d // 2}] tensors on {qkv.device}")
+            a.rope_cos, a.rope_sin = cos.data_ptr(), sin.data_ptr()
         self._call("fyc_temporal_attention", a)
 
     def _tblock_args(self, x, out, w_qkv, colsum, bias, pe_bias, w_out, b_out, clips, frames, pixels, heads, d, scale, eps):

@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off. */
-#define FYC_VERSION 302
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64. */
+#define FYC_VERSION 303
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -171,13 +171,20 @@ int fyc_attention(const fyc_attn_args* a, void* stream);
  * For every (clip b, pixel p, head h): softmax over the F frames (motion_module.py:371-464 with
  * mm_attn_cross.py:148-177).  qkv is the token-major output of the fused to_q|to_k|to_v GEMM,
  * [(b f p)][3C]; o is token-major [(b f p)][C].  The '(b f) d c -> (b d) f c' transposes of the
- * reference are index arithmetic here.
+ * reference are index arithmetic here.  frames <= 64, d a multiple of 8 up to 160.
  */
 typedef struct {
   const void* qkv; void* o;
   int32_t clips, frames, pixels, heads, d;
   float scale;
   int32_t dtype;
+  /* (version 303) rotary position encoding of the motion module (use_rope_postion_encoding; motion_module.py:408-422, rope.py:102-116):
+   * f32 tables [frames][d/2], both set or both NULL (= off).  With h = d/2, q and k of frame f are replaced before the score product by
+   *   x'[c] = x[c] * cos[f][c mod h] - x[c+h] * sin[f][c mod h]   (c <  h)
+   *   x'[c] = x[c] * cos[f][c mod h] + x[c-h] * sin[f][c mod h]   (c >= h)
+   * (rotate_half), computed in f32 on the loaded values and rounded once to `dtype`; v is untouched.  The reference's query factor
+   * log(train_video_length) / log(video_length) for clips longer than the training length goes into `scale`. */
+  const float* rope_cos; const float* rope_sin;
 } fyc_tattn_args;
 int fyc_temporal_attention(const fyc_tattn_args* a, void* stream);
 
