@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FYC_LIB_PATH") or os.path.join(HERE, "libfyc_hip.so")   # FYC_LIB_PATH: A/B builds
 
 FYC_F32, FYC_BF16, FYC_F16 = 0, 1, 2
-GEMM_PLAIN, GEMM_CONV3X3, GEMM_CONV3X3_UP2 = 0, 1, 2
+GEMM_PLAIN, GEMM_CONV3X3, GEMM_CONV3X3_UP2, GEMM_CONV_T3 = 0, 1, 2, 3
 EPI_LINEAR, EPI_GEGLU, EPI_HEADS = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2
 
@@ -29,7 +29,8 @@ class GemmArgs(C.Structure):
                 ("Hout", i32), ("Wout", i32), ("Hin", i32), ("Win", i32), ("Cin", i32), ("conv_stride", i32), ("conv_pad", i32),
                 ("rows_per_batch", i32), ("seg_cols", i32), ("heads", i32), ("tokens", i32),
                 ("out_scale", f32), ("dtype", i32), ("tile", i32), ("act", i32), ("ln_stats", vp), ("ln_colsum", vp),
-                ("ln_nparts", i32), ("ln_eps", f32), ("chan_parts", vp), ("cs_rows", i32), ("row_parts", vp), ("row_nparts", i32), ("workspace", vp), ("workspace_bytes", i64)]
+                ("ln_nparts", i32), ("ln_eps", f32), ("chan_parts", vp), ("cs_rows", i32), ("row_parts", vp), ("row_nparts", i32), ("workspace", vp), ("workspace_bytes", i64),
+                ("t3_frames", i32), ("t3_rows", i32)]
 
 
 class AttnArgs(C.Structure):
@@ -166,7 +167,7 @@ MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 303        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 304        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

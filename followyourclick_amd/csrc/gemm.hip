@@ -1,5 +1,5 @@
 // Host entry of the GEMM family: argument validation, tile/ring selection, dispatch.
-// Kernel template: gemm_kernel.h; instantiations: gemm_bf16_plain.hip, gemm_bf16_conv.hip, gemm_f32.hip.
+// Kernel template: gemm_kernel.h; instantiations: gemm_{bf16,f16}_{plain,conv,act,t3}.hip, gemm_f32.hip, gemm_f32_t3.hip.
 // The round-4 main-loop experiments that measured slower on every shape (ping-pong wave groups, tile configs 21 / 22 / 23; epilogue
 // under the next tile's K loop, config 31) live in tools/exp/gemm_variants/ and are only part of a library built with
 // FYC_GEMM_VARIANTS=1 (python -m followyourclick_amd._build; tests: tools/exp/gemm_variants/test_gemm_variants_gpu.py).
@@ -216,7 +216,8 @@ int split_of(const fyc_gemm_args* a, int& cfg) {
   // fyc_set_tuning key 10 = v > 0 (A/B): at least v K tiles per slice instead of 16, and K >= 128 v instead of 2048 - the K = 1280 linears
   // of the 8x8 latent level (profiles/r06_gemm_small_m_split_k.txt)
   const int min_kt = g_fyc_tuning[10] > 0 ? g_fyc_tuning[10] : 10;     // (16 until round 6: the K = 2560 shortcut of the 8x8 level now splits 4 ways, 39 -> 33 us)
-  if (a->M > 4096 || a->K < (g_fyc_tuning[10] > 0 ? 128 * min_kt : 2048) || a->N % 8 != 0 || a->N < 256) return 1;
+  // (under key 10 one 128-column tile is enough, so that a small test problem can be made to split; the default rule is untouched)
+  if (a->M > 4096 || a->K < (g_fyc_tuning[10] > 0 ? 128 * min_kt : 2048) || a->N % 8 != 0 || a->N < (g_fyc_tuning[10] > 0 ? 128 : 256)) return 1;
   const int c = (a->N % 320 == 0) ? 6 : 1;                     // 128x320 or 128x128 tiles
   const int bn = (c == 6) ? 320 : 128;
   const long long tiles = (long long)((a->M + 127) / 128) * ((a->N + bn - 1) / bn);
@@ -304,15 +305,27 @@ extern "C" int fyc_gemm(const fyc_gemm_args* a, void* stream) {
     const long long lim = 0xffffffffll;
     const bool small = (long long)a->N * a->ldw < lim &&
                        (a->mode == FYC_GEMM_PLAIN ? ((long long)a->M * a->lda < lim && (a->a2 == nullptr || (long long)a->M * a->lda2 < lim))
+                        : a->mode == FYC_GEMM_CONV_T3 ? (long long)a->M * a->Cin < lim
                                                   : (a->Hout > 0 && a->Wout > 0 && (long long)a->M / ((long long)a->Hout * a->Wout) * a->Hin * a->Win * a->Cin < lim));
     FYC_REQUIRE(small, "fyc_gemm: an operand has 2^32 elements or more (M=%d lda=%d N=%d ldw=%d): split the call", a->M, a->lda, a->N, a->ldw);
   }
+  FYC_REQUIRE(a->mode == FYC_GEMM_CONV_T3 || (a->t3_frames == 0 && a->t3_rows == 0), "fyc_gemm: t3_frames / t3_rows belong to FYC_GEMM_CONV_T3 (mode %d)", a->mode);
   if (a->mode == FYC_GEMM_PLAIN) {
     FYC_REQUIRE(a->lda % ch == 0 && a->stride_a % ch == 0, "fyc_gemm: lda/stride_a must keep 16-B alignment");
     if (a->a2 != nullptr) {
       FYC_REQUIRE(a->k_split > 0 && a->k_split < a->K && a->k_split % (8 * ch) == 0, "fyc_gemm: k_split=%d must be a multiple of %d inside (0, K)", a->k_split, 8 * ch);
       FYC_REQUIRE(a->lda2 % ch == 0 && ((uintptr_t)a->a2 % 16) == 0 && batch == 1, "fyc_gemm: a2 alignment / batch");
     }
+  } else if (a->mode == FYC_GEMM_CONV_T3) {
+    // 3 taps along the frame axis: a = [clips * t3_frames * t3_rows][Cin] channels-last, K order (slab, tap, channel)
+    FYC_REQUIRE(a->Cin > 0 && a->Cin % 64 == 0, "fyc_gemm conv_t3: Cin=%d must be a multiple of 64", a->Cin);
+    FYC_REQUIRE(a->K == 3 * a->Cin, "fyc_gemm conv_t3: K=%d != 3*Cin (Cin=%d)", a->K, a->Cin);
+    FYC_REQUIRE(a->t3_frames > 0 && a->t3_rows > 0, "fyc_gemm conv_t3: t3_frames=%d / t3_rows=%d must be positive", a->t3_frames, a->t3_rows);
+    FYC_REQUIRE((long long)a->M % ((long long)a->t3_frames * a->t3_rows) == 0, "fyc_gemm conv_t3: M=%d is not a whole number of clips of %d x %d rows", a->M, a->t3_frames, a->t3_rows);
+    FYC_REQUIRE(batch == 1, "fyc_gemm conv_t3: batch must be 1");
+    FYC_REQUIRE(a->a2 == nullptr && a->epilogue == FYC_EPI_LINEAR && a->act == FYC_ACT_NONE && a->ln_stats == nullptr,
+                "fyc_gemm conv_t3: the LINEAR epilogue without activation, a2 or a folded LayerNorm");
+    p.t3_frames = a->t3_frames; p.t3_rows = a->t3_rows;
   } else {
     const int bk = 8 * ch;
     FYC_REQUIRE(a->mode == FYC_GEMM_CONV3X3 || a->mode == FYC_GEMM_CONV3X3_UP2, "fyc_gemm: bad mode %d", a->mode);
@@ -417,6 +430,7 @@ extern "C" int fyc_gemm(const fyc_gemm_args* a, void* stream) {
       if (scfg == 6 && g_fyc_tuning[9] == 2 && pp_ok) scfg = 22;
 #endif
       const int rc = fycg::pp_cfg(scfg) ? (a->mode == FYC_GEMM_PLAIN ? fycg::run_pp_plain(q, scfg, st) : fycg::run_pp_conv(q, scfg, st))
+                     : a->mode == FYC_GEMM_CONV_T3 ? (f16 ? fycg::run_f16_t3(q, batch, scfg, 2, st) : fycg::run_bf16_t3(q, batch, scfg, 2, st))
                      : f16 ? ((a->mode == FYC_GEMM_PLAIN) ? fycg::run_f16_plain(q, batch, scfg, 2, st) : fycg::run_f16_conv(q, batch, scfg, 2, st))
                      : (a->mode == FYC_GEMM_PLAIN) ? fycg::run_bf16_plain(q, batch, scfg, 2, st) : fycg::run_bf16_conv(q, batch, scfg, 2, st);
       if (rc != 0) return rc;
@@ -445,6 +459,11 @@ extern "C" int fyc_gemm(const fyc_gemm_args* a, void* stream) {
   }
   FYC_REQUIRE(a->chan_parts == nullptr || a->dtype == FYC_F32 || p.wide || cfg == 1 || cfg == 2, "fyc_gemm: chan_parts in bf16 needs the 16-byte aligned layout or tile config 1 / 2");
   FYC_REQUIRE(a->row_parts == nullptr || a->dtype == FYC_F32 || p.wide, "fyc_gemm: row_parts in bf16 needs the 16-byte aligned layout (N, ldo, ldr multiples of 8; aligned pointers)");
+  if (a->mode == FYC_GEMM_CONV_T3) {
+    if (fycg::pp_cfg(cfg) || fycg::ov_cfg(cfg)) cfg = pp_twin(cfg);      // (the main-loop experiments are not built for this mode)
+    if (a->dtype == FYC_F32) return fycg::run_f32_t3(p, batch, cfg, st);
+    return f16 ? fycg::run_f16_t3(p, batch, cfg, ns, st) : fycg::run_bf16_t3(p, batch, cfg, ns, st);
+  }
   if (a->dtype == FYC_F32) return fycg::run_f32(p, batch, cfg, st);
   if (p.act != FYC_ACT_NONE) {
     FYC_REQUIRE(a->mode == FYC_GEMM_PLAIN, "fyc_gemm: act needs the PLAIN mode");

@@ -54,7 +54,7 @@ struct GemmP {
   int colc;   // bias / colsum / tile-uniform rowbias may be fetched 16 B at a time and staged through LDS once per tile
   int rb_tile; // rowbias row is the same for every row of a tile (rows_per_batch % BM == 0): folded into the staged bias
   int rb_slots; // bf16 LINEAR wide epilogue: a tile touches up to this many rowbias rows (rows_per_batch % 16 == 0), staged through LDS next to the bias
-  int splitk; float* ws;   // split-K (small M, long K): `splitk` work items per output tile, raw f32 partials to ws[splitk][M][N]
+  int splitk; int t3_frames; float* ws;   // t3_frames: CONV_T3, frames per clip.  split-K (small M, long K): `splitk` work items per output tile, raw f32 partials to ws[splitk][M][N]
   int stagger; // 8-wave tiles: the upper half of the waves issues its DMAs between its two MFMA k-steps (fyc_set_tuning key 5 = 1: off)
   int wide;   // bf16 linear epilogue may use 16-B row accesses (N, ldo, ldr multiples of 8; bias/rowbias 16-B aligned)
   const char* zero;
@@ -63,9 +63,11 @@ struct GemmP {
   int fast1;   // packed LINEAR epilogue: specialised pass 1 (fyc_set_tuning key 13 = 1: the generic one, A/B)
   int heads_pk; // head-split epilogue: the pack-first form (epilogue_heads_packed) - M <= 8192 only, see launch()
   int pre;     // round 6: the epilogue's per-row / per-column inputs are already in LDS (issue_consts in fyc_gemm_kernel), see pre_bytes()
-  int phase_delay;   // round 6 (A/B, fyc_set_tuning key 11): every other block of an XCD starts this many x 1024 cycles late, see fyc_gemm_kernel
+  int phase_delay; int t3_rows;   // t3_rows: CONV_T3, rows per frame (H*W).  phase_delay: round 6 (A/B, fyc_set_tuning key 11): every other block of an XCD starts this many x 1024 cycles late, see fyc_gemm_kernel
   unsigned long long* trace;   // timing builds (-DFYC_TRACE, tools/gemm_phase_probe.py): per-block s_memtime stamps; nullptr otherwise
 };
+// (t3_frames / t3_rows sit in the two alignment holes the struct had: its size and every kernel-argument offset of the older modes stay put)
+static_assert(sizeof(GemmP) == 392, "GemmP grew: the kernel-argument offsets of every instantiation move");
 
 // timing builds: waves 0 and 4 of a block append the shader clock to their list ([block][2][128] u64, zeroed by the host; the
 // count lives in a register so that a stamp is one store and no load)
@@ -1391,7 +1393,14 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   // 9-bit mask of the taps that fall inside the image (0 for rows beyond M) - built once per tile (KT = 45..360 K tiles follow);
   // per K tile a gather address is pos0 + tap offset (scalar) -> one 64-bit multiply-add
   constexpr bool C3 = (MODE == FYC_GEMM_CONV3X3);
+  // frame-axis conv (CONV_T3): output row m reads rows m - HW, m, m + HW of the same clip - the tap shift is a whole number of rows and the same
+  // for every row, so the base is the PLAIN one (a_base) and the only per-row state is a 3-bit presence mask (0 for rows beyond M), packed for
+  // all A_IT rows of the thread into one register
+  constexpr bool T3 = (MODE == FYC_GEMM_CONV_T3);
+  constexpr int TAPS = T3 ? 3 : 9;
+  static_assert(!T3 || A_IT * 3 <= 32, "CONV_T3: the presence masks of a thread's rows share one register");
   int a_pos[C3 ? A_IT : 1], a_msk[C3 ? A_IT : 1];
+  unsigned t_msk = 0, t_step = 0;     // CONV_T3: packed masks; element offset of one frame (HW * Cin)
   int a_pix[MODE == FYC_GEMM_CONV3X3_UP2 ? A_IT : 1], a_yx[MODE == FYC_GEMM_CONV3X3_UP2 ? A_IT : 1];   // upsampled conv: frame pixel base (-1: row outside M), (iy0 << 16) | (ix0 & 0xffff)
   int tap = 0, c0 = 0;  // conv: filter tap and channel offset of the K tile being issued
   // split-K: work item w = (output tile w / S, K slice w % S); K slice s covers K tiles [s*KT/S, (s+1)*KT/S)
@@ -1403,12 +1412,23 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
     const int t = remap(work / S);
     tile_coords(p, t, i_tm, i_tn);
     const int kt0 = kt_begin(work);
-    tap = kt0 % 9; c0 = (kt0 / 9) * BK;      // conv K order (slab, tap, channel): K tile kt = tap kt%9 of slab kt/9 (RB = 128; host keeps split-K off the 64-byte tiles)
+    tap = kt0 % TAPS; c0 = (kt0 / TAPS) * BK;      // conv K order (slab, tap, channel): K tile kt = tap kt%9 of slab kt/9 (RB = 128; host keeps split-K off the 64-byte tiles)
     if (MODE == FYC_GEMM_PLAIN || S == 1) { tap = 0; c0 = 0; }
     b_base = (unsigned)(i_tn * BN + lrow) * (unsigned)p.ldw + koff;
     if (MODE == FYC_GEMM_PLAIN) {
       a_base = (unsigned)(i_tm * BM + lrow) * (unsigned)p.lda + koff;
       a2_base = (unsigned)(i_tm * BM + lrow) * (unsigned)p.lda2 + koff - p.k_split;     // (+ k0 >= k_split at use)
+    } else if constexpr (T3) {
+      a_base = (unsigned)(i_tm * BM + lrow) * (unsigned)p.Cin + koff;
+      t_step = (unsigned)p.t3_rows * (unsigned)p.Cin;
+      t_msk = 0;
+#pragma unroll
+      for (int it = 0; it < A_IT; ++it) {
+        const int m = i_tm * BM + lrow + it * ROWS_IT;
+        const int f = (m / p.t3_rows) % p.t3_frames;
+        const unsigned msk = (f > 0 ? 1u : 0u) | 2u | (f + 1 < p.t3_frames ? 4u : 0u);
+        if (m < p.M) t_msk |= msk << (3 * it);
+      }
     } else {
 #pragma unroll
       for (int it = 0; it < A_IT; ++it) {
@@ -1440,6 +1460,10 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
       if (m >= p.M || k >= p.K) return zero;
       if (A2 != nullptr && k >= p.k_split) return A2 + (size_t)(a2_base + (unsigned)(it * ROWS_IT) * (unsigned)p.lda2 + k0);
       return A + (size_t)(a_base + (unsigned)(it * ROWS_IT) * (unsigned)p.lda + k0);
+    } else if constexpr (T3) {
+      // row m + (tap - 1) * HW of the same clip (unsigned wrap-around: an address is only formed for a tap that is present, and then lies in [0, M * Cin))
+      const unsigned e = a_base + (unsigned)(it * ROWS_IT) * (unsigned)p.Cin + (unsigned)(tap - 1) * t_step + (unsigned)c0;
+      return ((t_msk >> (3 * it + tap)) & 1u) ? A + (size_t)e : zero;
     } else if (C3) {
       const int ky = tap / 3, kx = tap - 3 * ky;                      // wave-uniform
       const int pos = a_pos[it] + ky * p.Win + kx;
@@ -1606,9 +1630,9 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
     for (int it = 0; it < B_IT; ++it) glds16(src_b(it, k0), sB + (it * NT + wave * 64) * 16);
     if (MODE != FYC_GEMM_PLAIN) {  // K order = (128-B channel slab, ky, kx, channel): the 9 taps of a slab are adjacent
       if (RB == 128) {
-        if (++tap == 9) { tap = 0; c0 += BK; }
+        if (++tap == TAPS) { tap = 0; c0 += BK; }
       } else {                       // 64-B tiles: two tiles per (slab, tap) unit
-        if (c0 & BK) { c0 -= BK; if (++tap == 9) { tap = 0; c0 += 2 * BK; } }
+        if (c0 & BK) { c0 -= BK; if (++tap == TAPS) { tap = 0; c0 += 2 * BK; } }
         else c0 += BK;
       }
     }
@@ -1902,5 +1926,9 @@ int run_f32(const GemmP& p, int batch, int cfg, hipStream_t st);
 int run_f16_plain(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_f16_conv(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_f16_act(const GemmP& p, int batch, int cfg, hipStream_t st);
+// 3-tap convolution along the frame axis (FYC_GEMM_CONV_T3): gemm_{bf16,f16,f32}_t3.hip
+int run_bf16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
+int run_f16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
+int run_f32_t3(const GemmP& p, int batch, int cfg, hipStream_t st);
 
 }  // namespace fycg

@@ -107,9 +107,10 @@ class EngineBase:
         return nbytes if nbytes <= self._direct_limit() else None
 
     def gn_from_stats(self, srcs: Sequence[Tuple[Tensor, Optional[ChanStats]]], gamma: Tensor, beta: Tensor, rows: int,
-                      rows_per_sample: int, eps: float, silu: bool) -> Optional[Tensor]:
+                      rows_per_sample: int, eps: float, silu: bool, groups: Optional[int] = None) -> Optional[Tensor]:
         """GroupNorm (+SiLU) of one activation, or of the channel concat of two, from their producers' sums: the one
-        fyc_gn_apply_cs call.  None when a source has no sums at this granularity (the caller runs the statistics pass)."""
+        fyc_gn_apply_cs call.  None when a source has no sums at this granularity (the caller runs the statistics pass).
+        `groups`: a norm whose group count is not the model's (TemporalConvBlock: always 32)."""
         sts = [st for _, st in srcs]
         if any(st is None or st.out_rows != sts[0].out_rows for st in sts) or rows_per_sample % sts[0].out_rows:
             return None
@@ -128,7 +129,7 @@ class EngineBase:
                 kw.update(cs2=self._stats(sts[1]))
             kw.update(cs_rows=s1.out_rows)
         y = self.new(rows, sum(st.C for st in sts))
-        self.ops.gn_apply_cs(srcs[0][0], cs1, gamma, beta, y, rows=rows, C1=s1.C, groups=self.groups, rows_per_sample=rows_per_sample,
+        self.ops.gn_apply_cs(srcs[0][0], cs1, gamma, beta, y, rows=rows, C1=s1.C, groups=groups or self.groups, rows_per_sample=rows_per_sample,
                              eps=eps, silu=silu, **kw)
         return y
 
@@ -169,11 +170,13 @@ class EngineBase:
                       chan_parts=None if stats is None else stats.parts, cs_rows=0 if stats is None else stats.stat_rows)
         return out
 
-    def group_norm(self, x: Tensor, g: Tensor, b: Tensor, rows: int, C: int, rows_per_sample: int, eps: float, silu: bool) -> Tensor:
-        stats = self.new(rows // rows_per_sample, self.groups, 2, dtype=torch.float64)
-        self.ops.gn_stats(x, stats, rows=rows, C_=C, groups=self.groups, rows_per_sample=rows_per_sample)
+    def group_norm(self, x: Tensor, g: Tensor, b: Tensor, rows: int, C: int, rows_per_sample: int, eps: float, silu: bool,
+                   groups: Optional[int] = None) -> Tensor:
+        groups = groups or self.groups
+        stats = self.new(rows // rows_per_sample, groups, 2, dtype=torch.float64)
+        self.ops.gn_stats(x, stats, rows=rows, C_=C, groups=groups, rows_per_sample=rows_per_sample)
         y = self.new(rows, C)
-        self.ops.gn_apply(x, stats, g, b, y, rows=rows, C_=C, groups=self.groups, rows_per_sample=rows_per_sample,
+        self.ops.gn_apply(x, stats, g, b, y, rows=rows, C_=C, groups=groups, rows_per_sample=rows_per_sample,
                           eps=eps, silu=silu)
         return y
 

@@ -38,6 +38,10 @@ class UNet3DConfig:
     use_camera_motion_condition: bool = False      # camera_motion_embedding added to the time embedding (reference unet.py:134-137, 538-544)
     use_first_frame_mask_condition_concat: bool = True
     use_first_frame_condition_concat: bool = False
+    # use_inflated_groupnorm (reference resnet.py:9-17, 237-263, unet.py:342-343): norm1 / norm2 of every ResNet and conv_norm_out take their
+    # statistics per frame instead of per clip; use_temporal_conv (resnet.py:29-68, 288-294, 339-340): a TemporalConvBlock behind every ResNet
+    use_inflated_groupnorm: bool = False
+    use_temporal_conv: bool = False
     use_ip_cross_attention: bool = False
     ip_scale: float = 1.0
     ip_num_tokens: int = 4

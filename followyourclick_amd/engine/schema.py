@@ -36,7 +36,7 @@ class _S(OrderedDict):
         self[p + ".weight"] = (c,)
         self[p + ".bias"] = (c,)
 
-    def resnet(self, p, cin, cout, temb):
+    def resnet(self, p, cin, cout, temb, temporal_conv=False):
         self.norm(p + ".norm1", cin)
         self.conv(p + ".conv1", cout, cin, 3)
         if temb:
@@ -45,6 +45,12 @@ class _S(OrderedDict):
         self.conv(p + ".conv2", cout, cout, 3)
         if cin != cout:
             self.conv(p + ".conv_shortcut", cout, cin, 1)
+        if temporal_conv:       # TemporalConvBlock (reference resnet.py:44-55): Sequential(GroupNorm, SiLU, [Dropout,] Conv3d (3,1,1))
+            for i in range(1, 5):
+                t = f"{p}.temporal_conv.conv{i}"
+                self.norm(t + ".0", cout)
+                self[f"{t}.{2 if i == 1 else 3}.weight"] = (cout, cout, 3, 1, 1)
+                self[f"{t}.{2 if i == 1 else 3}.bias"] = (cout,)
 
     def attn(self, p, c, ctx, ip=False):
         self.lin(p + ".to_q", c, c, False)
@@ -93,6 +99,7 @@ class _S(OrderedDict):
 def unet_schema(cfg: UNet3DConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     s = _S()
     boc, temb, nb = cfg.block_out_channels, cfg.time_embed_dim, len(cfg.block_out_channels)
+    tc = cfg.use_temporal_conv
     s.conv("conv_in", boc[0], cfg.conv_in_channels, 3)
     for name in (["time_embedding"] + (["camera_motion_embedding"] if cfg.use_camera_motion_condition else [])
                  + (["fps_embedding", "motion_embedding"] if cfg.use_fps_condition else [])):
@@ -102,7 +109,7 @@ def unet_schema(cfg: UNet3DConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     for i, bt in enumerate(cfg.down_block_types):
         inp, out = out, boc[i]
         for j in range(cfg.layers_per_block):
-            s.resnet(f"down_blocks.{i}.resnets.{j}", inp if j == 0 else out, out, temb)
+            s.resnet(f"down_blocks.{i}.resnets.{j}", inp if j == 0 else out, out, temb, tc)
             if bt.startswith("CrossAttn"):
                 s.transformer(f"down_blocks.{i}.attentions.{j}", out, cfg)
             if cfg.use_motion_module and (2 ** i) in cfg.motion_module_resolutions:
@@ -110,11 +117,11 @@ def unet_schema(cfg: UNet3DConfig) -> "OrderedDict[str, Tuple[int, ...]]":
         if i != nb - 1:
             s.conv(f"down_blocks.{i}.downsamplers.0.conv", out, out, 3)
     c = boc[-1]
-    s.resnet("mid_block.resnets.0", c, c, temb)
+    s.resnet("mid_block.resnets.0", c, c, temb, tc)
     s.transformer("mid_block.attentions.0", c, cfg)
     if cfg.use_motion_module and cfg.motion_module_mid_block:
         s.motion("mid_block.motion_modules.0", c, cfg)
-    s.resnet("mid_block.resnets.1", c, c, temb)
+    s.resnet("mid_block.resnets.1", c, c, temb, tc)
     rev = list(reversed(boc))
     out = rev[0]
     for i, bt in enumerate(cfg.up_block_types):
@@ -122,7 +129,7 @@ def unet_schema(cfg: UNet3DConfig) -> "OrderedDict[str, Tuple[int, ...]]":
         inp = rev[min(i + 1, nb - 1)]
         nl = cfg.layers_per_block + 1
         for j in range(nl):
-            s.resnet(f"up_blocks.{i}.resnets.{j}", (prev if j == 0 else out) + (inp if j == nl - 1 else out), out, temb)
+            s.resnet(f"up_blocks.{i}.resnets.{j}", (prev if j == 0 else out) + (inp if j == nl - 1 else out), out, temb, tc)
             if bt.startswith("CrossAttn"):
                 s.transformer(f"up_blocks.{i}.attentions.{j}", out, cfg)
             if cfg.use_motion_module and (2 ** (nb - 1 - i)) in cfg.motion_module_resolutions:

@@ -210,15 +210,15 @@ class UNet3DEngine(EngineBase):
         return DIRECT_STATS_BYTES
 
     def _gn(self, x: Union[Act, Tuple[Act, Act]], gamma: Tensor, beta: Tensor, rows: int, rows_per_sample: int, eps: float,
-            silu: bool) -> Tuple[Tensor, Optional[Tensor]]:
+            silu: bool, groups: Optional[int] = None) -> Tuple[Tensor, Optional[Tensor]]:
         """GroupNorm (+SiLU) of an activation or of the channel concat of two (up blocks: cat([hidden, skip], dim=1),
         reference unet_blocks.py:763,885).  Returns (normalised tensor, materialised concat or None)."""
         xs = (x,) if isinstance(x, Act) else x
-        y = self.gn_from_stats([(a.t, a.st) for a in xs], gamma, beta, rows, rows_per_sample, eps, silu)
+        y = self.gn_from_stats([(a.t, a.st) for a in xs], gamma, beta, rows, rows_per_sample, eps, silu, groups)
         if y is not None:
             return y, None
         if len(xs) == 1:
-            return self.group_norm(x.t, gamma, beta, rows, x.C, rows_per_sample, eps, silu), None
+            return self.group_norm(x.t, gamma, beta, rows, x.C, rows_per_sample, eps, silu, groups), None
         a, b = xs
         cat = self.new(rows, a.C + b.C)
         self.ops.concat_channels(a.t, b.t, cat, rows=rows, c1=a.C, c2=b.C)
@@ -312,16 +312,18 @@ class UNet3DEngine(EngineBase):
         return Act(out, C, self._produced(st), rp, rp_n)
 
     def resnet(self, r: Packed, x: Union[Act, Tuple[Act, Act]], temb: Tensor, g: dict, nxt: Tuple[int, int]) -> Act:
-        """ResnetBlock3D (reference resnet.py:296-342): cross-frame GroupNorm statistics.  x may be the (hidden, skip) pair of an
-        up block: the concat only ever exists normalised (norm1's output); the 1x1 shortcut reads both sources (dual-K GEMM)."""
+        """ResnetBlock3D (reference resnet.py:296-342): cross-frame GroupNorm statistics, per-frame ones with use_inflated_groupnorm
+        (InflatedGroupNorm, resnet.py:9-17).  x may be the (hidden, skip) pair of an up block: the concat only ever exists normalised
+        (norm1's output); the 1x1 shortcut reads both sources (dual-K GEMM).  use_temporal_conv: the TemporalConvBlock follows."""
         rows, rpb = g["rows"], g["F"] * g["H"] * g["W"]
         frames = g["B"] * g["F"]
-        h, cat = self._gn(x, r.n1_g, r.n1_b, rows, rpb, self.cfg.norm_eps, True)
+        gn_rows = g["H"] * g["W"] if self.cfg.use_inflated_groupnorm else rpb      # rows per sample of norm1 / norm2
+        h, cat = self._gn(x, r.n1_g, r.n1_b, rows, gn_rows, self.cfg.norm_eps, True)
         tb = temb[:, r.temb_off:]  # view: row pitch stays temb_total (ldrb)
         # time-embedding row per clip, or per (clip, frame) when frame 0 carries the timestep-0 embedding (use_first_frame_condition)
-        h1 = self._conv_act(h, r.c1_w, r.c1_b, frames, g["H"], g["W"], (g["H"] * g["W"], rpb), rowbias=tb,
+        h1 = self._conv_act(h, r.c1_w, r.c1_b, frames, g["H"], g["W"], (g["H"] * g["W"], gn_rows), rowbias=tb,
                             rpb=g["H"] * g["W"] if g.get("temb_per_frame") else rpb, ldrb=temb.shape[1])
-        h2, _ = self._gn(h1, r.n2_g, r.n2_b, rows, rpb, self.cfg.norm_eps, True)
+        h2, _ = self._gn(h1, r.n2_g, r.n2_b, rows, gn_rows, self.cfg.norm_eps, True)
         if r.sc_w is None:
             sc = x.t
         elif isinstance(x, Act) or cat is not None:
@@ -331,7 +333,29 @@ class UNet3DEngine(EngineBase):
             sc = self.new(rows, r.cout)
             self.ops.gemm(a.t, r.sc_w, sc, M=rows, N=r.cout, K=a.C + b.C, lda=a.C, ldw=a.C + b.C, ldo=r.cout, bias=r.sc_b,
                           a2=b.t, k_split=a.C, lda2=b.C)
-        return self._conv_act(h2, r.c2_w, r.c2_b, frames, g["H"], g["W"], nxt, residual=sc)
+        if r.tconv is None:
+            return self._conv_act(h2, r.c2_w, r.c2_b, frames, g["H"], g["W"], nxt, residual=sc)
+        y = self._conv_act(h2, r.c2_w, r.c2_b, frames, g["H"], g["W"], (g["H"] * g["W"], rpb), residual=sc)
+        return self.temporal_conv(r.tconv, y, g, nxt)
+
+    def temporal_conv(self, tc: List[Packed], x: Act, g: dict, nxt: Tuple[int, int]) -> Act:
+        """TemporalConvBlock (reference resnet.py:29-68): x + conv4(conv3(conv2(conv1(x)))), conv_i = GroupNorm(32, eps 1e-5) -> SiLU ->
+        Conv3d (3,1,1).  nn.GroupNorm sees the 5-D tensor: cross-frame statistics whatever use_inflated_groupnorm says, always 32 groups
+        and the default eps.  Each convolution is one FYC_GEMM_CONV_T3 launch whose epilogue writes the sums of the next norm; the
+        fourth adds x and writes those of the caller's consumer."""
+        rows, hw, F, C = g["rows"], g["H"] * g["W"], g["F"], x.C
+        h = x
+        for i, s in enumerate(tc):
+            last = i == len(tc) - 1
+            n, _ = self._gn(h, s.g, s.b, rows, F * hw, 1e-5, True, groups=32)
+            onx = nxt if last else (hw, F * hw)
+            st = self._cs_plan(rows, onx[0], C, 3 * C, L.GEMM_CONV_T3, onx[1])
+            out = self.new(rows, C)
+            self.ops.gemm(n, s.w, out, M=rows, N=C, K=3 * C, lda=C, ldw=3 * C, ldo=C, bias=s.cb, residual=x.t if last else None, ldr=C,
+                          mode=L.GEMM_CONV_T3, conv=dict(Cin=C, frames=F, rows=hw),
+                          chan_parts=None if st is None else st.parts, cs_rows=0 if st is None else st.stat_rows)
+            h = self._act(out, C, st)
+        return h
 
     def feed_forward_out(self, ff: Packed, ln, tok: Act, residual: Optional[Tensor], rows: int, C: int, nxt=None) -> Act:
         """LN -> GEGLU FF -> (+tok) -> output projection (+residual) with FF2 and the projection merged into one GEMM
@@ -510,8 +534,8 @@ class UNet3DEngine(EngineBase):
         def frame(gg):      # the consumer is a per-frame GroupNorm (transformer / motion module)
             return hw(gg), hw(gg)
 
-        def clip(gg):       # the consumer is a cross-frame GroupNorm (ResNet norm1 / conv_norm_out)
-            return hw(gg), F * hw(gg)
+        def clip(gg):       # the consumer is a ResNet's norm1 / conv_norm_out: cross-frame, per frame with use_inflated_groupnorm
+            return hw(gg), (hw(gg) if cfg.use_inflated_groupnorm else F * hw(gg))
 
         def layer(l, xin, gg):
             """resnet [-> transformer] [-> motion module]; each stage tells its producer which norm consumes its output"""
@@ -569,5 +593,5 @@ class UNet3DEngine(EngineBase):
                 g2["rows"] = B * F * Hn * Wn
                 x = self._conv_act(x.t, blk.up.w, blk.up.b, frames, g["H"], g["W"], clip(g2), up2=True, up_size=(Hn, Wn))
                 g = g2
-        h, _ = self._gn(x, P.out_g, P.out_b, g["rows"], F * hw(g), cfg.norm_eps, True)
+        h, _ = self._gn(x, P.out_g, P.out_b, g["rows"], clip(g)[1], cfg.norm_eps, True)
         return self.conv(h, P.conv_out_w, P.conv_out_b, frames, g["H"], g["W"])

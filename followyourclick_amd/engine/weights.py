@@ -44,6 +44,15 @@ def pack_conv3x3(w: Tensor, dtype, device) -> Tensor:
     return p.reshape(O, 9 * Ip).to(dtype).contiguous().to(device)
 
 
+def pack_conv_t3(w: Tensor, dtype, device) -> Tensor:
+    """Conv3d (O, I, 3, 1, 1) -> [O][slab][tap][c in slab]: K order of FYC_GEMM_CONV_T3 (the 3 frame taps of a slab are adjacent K tiles)"""
+    O, I, kt, kh, kw = w.shape
+    assert (kt, kh, kw) == (3, 1, 1) and I % K_ALIGN == 0
+    sl = conv_slab(dtype)
+    p = w.detach().float().reshape(O, I // sl, sl, 3).permute(0, 1, 3, 2)
+    return p.reshape(O, 3 * I).to(dtype).contiguous().to(device)
+
+
 def pack_linear(w: Tensor, dtype, device, k_pad: Optional[int] = None) -> Tensor:
     w = w.reshape(w.shape[0], -1)  # also accepts (O, I, 1, 1)
     if k_pad is not None and k_pad != w.shape[1]:
@@ -101,6 +110,13 @@ def _resnet(sd: Dict[str, Tensor], p: str, dtype, device, temb: bool = True) -> 
     if (p + ".conv_shortcut.weight") in sd:
         r["sc_w"] = pack_linear(sd[p + ".conv_shortcut.weight"], dtype, device)
         r["sc_b"] = f32(sd[p + ".conv_shortcut.bias"], device)
+    r["tconv"] = None
+    if (p + ".temporal_conv.conv1.0.weight") in sd:     # TemporalConvBlock: four (GroupNorm(32), SiLU, Conv3d (3,1,1)) stages
+        r["tconv"] = []
+        for i in range(1, 5):
+            n, c = f"{p}.temporal_conv.conv{i}.0", f"{p}.temporal_conv.conv{i}.{2 if i == 1 else 3}"
+            r["tconv"].append(Packed(g=f32(sd[n + ".weight"], device), b=f32(sd[n + ".bias"], device),
+                                     w=pack_conv_t3(sd[c + ".weight"], dtype, device), cb=f32(sd[c + ".bias"], device)))
     return r
 
 
@@ -402,6 +418,10 @@ def pack_unet(sd: Dict[str, Tensor], cfg: UNet3DConfig, dtype, device) -> Packed
 
     def add_resnet(p):
         r = _resnet(sd, p, dtype, device)
+        if not cfg.use_temporal_conv:
+            r["tconv"] = None
+        elif r.tconv is None:
+            raise KeyError(f"use_temporal_conv: the state dict has no {p}.temporal_conv.* entries")
         r["temb_off"] = sum(w.shape[0] for w in temb_w)
         temb_w.append(sd[p + ".time_emb_proj.weight"])
         temb_b.append(sd[p + ".time_emb_proj.bias"])

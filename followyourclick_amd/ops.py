@@ -195,7 +195,9 @@ class HipOps:
         g.a2, g.k_split, g.lda2 = _p(a2), k_split, lda2
         if a.dtype != w.dtype:
             raise TypeError(f"gemm: activation {a.dtype} vs weight {w.dtype}")
-        if conv is not None:
+        if conv is not None and mode == L.GEMM_CONV_T3:      # 3 taps along the frame axis: channels, frames per clip, rows per frame
+            g.Cin, g.t3_frames, g.t3_rows = conv["Cin"], conv["frames"], conv["rows"]
+        elif conv is not None:
             g.Hout, g.Wout, g.Hin, g.Win, g.Cin, g.conv_stride = (conv["Hout"], conv["Wout"], conv["Hin"], conv["Win"],
                                                                   conv["Cin"], conv.get("stride", 1))
             g.conv_pad = conv.get("pad", 1)

@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64. */
-#define FYC_VERSION 303
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off. */
+#define FYC_VERSION 304
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -51,7 +51,7 @@ int fyc_device_caps(int64_t* caps);
  * not part of the product library): key 8 = 1: no s_setprio around the MFMA phases of the ping-pong loop; key 9 = 2: the ping-pong loop (tile
  * configs 21 / 22 / 23) wherever it is built, 3: the overlapped-epilogue kernel (config 31).  In the product library key 9 is ignored and a
  * request for one of those tile configs runs its one-phase twin (5 / 6 / 7 / 6): the one-phase loop always;
- * key 10 = v > 0: split-K for M <= 4096 keeps at least v K tiles per slice (default 16) and starts at K >= 128 v (default 2048);
+ * key 10 = v > 0: split-K for M <= 4096 keeps at least v K tiles per slice (default 16), starts at K >= 128 v (default 2048) and at N >= 128 (default 256);
  * key 11 = v > 0: every other GEMM block of an XCD starts v x 1024 cycles late (phase shift between the CUs' epilogues, A/B);
  * key 12 = 1: the GEMM epilogues load their per-row / per-column inputs themselves instead of finding them pre-staged in LDS (A/B);
  * key 13 = 1: the generic pass 1 of the packed LINEAR epilogue instead of its specialised copies (A/B);
@@ -70,14 +70,21 @@ int fyc_set_tuning(int key, int value);
  */
 /* CONV3X3_UP2: 3x3 conv over the nearest-neighbour upsampling of the input to (Hout, Wout); 2x is the fast path,
  * any Hout >= Hin works (Upsample3D with a forwarded `upsample_size`, reference resnet.py:152-157, unet.py:644-645) */
-enum { FYC_GEMM_PLAIN = 0, FYC_GEMM_CONV3X3 = 1, FYC_GEMM_CONV3X3_UP2 = 2 };
+/* CONV_T3 (version 304): nn.Conv3d(C, C, (3,1,1), padding=(1,0,0)) of TemporalConvBlock (animatediff/models/resnet.py:29-68) on the channels-last
+ * activation a = [clips * t3_frames * t3_rows][Cin]; output row m belongs to frame f = (m / t3_rows) % t3_frames and
+ *   out[m][n] = sum_{t<3} sum_c a[m + (t-1) * t3_rows][c] * W[n][c][t],  a tap being present only if 0 <= f + t - 1 < t3_frames
+ * (an absent tap reads the zero page: never the neighbouring clip, never outside the tensor).  K = 3*Cin, Cin a multiple of 64, M a whole number
+ * of clips; LINEAR epilogue with bias, rowbias, residual, out_scale, chan_parts; split-K like the 3x3 modes.  Weight (O, I, 3, 1, 1) packed as
+ * [O][slab][tap][c in slab] with 128-byte channel slabs (64 16-bit / 32 f32 channels): K tile kt = tap kt % 3 of slab kt / 3, ldw = 3*Cin
+ * (engine/weights.py::pack_conv_t3). */
+enum { FYC_GEMM_PLAIN = 0, FYC_GEMM_CONV3X3 = 1, FYC_GEMM_CONV3X3_UP2 = 2, FYC_GEMM_CONV_T3 = 3 };
 enum { FYC_EPI_LINEAR = 0, FYC_EPI_GEGLU = 1, FYC_EPI_HEADS = 2 };
 /* pointwise activation of the LINEAR epilogue (conditioning encoders): exact erf GELU (CLIP-ViT-H `gelu`, ip_adapter/resampler.py:17)
  * and x*sigmoid(1.702x) (CLIP-ViT-L text encoder `quick_gelu`) */
 enum { FYC_ACT_NONE = 0, FYC_ACT_GELU = 1, FYC_ACT_QUICK_GELU = 2 };
 
 typedef struct {
-  const void* a;         /* PLAIN: [batch][M][lda]; CONV: NHWC input [frames][Hin][Win][Cin] */
+  const void* a;         /* PLAIN: [batch][M][lda]; CONV: NHWC input [frames][Hin][Win][Cin]; CONV_T3: [clips * t3_frames * t3_rows][Cin] */
   const void* a2;        /* PLAIN only, optional: K columns >= k_split come from a2[m][k - k_split] (row pitch lda2): A = [a | a2] */
   const void* w;         /* [batch?][Nw][ldw], K contiguous; conv: K = 9*Cin ordered (slab, ky, kx, c) with 128-byte channel slabs */
   const float* bias;     /* [N] or NULL (GEGLU: packed order) */
@@ -126,6 +133,8 @@ typedef struct {
    * problem would like (0: no split); with less, or NULL, the GEMM runs unsplit.  16-byte aligned device memory, contents
    * undefined before and after the call. */
   void* workspace; int64_t workspace_bytes;
+  /* (version 304) FYC_GEMM_CONV_T3: frames per clip and rows per frame (H*W) of `a`; both zero in every other mode */
+  int32_t t3_frames, t3_rows;
 } fyc_gemm_args;
 int fyc_gemm(const fyc_gemm_args* a, void* stream);
 /* scratch bytes fyc_gemm can use for these arguments (split-K partial sums); 0 = none needed */
