@@ -24,7 +24,7 @@ extern "C" int fyc_attention(const fyc_attn_args* a, void* stream) {
   // profiles/r02_attention_variants.txt); small ones QT = 2 so that the grid still fills the chip.  tuning key 3 forces QT.
   const long long wg3 = (long long)a->batch * a->heads * ((a->n_q + 191) / 192);
   int qt = (a->n_q >= 1024 && wg3 >= 512 && a->d <= 48) ? 3 : 2;      // larger head dims: 3 tiles no longer fit 2 waves / SIMD
-  if (g_fyc_tuning[3] >= 2 && g_fyc_tuning[3] <= 4 && (a->d <= 80 || g_fyc_tuning[3] == 2)) qt = g_fyc_tuning[3];
+  if (g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] >= 2 && g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] <= 4 && (a->d <= 80 || g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] == 2)) qt = g_fyc_tuning[FYC_TUNE_ATTN_VARIANT];
   if (a->dtype == FYC_F16) {
     if (a->d <= 48) return fyca::run_small<f16_t>(p, qt, st);
     if (a->d <= 96) return fyca::run_medium<f16_t>(p, qt, st);

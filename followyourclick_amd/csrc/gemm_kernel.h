@@ -1832,21 +1832,21 @@ int launch(const GemmP& p, int batch, hipStream_t st) {
     constexpr int BK = (RB / 16) * (16 / (int)sizeof(T));
     const int kt = (p.K + BK - 1) / BK;
     const bool rb_ok = p.rowbias == nullptr || (EPI == FYC_EPI_LINEAR && (q.rb_tile || q.rb_slots > 0));
-    q.pre = (PRE_BUILT && g_fyc_tuning[12] != 1 && kt >= 2 && !(q.splitk > 1) && p.ln_nparts == 0 && rb_ok && p.wide &&
+    q.pre = (PRE_BUILT && g_fyc_tuning[FYC_TUNE_NO_PRESTAGE] != 1 && kt >= 2 && !(q.splitk > 1) && p.ln_nparts == 0 && rb_ok && p.wide &&
              (p.ln_stats == nullptr || (p.M % 2 == 0 && ((uintptr_t)p.ln_stats % 16) == 0))) ? 1 : 0;
   }
-  q.fast1 = g_fyc_tuning[13] == 1 ? 0 : 1;
+  q.fast1 = g_fyc_tuning[FYC_TUNE_GENERIC_PASS1] == 1 ? 0 : 1;
   // pack-first head-split epilogue: in the pipeline it wins at the 16x16 level only (8192x3840x1280 0.588 -> 0.562 ms per DDIM step, 8192x1280x1280
   // 0.235 -> 0.212) and LOSES at the 64x64 / 32x32 levels (131072x960x320 0.970 -> 1.051, 32768x1920x640 0.666 -> 0.756: profiles/r06_gemm_epilogue_ab.txt
   // part 4) - key 15 = 1 forces it on, 2 off
-  q.heads_pk = g_fyc_tuning[15] == 1 ? 1 : g_fyc_tuning[15] == 2 ? 0 : (p.M <= 8192 ? 1 : 0);
-  q.stagger = g_fyc_tuning[5] == 1 ? 0 : 1;
-  q.phase_delay = g_fyc_tuning[11] > 0 ? g_fyc_tuning[11] : 0;
+  q.heads_pk = g_fyc_tuning[FYC_TUNE_HEADS_PACKED] == 1 ? 1 : g_fyc_tuning[FYC_TUNE_HEADS_PACKED] == 2 ? 0 : (p.M <= 8192 ? 1 : 0);
+  q.stagger = g_fyc_tuning[FYC_TUNE_NO_STAGGER] == 1 ? 0 : 1;
+  q.phase_delay = g_fyc_tuning[FYC_TUNE_PHASE_DELAY] > 0 ? g_fyc_tuning[FYC_TUNE_PHASE_DELAY] : 0;
   q.res_acc = (WIDE && EPI == FYC_EPI_LINEAR && p.residual != nullptr && p.ln_stats == nullptr && !(q.splitk > 1)) ? 1 : 0;
 #ifdef FYC_TRACE
   q.trace = g_fyc_trace;
 #endif
-  q.strip = (q.tiles_n > 4 && g_fyc_tuning[4] >= 0) ? (g_fyc_tuning[4] > 0 ? g_fyc_tuning[4] : (q.tiles_n >= 16 ? 8 : 4)) : 0;   // measured: profiles/r01_gemm_strip_order.txt
+  q.strip = (q.tiles_n > 4 && g_fyc_tuning[FYC_TUNE_GEMM_STRIP] >= 0) ? (g_fyc_tuning[FYC_TUNE_GEMM_STRIP] > 0 ? g_fyc_tuning[FYC_TUNE_GEMM_STRIP] : (q.tiles_n >= 16 ? 8 : 4)) : 0;   // measured: profiles/r01_gemm_strip_order.txt
   // persistent grid: as many blocks as stay resident (LDS-limited), each walks a strided tile list
   int occ = (160 * 1024) / smem;
   const int wave_cap = 32 / (WGM * WGN);

@@ -51,7 +51,7 @@ int fyc_device_caps(int64_t* caps);
  * not part of the product library): key 8 = 1: no s_setprio around the MFMA phases of the ping-pong loop; key 9 = 2: the ping-pong loop (tile
  * configs 21 / 22 / 23) wherever it is built, 3: the overlapped-epilogue kernel (config 31).  In the product library key 9 is ignored and a
  * request for one of those tile configs runs its one-phase twin (5 / 6 / 7 / 6): the one-phase loop always;
- * key 10 = v > 0: split-K for M <= 4096 keeps at least v K tiles per slice (default 16), starts at K >= 128 v (default 2048) and at N >= 128 (default 256);
+ * key 10 = v > 0: split-K for M <= 4096 keeps at least v K tiles per slice and starts at K >= 128 v and N >= 128 (default, key 10 = 0: 10 K tiles per slice, K >= 2048, N >= 256);
  * key 11 = v > 0: every other GEMM block of an XCD starts v x 1024 cycles late (phase shift between the CUs' epilogues, A/B);
  * key 12 = 1: the GEMM epilogues load their per-row / per-column inputs themselves instead of finding them pre-staged in LDS (A/B);
  * key 13 = 1: the generic pass 1 of the packed LINEAR epilogue instead of its specialised copies (A/B);

@@ -96,6 +96,36 @@ def test_argument_validation_without_gpu(lib):
     assert lib.fyc_set_tuning(99, 1) != 0
 
 
+_CONFLICT = """
+import ctypes
+from followyourclick_amd import _lib
+lib = _lib.load()
+zero = ctypes.create_string_buffer(4096 + 256)
+assert lib.fyc_init((ctypes.addressof(zero) + 255) & ~255) == 0
+g = _lib.GemmArgs()
+g.M, g.N, g.K, g.lda, g.ldw, g.ldo, g.batch, g.dtype, g.out_scale, g.cs_rows = 512, 5120, 2560, 2560, 2560, 5120, 1, 1, 1.0, 64
+g.a, g.w, g.out, g.chan_parts = 0x10000000, 0x20000000, 0x30000000, 0x40000000
+tr, sl = _lib.i32(0), _lib.i32(0)
+print(lib.fyc_gemm_stat_layout(ctypes.byref(g), ctypes.byref(tr), ctypes.byref(sl)), tr.value, sl.value)
+g.ln_stats, g.ln_colsum = 0x50000000, 0x60000000
+g.workspace, g.workspace_bytes = 0x70000000, 4 * 512 * 5120 * 4
+print(lib.fyc_gemm(ctypes.byref(g), None))
+print(lib.fyc_last_error().decode())
+"""
+
+
+def test_conflict_between_arguments_and_the_announced_layout_is_refused(lib):
+    """chan_parts of M=512 N=5120 K=2560 are announced in the 128-row tiles of the split-K finish kernel; ln_stats cannot join a split, and
+    the unsplit tile is 256 rows high: the call is refused before anything is launched and the message names both (it used to write another
+    layout and return 0).  In a child process: fyc_init() gets a host buffer here, which must not become this process's zero page."""
+    import sys
+    env = dict(os.environ, PYTHONPATH=ROOT, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", _CONFLICT], capture_output=True, text=True, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    layout, rc, msg = r.stdout.strip().splitlines()
+    assert layout == "4 128 2" and int(rc) != 0 and "ln_stats" in msg and "chan_parts" in msg, r.stdout
+
+
 def test_source_digest_identifies_the_kernel_sources():
     """bench.py matches PMC traffic profiles to the running library through this digest (and the binary's sha256)"""
     import json

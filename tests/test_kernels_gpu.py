@@ -1137,11 +1137,12 @@ def test_gemm_split_k(hip, emu, kind, M, N, K, res):
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("kind,M,N,K,cs_rows,res", [("conv", 2048, 1280, 11520, 64, True), ("conv", 2048, 1280, 23040, 64, False), ("gemm", 2048, 1280, 6400, 64, True),
-                                                    ("gemm", 1008, 640, 2560, 48, False), ("conv", 512, 320, 5760, 64, False)])
+                                                    ("gemm", 1008, 640, 2560, 48, False), ("conv", 512, 320, 5760, 64, False), ("gemm", 512, 5120, 2560, 64, False)])
 def test_gemm_split_k_output_statistics(hip, emu, dt, kind, M, N, K, cs_rows, res):
     """round 6: the split-K finish kernel writes the per-(128-row tile, sample slot, channel) sums of the values it stores - the 8x8-level
     convolutions no longer send their consumers to the separate statistics pass - in the layout fyc_gemm_stat_layout announces; bitwise
-    repeatable (ordered adds, no atomics), incl. samples that straddle tiles (48-row samples) and a ragged last tile"""
+    repeatable (ordered adds, no atomics), incl. samples that straddle tiles (48-row samples) and a ragged last tile.  512x5120x2560 is the
+    smallest shape whose unsplit tile (256 rows) is higher than the split one: a layout announced for the wrong one of the two shows here"""
     T = DT[dt]
     w, bias = rnd((N, K), T, 2, 1 / math.sqrt(K)), rnd((N,), torch.float32, 3)
     r = rnd((M, N), T, 4) if res else None

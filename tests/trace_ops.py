@@ -32,7 +32,7 @@ WRITES = dict(
 
 
 def stat_slots(tile_rows: int, cs_rows: int) -> int:
-    """sample slots a row tile can touch (csrc/gemm.hip::stat_slots)"""
+    """sample slots a row tile can touch (csrc/gemm_plan.h::plan_gemm, cs_slots)"""
     if cs_rows % tile_rows == 0:
         return 1
     if tile_rows % cs_rows == 0:

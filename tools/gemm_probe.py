@@ -65,7 +65,7 @@ def run(h, M, N, K, *, epi=0, res=False, ln=False, rowbias=False, stats=False, n
 
 
 def sweep(h):
-    """cold operands + the epilogue features the UNet uses, per tile config: input of gemm.hip::choose"""
+    """cold operands + the epilogue features the UNet uses, per tile config: input of gemm_plan.h::plan_gemm"""
     cases = [
         ("FF1 GEGLU L0 ln", 131072, 2560, 320, dict(epi=1, ln=True)), ("FF1 GEGLU L1 ln", 32768, 5120, 640, dict(epi=1, ln=True)),
         ("FF1 GEGLU L2 ln", 8192, 10240, 1280, dict(epi=1, ln=True)),
