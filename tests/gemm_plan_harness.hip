@@ -11,6 +11,16 @@
 //       for the pointer-free copy of the arguments
 //   I2  row_parts: row_nparts == ceil(N / column-tile width) of the executed tile
 //   I3  fyc_gemm_workspace_bytes > 0 exactly when the call, given that workspace, splits
+//
+// Second mode (tests/test_gemm_cases.py): `gemm_plan_harness <file>` (`-` = stdin) plans the cases of that file instead of the grid, one per
+// line: a name without blanks, then key=value fields (tests/gemm_cases.py::harness_line writes them; an unknown key is an error, exit 4).
+//   scalars:   dtype mode M N K lda ldw ldo ldr ldrb rpb tile batch stride_a stride_w stride_o cs_rows
+//              Hout Wout Hin Win Cin stride pad t3_frames t3_rows
+//   operands:  bias rowbias residual chan = 1 (present) / 0; residual = 2: the residual IS the output (in-place add)
+//   offsets:   out_off rb_off res_off = bytes added to the made-up 256-byte aligned address of that operand
+//   tuning:    tune=<key>:<value>, may repeat; reset after the case
+//   answer:    <name> | <launch, as above> | <executed cfg> <executed rows>x<columns> | <rc> [message]
+// Without an argument the output is the table above, byte for byte.
 #include <stdlib.h>
 
 #include <functional>
@@ -185,9 +195,103 @@ void executed_tile(const Rec& r, int N, int& bm, int& bn) {
     default: bm = 128; bn = 128; break;
   }
 }
+
+// the tile config a recorded launch executes: the !WIDE rewrite of gemm_kernel.h::dispatch_cfg (and the act entries' own folding)
+int executed_cfg(const Rec& r, int N) {
+  const std::string fam = r.fam;
+  if (fam.find("act") != std::string::npos && r.wide) return (r.cfg == 6 || r.cfg == 5) ? 6 : (r.cfg == 1 || r.cfg == 3 || r.cfg == 7) ? 1 : 2;
+  if (!r.wide && r.cfg != 1 && r.cfg != 2) return (N % 128 == 0 || N > 512) ? 1 : 2;
+  return r.cfg;
+}
+
+// ---- second mode: the cases of a file ---------------------------------------------------------------------------------------------
+bool parse_case(const std::string& line, Case& c, std::string& why) {
+  std::vector<std::string> tok;
+  for (size_t i = 0; i < line.size();) {
+    while (i < line.size() && (line[i] == ' ' || line[i] == '\t')) ++i;
+    size_t j = i;
+    while (j < line.size() && line[j] != ' ' && line[j] != '\t') ++j;
+    if (j > i) tok.push_back(line.substr(i, j - i));
+    i = j;
+  }
+  if (tok.empty()) { why = "empty line"; return false; }
+  c = Case();
+  c.name = tok[0];
+  fyc_gemm_args& a = c.a;
+  memset(&a, 0, sizeof(a));
+  a.a = fake(P_A); a.w = fake(P_W); a.out = fake(P_OUT);
+  a.batch = 1; a.out_scale = 1.f; a.epilogue = FYC_EPI_LINEAR; a.conv_stride = 1; a.conv_pad = 1;
+  long long out_off = 0, rb_off = 0, res_off = 0;
+  int res = 0;
+  for (size_t t = 1; t < tok.size(); ++t) {
+    const size_t eq = tok[t].find('=');
+    if (eq == std::string::npos) { why = "field without '=': " + tok[t]; return false; }
+    const std::string k = tok[t].substr(0, eq), vs = tok[t].substr(eq + 1);
+    if (k == "tune") {
+      const size_t colon = vs.find(':');
+      if (colon == std::string::npos) { why = "tune wants <key>:<value>"; return false; }
+      c.tuning.push_back({atoi(vs.substr(0, colon).c_str()), atoi(vs.substr(colon + 1).c_str())});
+      continue;
+    }
+    const long long v = atoll(vs.c_str());
+    if (k == "dtype") a.dtype = (int)v; else if (k == "mode") a.mode = (int)v;
+    else if (k == "M") a.M = (int)v; else if (k == "N") a.N = (int)v; else if (k == "K") a.K = (int)v;
+    else if (k == "lda") a.lda = (int)v; else if (k == "ldw") a.ldw = (int)v; else if (k == "ldo") a.ldo = (int)v;
+    else if (k == "ldr") a.ldr = (int)v; else if (k == "ldrb") a.ldrb = (int)v; else if (k == "rpb") a.rows_per_batch = (int)v;
+    else if (k == "tile") a.tile = (int)v; else if (k == "batch") a.batch = (int)v;
+    else if (k == "stride_a") a.stride_a = v; else if (k == "stride_w") a.stride_w = v; else if (k == "stride_o") a.stride_o = v;
+    else if (k == "cs_rows") a.cs_rows = (int)v;
+    else if (k == "Hout") a.Hout = (int)v; else if (k == "Wout") a.Wout = (int)v; else if (k == "Hin") a.Hin = (int)v; else if (k == "Win") a.Win = (int)v;
+    else if (k == "Cin") a.Cin = (int)v; else if (k == "stride") a.conv_stride = (int)v; else if (k == "pad") a.conv_pad = (int)v;
+    else if (k == "t3_frames") a.t3_frames = (int)v; else if (k == "t3_rows") a.t3_rows = (int)v;
+    else if (k == "bias") a.bias = v ? (const float*)fake(P_BIAS) : nullptr;
+    else if (k == "rowbias") a.rowbias = v ? (const float*)fake(P_RB) : nullptr;
+    else if (k == "chan") a.chan_parts = v ? (float*)fake(P_CP) : nullptr;
+    else if (k == "residual") res = (int)v;
+    else if (k == "out_off") out_off = v; else if (k == "rb_off") rb_off = v; else if (k == "res_off") res_off = v;
+    else { why = "unknown key " + k; return false; }
+  }
+  a.out = (char*)a.out + out_off;
+  if (a.rowbias != nullptr) a.rowbias = (const float*)((const char*)a.rowbias + rb_off);
+  if (res == 2) a.residual = a.out;
+  else if (res == 1) a.residual = (char*)fake(P_RES) + res_off;
+  if (a.mode != FYC_GEMM_CONV3X3) { a.conv_stride = 0; a.conv_pad = 0; }
+  return true;
+}
+
+int run_file(FILE* f) {
+  int bad = 0;
+  char buf[4096];
+  while (fgets(buf, sizeof(buf), f) != nullptr) {
+    std::string line = buf;
+    while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    Case c;
+    std::string why;
+    if (!parse_case(line, c, why)) { fprintf(stderr, "gemm_plan_harness: %s in: %s\n", why.c_str(), line.c_str()); return 4; }
+    fyc_gemm_args& a = c.a;
+    for (auto& kv : c.tuning) fyc_set_tuning(kv.first, kv.second);
+    const long long need = (long long)fyc_gemm_workspace_bytes(&a);
+    if (need > 0) { a.workspace = fake(P_WS); a.workspace_bytes = need; }
+    g_rec = Rec{"-", 0, 0, 0, 0, 0, 0, 0, 0};
+    int rc = fyc_gemm(&a, nullptr);
+    std::string msg = rc != 0 ? fyc_last_error() : "";
+    if (rc == -3 && g_rec.calls == 1 && g_rec.splitk > 1 && msg.find("fyc_gemm split-K finish") == 0) { rc = 0; msg.clear(); }   // (no device: see the head of the file)
+    (void)hipGetLastError();
+    if (msg.size() > 160) msg.resize(160);
+    int bm = 0, bn = 0;
+    if (rc == 0 && g_rec.calls == 1) executed_tile(g_rec, a.N, bm, bn);
+    else ++bad;
+    printf("%s | %s %d %d %d %d %d %d %d | %d %dx%d | %d%s%s\n", c.name.c_str(), g_rec.fam, g_rec.cfg, g_rec.ns, g_rec.wide, g_rec.colc, g_rec.splitk, g_rec.cs_slots,
+           g_rec.batch, executed_cfg(g_rec, a.N), bm, bn, rc, msg.empty() ? "" : " ", msg.c_str());
+    for (auto& kv : c.tuning) fyc_set_tuning(kv.first, 0);
+  }
+  fflush(stdout);
+  return bad ? 1 : 0;
+}
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
   setenv("HIP_VISIBLE_DEVICES", "-1", 1);
   setenv("ROCR_VISIBLE_DEVICES", "-1", 1);
   int ndev = 0;
@@ -199,6 +303,11 @@ int main() {
   void* zero = aligned_alloc(256, 4096);
   memset(zero, 0, 4096);
   if (fyc_init(zero) != 0) return 2;
+  if (argc > 1) {
+    FILE* f = strcmp(argv[1], "-") == 0 ? stdin : fopen(argv[1], "r");
+    if (f == nullptr) { fprintf(stderr, "gemm_plan_harness: cannot read %s\n", argv[1]); return 4; }
+    return run_file(f);
+  }
   int bad = 0;
   for (Case& c : grid()) {
     fyc_gemm_args& a = c.a;

@@ -1,0 +1,98 @@
+"""Which kernel every case of tests/gemm_cases.py launches, proven without a GPU: the cases are written in the line format of
+tests/gemm_plan_harness.hip's second mode (the planner and fyc_gemm linked with recording stubs, as in tests/test_gemm_plan.py) and the
+recorded launch - the tile config after the narrow-epilogue rewrite, ring depth, wide, split or not - must equal the intent the case declares.
+The GPU tests (tests/test_gemm_epilogues_gpu.py) parametrise from the same list, so a case there cannot silently run another kernel than
+its name says: that is what had happened to the 16-bit sweeps of test_gemm_plain / test_gemm_conv, whose arguments are pinned here too."""
+import os
+import subprocess
+
+import pytest
+
+import gemm_cases as G
+from test_kernels_gpu import CONV_TILES, F16_TILES, PLAIN_TILES
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "followyourclick_amd", "csrc")
+MI32_TWINS = (12, 13, 14)        # only built with FYC_GEMM_MI32: they follow FYC_TEST_MI32 on the GPU, not here
+CASES = [c for c in G.CASES if c.tile not in MI32_TWINS]
+
+
+@pytest.fixture(scope="module")
+def recorded(tmp_path_factory):
+    from followyourclick_amd import _build
+    try:
+        hipcc = _build._hipcc()
+    except RuntimeError:
+        pytest.skip("hipcc not available")
+    tmp = tmp_path_factory.mktemp("gemm_cases")
+    exe = tmp / "gemm_plan_harness"
+    cmd = [hipcc, *_build._flags("gemm.hip"), os.path.join(ROOT, "tests", "gemm_plan_harness.hip"), os.path.join(CSRC, "gemm.hip"), os.path.join(CSRC, "api.hip"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    cases = CASES + G.OLD_PLAIN_SWEEP
+    path = tmp / "cases.txt"
+    path.write_text("".join(G.harness_line(c) + "\n" for c in cases))
+    # the program passes made-up pointers: no device may be visible to it (it checks, and hides them itself as well)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, env=env)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0 and len(lines) == len(cases), (r.returncode, r.stderr[-2000:], lines[-3:])
+    out = {}
+    for c, ln in zip(cases, lines):
+        name, launch, executed, rc = ln.split(" | ")
+        assert name == c.name, (name, c.name)
+        fam, cfg, ns, wide, colc, splitk, cs_slots, batch = launch.split()
+        out[c.name] = dict(fam=fam, asked_cfg=int(cfg), cfg=int(executed.split()[0]), ring=int(ns), wide=int(wide), splitk=int(splitk), rc=int(rc.split()[0]), line=ln)
+    return out
+
+
+def table(recorded):
+    """the table of profiles/gemm_epilogue_coverage.txt"""
+    return [f"{c.name:34s} {r['fam']:10s} tile {r['cfg']:2d}  ring {r['ring']:2d}  wide {r['wide']}  splitk {r['splitk']}" for c in CASES for r in [recorded[c.name]]]
+
+
+@pytest.mark.parametrize("case", CASES, ids=G.case_ids(CASES))
+def test_case_launches_what_it_declares(recorded, case):
+    r = recorded[case.name]
+    assert r["rc"] == 0, r["line"]
+    got = (r["cfg"], r["ring"], r["wide"], r["splitk"] > 1)
+    assert got == (case.want_cfg, case.want_ring, case.want_wide, case.want_split), f"(tile, ring, wide, split) {got} recorded: {r['line']}"
+    if case.want_wide and case.tile in (8, 10) and not (case.rowbias and case.rpb % 128 != 0):
+        assert r["cfg"] == case.tile, r["line"]      # (with row-bias groups to stage, the 128-byte twins 6 / 1 run: gemm_cases.py)
+    fam = {"f32": "f32", "bf16": "bf16_", "f16": "f16_"}[case.dt]
+    assert r["fam"].startswith(fam) and r["fam"].endswith({G.PLAIN: ("plain", "f32"), G.CONV: ("conv", "f32"), G.UP2: ("conv", "f32"), G.T3: ("t3",)}[case.mode]), r["line"]
+
+
+@pytest.mark.parametrize("mode,tiles,extra", [(G.PLAIN, PLAIN_TILES, G.EXTRA_PLAIN_RINGS), (G.CONV, CONV_TILES, []), (G.UP2, CONV_TILES, [])])
+def test_every_tile_of_the_sweeps_is_executed_wide(recorded, mode, tiles, extra):
+    """across the wide, unsplit cases of a mode the executed (tile config, ring depth) are exactly the sweep's list (tile 0 being the automatic
+    choice) and the f16 subset's (F16_TILES has (1, 2) and (2, 2), which CONV_TILES leaves out), plus in PLAIN mode the two deeper rings of the 128x64 linears"""
+    executed = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in CASES if c.mode == mode and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
+    want = {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles + F16_TILES if t not in MI32_TWINS} | set(extra)
+    assert executed == want, (sorted(executed - want), sorted(want - executed))
+    bf16 = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in CASES if c.mode == mode and c.dt == "bf16" and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
+    assert {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles if t not in MI32_TWINS} <= bf16
+    for t in (8, 10):      # and the 64-byte K-tile configs by cases that ASKED for them
+        assert any(c.tile == t and recorded[c.name]["cfg"] == t and recorded[c.name]["wide"] == 1 for c in CASES if c.mode == mode), t
+
+
+def test_every_group_and_dtype_has_cases():
+    have = {(c.group, c.dt) for c in CASES}
+    want = {(g, dt) for g in ("plain", "conv", "pixel", "stripes") for dt in ("bf16", "f16", "f32")} | {(g, dt) for g in ("narrow", "alias", "splitk") for dt in ("bf16", "f16")}
+    assert have == want
+
+
+def test_narrow_and_split_cases_are_what_they_say(recorded):
+    for c in G.by_group("narrow"):
+        assert recorded[c.name]["wide"] == 0 and recorded[c.name]["cfg"] in (1, 2), recorded[c.name]["line"]
+    for c in G.by_group("splitk"):
+        assert recorded[c.name]["splitk"] > 1 and recorded[c.name]["wide"] == 1, recorded[c.name]["line"]
+
+
+@pytest.mark.parametrize("case", G.OLD_PLAIN_SWEEP, ids=G.case_ids(G.OLD_PLAIN_SWEEP))
+def test_old_plain_sweep_takes_the_narrow_epilogue(recorded, case):
+    """THE FINDING, pinned: test_gemm_plain's arguments (rows_per_batch = 50: row-bias groups the packed epilogue cannot stage) make every 16-bit case
+    narrow, and the narrow epilogue only exists for configs 1 / 2 - tile 5 is asked for and never runs.  If a planner change turns this sweep into
+    a real one (or hollows out the new one: test_case_launches_what_it_declares), it shows here"""
+    r = recorded[case.name]
+    assert r["rc"] == 0 and r["asked_cfg"] == 5 and r["wide"] == 0 and r["cfg"] in (1, 2) and r["cfg"] == case.want_cfg, r["line"]

@@ -58,6 +58,11 @@ def _dt_tiles(tiles):
     return [("bf16", t) for t in tiles] + [("f32", (0, 0))] + [("f16", t) for t in F16_TILES]
 
 
+# NOT a tile sweep for the 16-bit types, whatever the parameters look like: rows_per_batch = 50 is neither a multiple of the row-tile height nor
+# of 16, so the packed LINEAR epilogue cannot stage the row-bias groups and csrc/gemm_plan.h plans every bf16 / f16 case NARROW (wide = 0) - and the narrow
+# per-lane epilogue only exists for tile configs 1 / 2 (gemm_kernel.h::dispatch_cfg rewrites the rest).  All (tile, ring) pairs below run 128x128 or
+# 128x64 with the per-lane epilogue and a 2-deep ring.  The test stays as the narrow epilogue's check on six shapes; the packed epilogue on the tiles it
+# names is tests/test_gemm_epilogues_gpu.py, and tests/test_gemm_cases.py pins on the CPU what both launch.
 @pytest.mark.parametrize("dt,tile_ring", _dt_tiles(PLAIN_TILES))
 @pytest.mark.parametrize("M,N,K", [(256, 128, 128), (300, 320, 320), (154, 64, 768), (8, 256, 64), (1000, 960, 40), (513, 4, 576)])
 def test_gemm_plain(hip, emu, dt, tile_ring, M, N, K):
@@ -81,6 +86,10 @@ def test_gemm_plain(hip, emu, dt, tile_ring, M, N, K):
     close(o_h, o_e, f"gemm {dt} {M}x{N}x{K} tile/ring={tile_ring}", RTOL[dt])
 
 
+# Six of the nine shapes take the NARROW epilogue on config 1 / 2 in bf16 / f16 for the same reason as test_gemm_plain: the row bias has one group per
+# frame, and Hout * Wout = 120, 1, 1, 45, 9 is no multiple of 16 (or N = 4 is no multiple of 8).  Only the first three shapes - frames of 64, 192 and
+# 64 output rows, all CONV3X3 - keep the wide epilogue and run the forced tile: no CONV3X3_UP2 case and no single-pixel case does.  The wide epilogue of
+# every geometry on every tile is tests/test_gemm_epilogues_gpu.py.
 @pytest.mark.parametrize("dt,tile_ring", _dt_tiles(CONV_TILES))
 @pytest.mark.parametrize("mode,stride,frames,H,W,Cin,Cout", [
     (1, 1, 3, 8, 8, 64, 64), (1, 1, 2, 16, 12, 128, 320), (1, 2, 2, 16, 16, 64, 128), (2, 1, 2, 6, 5, 64, 64),
