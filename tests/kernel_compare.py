@@ -11,7 +11,48 @@ Algorithms, section 3.1: |e| <= gamma_n sum |x_i y_i|), hence
     |got - ref| <= ulp_T(ref) + C_ACC (K + 8) 2^-24 S
 with C_ACC = 1.  Any other summation order (the matrix instructions add 4 / 16 / 32 products at a time, the K slices of split-K are added
 afterwards) has FEWER roundings on the path of a term than the sequential one, so it stays under the same bound.
+
+Softmax attention (fyc_attention, fyc_temporal_attention) gets a bound of the same kind, derived from the kernels' rounding points; the reference is
+plain f64 - scores s_j = scale q.k_j, weights w = softmax(s), o = sum_j w_j v_j - with NO rounding of the weights (softmax_bound_terms below; not
+EmuOps.attention, which rounds P as the kernels do and so hides a kernel that rounds it wrongly).  u = 2^-9 (bf16), 2^-12 (f16), 2^-24 (f32).
+
+Rounding points of the flash kernel (csrc/attention_kernel.h), T the 16-bit storage type:
+  1. Q' = T(f32(q scale log2e)): one f32 product, one rounding to T per element;
+  2. the score in log2 units: an f32 MFMA sum of d products of T values (exact in f32) - d roundings; under MSUB the slot of index d adds
+     (-m) * 1 with m a T number: exact, no rounding of its own;
+  3. s - m (not under MSUB), s - delta when the maximum moves: f32 subtractions; exp2 in f32 (v_exp_f32, 1 ulp);
+  4. p = T(exp2(s - m)): one rounding to T.  p <= 2^6 between moves of the maximum, which changes nothing in relative terms;
+  5. O^T += V^T P^T and l += 1 P^T: f32 MFMA sums over the n_k keys of products of T values, multiplied by alpha = exp2(m_old - m_new) (f32) on a move;
+  6. o / l as o * (1 / l): two f32 roundings; one rounding to T at the store (o_accumulate: prev + o_scale * v in f32 - two roundings - then T).
+Hence the score of key j is off by at most Es_j = (u + (d + 8) 2^-24) scale log2e sum_i |q_i| |k_ji| log2 units (u: point 1; d + 8: points 2, 3), the weight
+the kernel gives key j is w_j (1 + e_j) with |e_j| <= eta_j = expm1(u + ln2 Es_j) (u: point 4) BEFORE normalisation, and as l is the sum of the very same
+rounded p the normalised weights still add up to 1: their error moves the output only along v_j - o,
+    |got - ref| <= ulp_T(ref) + sum_j w_j eta_j |v_j - o| / (1 - sum_j w_j eta_j) + (n_k + 8) 2^-24 sum_j w_j |v_j|        (points 5, 6).
+The code divides by sum_j w_j exp(-a_j), a_j = u + ln2 Es_j, the exact lower end of sum_j w_j (1 + e_j): it is never below 1 - sum_j w_j eta_j, so the bound
+is never wider than the line above, and it stays positive where a common score offset of +-120 log2 units makes sum_j w_j eta_j approach 1 in bf16.
+o_accumulate: the last two terms times |o_scale|, plus 2 2^-24 (|prev| + |o_scale o|) for the f32 multiply-add, and ulp_T of the accumulated result.
+
+16-bit temporal kernel (csrc/temporal_attn.hip): q and k enter the MFMA as stored (no Q' rounding: Es_j = (d + 8) 2^-24 scale log2e sum_i |q_i| |k_ji|, the 8
+covering (s - max) * scale log2e in f32 and exp2); the weights are normalised in f32 BEFORE they are rounded to T (p_j * (1 / sum)), so their sum is no
+longer 1 and the middle term acts on |v_j| instead of |v_j - o|; P V is an f32 MFMA sum over F frames: (F + 8) 2^-24 sum_j w_j |v_j|.
+Here the rounding of P is charged r = 2 u = 2^-8 (bf16), 2^-11 (f16), the unit roundoff of the type: eta_j = expm1(r + ln2 Es_j).  Half a unit in the last
+place is u of a number just below a power of two but 2 u of one just above.  In the flash form u is kept: its single roundings sit beside an Es_j that is an
+ABSOLUTE sum over d products and several times larger (the model of tests/attention_cases.py stays below 0.98 of that bound, the ulp_T term included).  A
+temporal row of two frames has nothing beside it - one weight near 0.47, rounded down by nearly 2 u, carries the whole error - and correct arithmetic (the
+same model) left a bound with u there, at 1.15 x for F = 2 and at 1.02 x for F = 17: the derivation had charged a single rounding half of what it can be.
+RoPE: kernel and reference both evaluate x cos -/+ x' sin in f32 and round once to T, but the kernel may contract the sum into an FMA, so a rotated element
+may land on the neighbouring T number: Es_j gains scale log2e sum_i (ulp_T(q'_i) |k'_ji| + |q'_i| ulp_T(k'_ji) + ulp_T(q'_i) ulp_T(k'_ji)), q', k' the
+reference's rotated, rounded values.
+
+f32 temporal kernel (one thread per query frame, fmaf chains): the same form with u = 2^-24: Es_j = (d + 8) u scale log2e sum_i |q_i| |k_ji|; expf is assumed
+good to 4 ulp on an argument that itself carries 2 u |s_j - max| from the scale product and the subtraction, eta_j = expm1(4 u + 2 u |s_j - max| + ln2 Es_j);
+nothing is rounded to a 16-bit type, the weights are normalised before use (middle term on |v_j|), P V is a chain of F fmaf: (F + 8) u sum_j w_j |v_j|.
+RoPE in f32: three roundings per rotated element on either side, contracted or not: Es_j gains the term above with 3 u (|x cos| + |x' sin|) in place of ulp_T.
+
+The constant in front of these terms is 1, like C_ACC.  A CPU model of the rounding points (tests/attention_cases.py) stays below the bound on every case
+(tests/test_attention_cases.py); what the MI355X measured is in profiles/attention_bound_coverage.txt.
 """
+import math
 from collections import namedtuple
 
 import torch
@@ -43,7 +84,38 @@ def element_bound(ref, dtype, bound_terms):
     return ulp(ref, dtype) + C_ACC * (bound_terms.K + 8) * 2.0 ** -24 * bound_terms.S.double()
 
 
+U = {"bf16": 2.0 ** -9, "f16": 2.0 ** -12, "f32": 2.0 ** -24}      # the u of the softmax bounds (module docstring)
+R = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11, "f32": 2.0 ** -24}      # the unit roundoff r: what the rounding of P is charged in the temporal form
+LOG2E, LN2 = 1.4426950408889634, math.log(2.0)
+# row / column labels of an attention output for compare()'s messages: rows are (batch, query) or (clip, frame, pixel), columns (head, channel)
+Labels = namedtuple("Labels", ["row", "col"])
+
+
+def softmax_bound_terms(q, k, v, *, scale, dtype, kind, dq=None, dk=None):
+    """One (batch, head), or a few with leading dimensions: q [n_q][d], k [n_k][d], v [n_k][d] as f64 -> (o, rest, w): the f64 reference output [n_q][d], the bound WITHOUT its ulp_T(ref)
+    term (the caller rounds o into its buffer and adds the ulp of what it stored) and the reference weights [n_q][n_k].  kind: "flash" or "temporal"
+    (16-bit or f32 by dtype); dq, dk: per-element uncertainty of the rotated q and k (RoPE), same shapes.  The middle term is O(n_q n_k d): call per head."""
+    assert q.dtype == k.dtype == v.dtype == torch.float64 and kind in ("flash", "temporal")
+    d, n_k, u, f32 = q.shape[-1], k.shape[-2], U[dtype], 2.0 ** -24
+    r = u if kind == "flash" else R[dtype]      # what one rounding to T is charged (module docstring)
+    kt = k.transpose(-1, -2)
+    s = (q @ kt) * scale
+    w = torch.softmax(s, dim=-1)
+    o = w @ v
+    Es = ((r if kind == "flash" else 0.0) + (d + 8) * f32) * scale * LOG2E * (q.abs() @ kt.abs())
+    if dq is not None:
+        Es = Es + scale * LOG2E * (dq.abs() @ kt.abs() + q.abs() @ dk.abs().transpose(-1, -2) + dq.abs() @ dk.abs().transpose(-1, -2))
+    arg = r + LN2 * Es if dtype != "f32" else 4 * u + 2 * u * (s - s.max(dim=-1, keepdim=True).values).abs() + LN2 * Es
+    we = w * torch.expm1(arg)
+    dev = (v[..., None, :, :] - o[..., :, None, :]).abs() if kind == "flash" else v.abs()[..., None, :, :]
+    den = (w * torch.exp(-arg)).sum(dim=-1, keepdim=True)      # sum_j w_j (1 + e_j) >= sum_j w_j exp(-a_j) (>= 1 - sum_j w_j eta_j, and never 0)
+    rest = (we[..., None] * dev).sum(dim=-2) / den + (n_k + 8) * f32 * (w @ v.abs())
+    return o, rest, w
+
+
 def _where(i, j, tile, prefix=""):
+    if isinstance(tile, Labels):
+        return f"{prefix}row {i} ({tile.row(i)}), column {j} ({tile.col(j)})"
     bm, bn = tile
     return (f"{prefix}row {i}, column {j} (row tile {i // bm} of {bm} rows, row {i % bm} in it; column tile {j // bn} of {bn} columns, column {j % bn} in it; "
             f"16-row pass {i % bm // 16}, lane column {j % 16})")
@@ -54,14 +126,23 @@ def _bits(t):
     return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
-def compare(got, ref, *, dtype, bound_terms, guard=None, tag):
-    """got, ref: [rows][columns], the kernel's output window and the reference from EmuOps(acc=torch.float64), both in the storage type `dtype`
+def compare(got, ref, *, dtype, bound_terms=None, guard=None, tag, bound=None, rtol=None, labels=None):
+    """With `bound` ([rows][columns] f64, a precomputed per-element bound: the softmax bounds of the module docstring), `rtol` (the global tolerance to
+    assert) and `labels` (a Labels): (a), (b), (d), (e) below.  (c) is skipped: a single attention row whose arithmetic is right can sit at several times
+    the project's global tolerance (one rounding of a dominant probability moves the whole row), which is exactly why the bound is per element.
+
+    got, ref: [rows][columns], the kernel's output window and the reference from EmuOps(acc=torch.float64), both in the storage type `dtype`
     ("bf16" / "f16" / "f32").  Asserts, in this order: (a) finite everywhere, (b) global relative L2 <= RTOL[dtype], (c) relative L2 of every row and
     of every column <= RTOL[dtype] (rows / columns whose reference norm is below the norm of their per-element bounds are left to (d)),
     (d) every element within element_bound(), (e) everything outside guard.mask bit-identical.  No element is exempt from (d)."""
     g, r = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert g.dim() == 2 and g.shape == r.shape == tuple(bound_terms.S.shape), (tag, g.shape, r.shape, tuple(bound_terms.S.shape))
-    tile, rtol = bound_terms.tile, RTOL[dtype]
+    if bound is not None:
+        assert bound_terms is None and rtol is not None and labels is not None
+        assert g.dim() == 2 and g.shape == r.shape == tuple(bound.shape), (tag, g.shape, r.shape, tuple(bound.shape))
+        tile, form = labels, "its precomputed bound"
+    else:
+        assert g.dim() == 2 and g.shape == r.shape == tuple(bound_terms.S.shape), (tag, g.shape, r.shape, tuple(bound_terms.S.shape))
+        tile, rtol, form = bound_terms.tile, RTOL[dtype], f"ulp + {C_ACC:g} (K + 8) 2^-24 S"
     fig = last_figures
     fig.clear()
     fig.update(tag=tag, dtype=dtype)
@@ -69,7 +150,7 @@ def compare(got, ref, *, dtype, bound_terms, guard=None, tag):
     nonfin = (~torch.isfinite(g)).nonzero()
     assert nonfin.numel() == 0, f"{tag}: {nonfin.shape[0]} non-finite values, first at {_where(*nonfin[0].tolist(), tile)}"
     diff = g - r
-    bound = element_bound(r, dtype, bound_terms)
+    bound = element_bound(r, dtype, bound_terms) if bound is None else bound.detach().cpu().double()
     ratio = diff.abs() / bound
     worst = int(ratio.argmax())
     wi, wj = divmod(worst, g.shape[1])
@@ -78,7 +159,7 @@ def compare(got, ref, *, dtype, bound_terms, guard=None, tag):
     fig.update(global_rel=rel, elem_ratio=ratio.max().item())
     assert rel <= rtol, f"{tag}: global rel-L2 {rel:.3e} > {rtol:.1e}; worst element {ratio.max().item():.3g} x its bound at {_where(wi, wj, tile)}"
     # (c)
-    for axis, what in ((1, "row"), (0, "column")):
+    for axis, what in ((1, "row"), (0, "column")) if bound_terms is not None else ():
         rn, dn, bnorm = r.norm(dim=axis), diff.norm(dim=axis), bound.norm(dim=axis)
         judged = rn > bnorm
         rel_ax = torch.where(judged, dn / rn.clamp_min(1e-300), torch.zeros_like(dn))
@@ -95,7 +176,7 @@ def compare(got, ref, *, dtype, bound_terms, guard=None, tag):
     over = (diff.abs() > bound).nonzero()
     if over.numel():
         i, j = over[0].tolist()
-        raise AssertionError(f"{tag}: {over.shape[0]} of {g.numel()} elements outside |got - ref| <= ulp + {C_ACC:g} (K + 8) 2^-24 S; first: got {g[i, j].item():.8g}, "
+        raise AssertionError(f"{tag}: {over.shape[0]} of {g.numel()} elements outside |got - ref| <= {form}; first: got {g[i, j].item():.8g}, "
                              f"ref {r[i, j].item():.8g}, |diff| {abs(diff[i, j].item()):.3e} = {ratio[i, j].item():.3g} x bound {bound[i, j].item():.3e} at {_where(i, j, tile)}; "
                              f"worst {ratio.max().item():.3g} x at {_where(wi, wj, tile)}")
     # (e)
