@@ -51,6 +51,36 @@ RoPE in f32: three roundings per rotated element on either side, contracted or n
 
 The constant in front of these terms is 1, like C_ACC.  A CPU model of the rounding points (tests/attention_cases.py) stays below the bound on every case
 (tests/test_attention_cases.py); what the MI355X measured is in profiles/attention_bound_coverage.txt.
+
+Normalisation kernels (csrc/norm.hip, csrc/chan_parts.h).  The bounds are computed in tests/norm_cases.py beside the f64 references and handed to compare() as `bound`;
+u = 2^-24 throughout (all arithmetic is f32, whatever the storage type T), the constant is 1, ulp_T(ref) is added for the store (for T = f32 the kernel does not round again
+there, but the reference does when it is stored: half of that unit is the reference's own, the other half is slack).
+  Statistics (fyc_gn_stats), per {sum, sum sq} entry, the two judged separately:  |s - s_ref| <= L u sum |x|,  |q - q_ref| <= (L + 1) u sum x^2.  L is the longest chain of f32
+    additions a term passes through: the rows one thread walks (the 4-row tree has fewer roundings on a term's path than the row-by-row tail) + rpi row lanes + the channels of a
+    group.  The + 1 is the rounding of the square and is charged for T = f32 only: the square of a bf16 / f16 number is exact in f32.  The f64 additions of the chunk partials
+    cost 2^-53 each.  Integer-valued inputs in [-3, 3] keep every f32 partial an integer below 2^24: the result must be the f64 sum bit for bit.
+  fyc_gn_apply: m = s / n, var = q / n - m^2 in f64 (4 2^-53 (q / n + m^2)), then mean_f = (float)m: dm = u |m| + ds / n;  dvar = dq / n + 2 |m| ds / n (zero from exact
+    statistics); rstd = rsqrtf((float)var + eps) has the relative error rho = (dvar + u var + u (var + eps)) / (2 (var + eps)) + 2 u - the conversion, the addition, and rsqrtf at
+    the 1 ulp (= up to 2 u) of the HIP math API's accuracy table.  o = (x - mean) * rstd * g + b is charged FOUR f32 roundings, one more than the three of a fused form: the
+    library is built with -ffp-contract=off (followyourclick_amd/_build.py), so * g + b is a product and a sum (the CPU model runs that order, and the fused one as well):
+        |o - o_ref| <= |g| rstd dm + |(x - m) rstd g| (rho + 3 u) + u |o|.
+  fyc_gn_apply_cs: sc = rstd g (rho + u), mean_f sc (dm |sc|, the error of sc, and its own rounding: the u |mean sc| term), sf = beta - mean sc (u |sf|), one fused multiply-add:
+        |o - o_ref| <= |x sc| (rho + u) + dm |sc| + |m sc| (rho + u) + u |m sc| + u |sf| + u |o|;
+    the f64 fold of the channel sums (reduced sums or row-tile partials, 8 lanes and 3 shuffles) is charged n 2^-53 sum |terms|.  With mean / std = 64 the terms |x sc| and
+    |m sc| are 64 times the output: that, not the f64 subtraction, is where an ill-conditioned GroupNorm loses its digits.
+  SiLU: silu_f(o) = o / (1 + __expf(-o)), __expf = exp2(-o log2e).  E = exp(-o) carries the relative error u |o| of the rounded product (u |o| log2e in log2 units), 0.25 u |o| of
+    log2e as an f32 constant (it is off by 0.22 u), 2 u of the instruction (1 ulp); through d silu / dE = -o / (1 + E)^2, plus the addition and the division (u |silu| each) and
+    |silu'(o)| times the error of o.
+  fyc_layernorm / fyc_row_stats (16 lanes per row, two passes): a lane adds its 8 need values in a chain and 4 shuffles follow, L = 8 need + 4; mean = s / C:
+    dm = L u sum |x| / C + u |m|.  q = sum fl(fl(x - mean_f)^2): the common shift dm adds dm^2 per element (sum (x - m) = 0 removes the cross term), each difference and each
+    square one rounding, the sum its chain: dvar = dm^2 + (L + 3) u sum (|x - m| + dm)^2 / C + u var; rho and the four roundings of the output as for fyc_gn_apply, one more
+    for the positional row.  row_stats: |mean - m| <= dm and |rstd - rstd_ref| <= rstd rho, each plus the f32 ulp of the stored reference, judged separately.
+  fyc_softmax_rows: the maximum is exact; x - max is one rounding (u |x - max| on the exponent), expf the 1 ulp (2 u) OCML documents: eta_j = u |x_j - max| + 2 u; the sum is a
+    chain of `laps` terms per thread, 6 shuffles and 3 additions; one reciprocal, one product:  |p_j - ref_j| <= p_j (eta_j + sum_k p_k eta_k + (laps + 11) u) + ulp_T(ref_j).
+    Masked (causal) columns must be exact zeros.
+  fyc_chan_stats_reduce and the fold of fyc_gn_apply_cs: f64 sums of f32 values, n 2^-53 sum |terms|; with integer-valued partials exact.
+A torch model of these rounding points (tests/norm_cases.py: f32 tensors combined in the kernel's order) stays inside every bound (tests/test_norm_cases.py); what the MI355X
+measured is in profiles/norm_bound_coverage.txt.
 """
 import math
 from collections import namedtuple
