@@ -64,7 +64,9 @@ def _hipcc() -> str:
 
 def _digest(path: str) -> str:
     h = hashlib.sha256()
-    for dep in [path, os.path.join(CSRC, "fyc_common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "attention_kernel.h"), os.path.join(CSRC, "attention_groups.h"), os.path.join(CSRC, "chan_parts.h"), os.path.join(HERE, "..", "include", "fyc.h")]:
+    # every header below csrc/, not a hand-kept list: one that is missing from a list leaves stale objects behind
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    for dep in [path, *headers, os.path.join(HERE, "..", "include", "fyc.h")]:
         with open(dep, "rb") as f:
             h.update(f.read())
     h.update(" ".join(_flags(os.path.basename(path))).encode())

@@ -20,7 +20,7 @@
 //     consecutive k (lane / 32) of it per operand register, and of a 32-feature result block the features 8 b + 4 (lane / 32) + e;
 //   * the weights arrive as one pre-packed stream (engine/weights.py::pack_ff_block): half-stages of 32 KiB, every 1-KiB piece
 //     already the A operand of one MFMA in lane order (lane l holds W[32 j + l % 32][16 s + 8 (l / 32) .. +8]), so a half is a run
-//     of global -> LDS DMAs (global_load_lds, 16 B / lane, lane-linear image = conflict-free ds_read_b128 at base + lane * 16)
+//     of global -> LDS DMAs (row_panel.h::dma16x4, 16 B / lane, lane-linear image = conflict-free ds_read_b128 at base + lane * 16)
 //     into a 4-deep ring: half h + 2 is requested while half h computes;
 //   * per chunk of 32 hidden units a wave runs 40 MFMAs of FF1 (value block, gate block; K = C from registers), the GEGLU gate on
 //     its 32 x 32 results - which ARE the B operand of FF2 as they stand (the k-slots of the W2' fragments are packed in the
@@ -32,10 +32,9 @@
 //
 // Built for the level where it pays (C = 320, hidden 1280, bf16, rows % 128 == 0); other shapes keep the unfused schedule.
 // Compiled WITHOUT -amdgpu-mfma-vgpr-form and with -fno-slp-vectorize (see _build.py).
-#include <mutex>
 #include <type_traits>
 
-#include "fyc_common.h"
+#include "row_panel.h"
 
 namespace {
 
@@ -43,7 +42,7 @@ constexpr int C_ = 320, HID = 1280, ROWS = 128, NW = 4, NT = 64 * NW;
 constexpr int KS = C_ / 16;                    // 20 MFMA k-steps (of 16) over C
 constexpr int NB = C_ / 32;                    // 10 feature blocks (of 32) of the output
 constexpr int CHUNKS = HID / 32;               // 40 hidden chunks of 32 units
-constexpr int PIECE = 1024;                    // one MFMA A operand for all 64 lanes: a 32 x 16 weight block
+using rp::PIECE;                               // one MFMA A operand for all 64 lanes: a 32 x 16 weight block
 // The weight stream is cut into HALF-STAGES of HP = 32 pieces (32 KiB) that go through a 4-deep LDS ring: the pieces of half
 // h + 2 are requested while half h computes, i.e. a whole stage-time before they are needed.
 //   half t < 10           k-steps 2 t, 2 t + 1 of the projection: pieces 10 s' + j (s' < 2, j < 10) = Wp rows 32 j .. +32, columns 16 (2 t + s') .. +16
@@ -69,7 +68,7 @@ static_assert(TILE_BYTES % PIECE == 0 && TILE_BYTES <= ((NHALF - 2) % NSLOT) * H
 static_assert(TILE_BYTES + SCR_BYTES <= LDS_BYTES, "epilogue tile + statistics scratch overlay the ring");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using rp::f32x16;
 
 struct FFP {
   const bf16_t* x; const bf16_t* res; bf16_t* out;
@@ -80,52 +79,17 @@ struct FFP {
   float eps;
 };
 
-// Four consecutive pieces (4 KiB of the stream -> 4 KiB of the ring) by one wave, issued from inline asm: ONE M0 write, the
-// instruction's immediate offset moves the global and the LDS address together.  NOT the builtin: while a builtin LDS-DMA is
-// outstanding hipcc turns every counted lgkmcnt wait of the fragment reads into lgkmcnt(0) (it models the DMA as a FLAT access
-// that may touch LDS), so each k-step paid the full LDS round trip.  The compiler does not count these loads: the barriers of
-// this kernel carry their own s_waitcnt vmcnt.  M0 is saved and restored inside the statement (as in panel_linear.hip and
-// temporal_block_rr.hip): it is compiler-reserved, and an "m0" clobber is only a warning, so a statement must leave it as it found it.
-__device__ __forceinline__ void dma16x4(const char* gbase, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %1, %2\n\t"
-               "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-               "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-               "global_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(gbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma16v(const void* gsrc, unsigned lds_dst) {                        // one piece, per-lane source address
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma_landed_barrier() {       // all of this wave's DMA pieces have landed, then the workgroup meets
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
+// LDS-DMA, MFMA, fragment read and lane-half sum: row_panel.h, with the rules they follow
+using rp::dma16x4; using rp::dma16v; using rp::dma_landed_barrier; using rp::mfma; using rp::frag;
 __device__ __forceinline__ void half_landed_barrier() {      // all but this wave's newest half (4 GPW loads) have landed, then the workgroup meets
   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * GPW) : "memory");
   __syncthreads();
 }
-
-// sum over the two lane halves of a wave (every lane gets it): gfx950's v_permlane32_swap, plain VALU.  NOT __shfl_xor: that is
-// ds_bpermute_b32, an LDS-queue instruction, and hipcc (which cannot see the asm DMAs above) waits for it with a COUNTED lgkmcnt
-// between the fragment reads of the projection stages it sinks this code into - with LDS-DMA writes in flight the result was
-// consumed early in ~12 % of the row blocks (row statistics off by ~1e-3: tools/ff_stress.py found the kernel's output changing
-// from launch to launch; profiles/r03_ff_block_race.txt).  -DFF_BPERMUTE rebuilds that form.
-__device__ __forceinline__ float halves_sum(float v) {
-#ifdef FF_BPERMUTE
-  return v + __shfl_xor(v, 32);
+#ifdef FF_BPERMUTE                                              // the racing form of row_panel.h::halves_sum (profiles/r03_ff_block_race.txt)
+__device__ __forceinline__ float halves_sum(float v) { return v + __shfl_xor(v, 32); }
 #else
-  return swap32_sum(v);          // (fyc_common.h: the two results of the swap must stay opaque to hipcc)
+using rp::halves_sum;
 #endif
-}
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-template <typename Frag> __device__ __forceinline__ Frag frag(const char* sl, int piece) { return *reinterpret_cast<const Frag*>(sl + piece * PIECE); }
 
 #ifdef FF_TIMING                                                // phase timestamps of wave 0 of every workgroup (tools/ff_probe.py prints them)
 __device__ unsigned long long g_ff_time[1024 * 16];
@@ -429,19 +393,6 @@ __global__ void __launch_bounds__(NT) ff_block_kernel(const FFP p) {
 
 }  // namespace
 
-// LDS per CU and CU count of this process's device (one GPU per process), queried once; 0 when no device answers
-static void device_limits(int64_t& lds_cap, int64_t& n_cu) {
-  static std::mutex mu;
-  static int64_t cap = -1, cus = 0;
-  std::lock_guard<std::mutex> lk(mu);
-  if (cap < 0) {
-    int64_t caps[8];
-    if (fyc_device_caps(caps) == 0) { cap = caps[1]; cus = caps[0]; } else { cap = 0; cus = 0; }
-  }
-  lds_cap = cap;
-  n_cu = cus;
-}
-
 #ifdef FF_TIMING
 extern "C" int fyc_ff_timing(unsigned long long* host_out, int n) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_ff_time), sizeof(unsigned long long) * n);
@@ -453,10 +404,7 @@ extern "C" int64_t fyc_ff_block_wstream_bytes(void) { return (int64_t)NHALF * HA
 extern "C" int fyc_ff_block_supported(const fyc_ff_block_args* a) {
   if (a == nullptr || (a->dtype != FYC_BF16 && a->dtype != FYC_F16) || a->C != C_ || a->hidden != HID || a->rows <= 0 || a->rows % ROWS != 0) return 0;
   if (a->chan_parts != nullptr && (a->cs_rows <= 0 || a->cs_rows % ROWS != 0 || a->rows % a->cs_rows != 0)) return 0;
-  int64_t lds_cap = 0, n_cu = 0;
-  device_limits(lds_cap, n_cu);
-  if (lds_cap > 0 && lds_cap < LDS_BYTES) return 0;   // a device / partition mode with less LDS: the caller keeps the unfused schedule
-  return 1;
+  return rp::lds_fits(LDS_BYTES) ? 1 : 0;
 }
 
 extern "C" int fyc_ff_block(const fyc_ff_block_args* a, void* stream) {
@@ -464,25 +412,12 @@ extern "C" int fyc_ff_block(const fyc_ff_block_args* a, void* stream) {
   FYC_REQUIRE(fyc_ff_block_supported(a), "fyc_ff_block: built for bf16 / f16, C=320, hidden=1280, rows %% 128 == 0, cs_rows %% 128 == 0 and >= %d B of LDS (got C=%d hidden=%d rows=%d cs_rows=%d)",
               LDS_BYTES, a->C, a->hidden, a->rows, a->cs_rows);
   FYC_REQUIRE(a->x != a->out, "fyc_ff_block: out must not alias x");
-  FYC_REQUIRE(((uintptr_t)a->x % 16) == 0 && ((uintptr_t)a->out % 16) == 0 && ((uintptr_t)a->wstream % 16) == 0 && ((uintptr_t)a->b_out % 16) == 0 &&
-              ((uintptr_t)a->residual % 16) == 0 && ((uintptr_t)a->chan_parts % 16) == 0, "fyc_ff_block: operands must be 16-byte aligned");
+  FYC_REQUIRE(rp::aligned16(a->x, a->out, a->wstream, a->b_out, a->residual, a->chan_parts), "fyc_ff_block: operands must be 16-byte aligned");
   FFP p;
   p.x = (const bf16_t*)a->x; p.res = (const bf16_t*)a->residual; p.out = (bf16_t*)a->out; p.ws = (const char*)a->wstream;
   p.b_out = a->b_out; p.parts = a->chan_parts; p.eps = a->eps; p.ntiles = a->rows / ROWS;
-  {  // dynamic LDS above 64 KB needs the function attribute once per device; one process may drive several GPUs from several threads
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_done[kMaxDev] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev < 0 || dev >= kMaxDev || !attr_done[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ff_block_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(ff_block_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e != hipSuccess) FYC_FAIL(-3, "fyc_ff_block: %d bytes of dynamic LDS refused: %s", LDS_BYTES, hipGetErrorString(e));
-      if (dev >= 0 && dev < kMaxDev) attr_done[dev] = true;
-    }
-  }
+  static rp::LdsAttr attr;
+  if (int rc = attr.set("fyc_ff_block", LDS_BYTES, ff_block_kernel<bf16_t>, ff_block_kernel<f16_t>)) return rc;
   if (a->dtype == FYC_F16) hipLaunchKernelGGL(ff_block_kernel<f16_t>, dim3((unsigned)p.ntiles), dim3(NT), LDS_BYTES, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(ff_block_kernel<bf16_t>, dim3((unsigned)p.ntiles), dim3(NT), LDS_BYTES, (hipStream_t)stream, p);
   FYC_CHECK_LAUNCH("fyc_ff_block");

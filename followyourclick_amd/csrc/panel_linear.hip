@@ -17,16 +17,14 @@
 //   * per 320-column pass: residual tile by DMA into LDS beside the ring, bias + residual + accumulators in f32, one rounding
 //     to bf16, rows leave as 16-byte stores over whole 640-byte segments.
 // Built for bf16, rows % 128 == 0, (K, N) in {320, 640}^2; other shapes keep fyc_gemm.  AGPR accumulators (see _build.py).
-#include <mutex>
-
 #include "chan_parts.h"
-#include "fyc_common.h"
+#include "row_panel.h"
 
 namespace {
 
 constexpr int ROWS = 128, NT = 256, PN = 320;     // rows per workgroup, threads, columns per pass
 constexpr int NB = PN / 16;                        // 20 column blocks per pass
-constexpr int PIECE = 1024;
+using rp::PIECE;
 constexpr int NPIECE = 2 * NB;                     // 40 pieces per stage: 2 k-steps x 20 column blocks
 constexpr int STAGE_BYTES = NPIECE * PIECE;        // 40960
 constexpr int RING_BYTES = 2 * STAGE_BYTES;        // 81920
@@ -46,24 +44,8 @@ struct PLP {
   int N;
 };
 
-// 1 KiB global -> LDS by DMA from inline asm (see ff_block.hip: the builtin form degrades every lgkmcnt wait to lgkmcnt(0))
-__device__ __forceinline__ void dma16(const char* gbase, unsigned voff, unsigned lds_dst) {          // wave-uniform base + 32-bit lane offset
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(gbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma16v(const void* gsrc, unsigned lds_dst) {                        // per-lane source address
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma_landed_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-template <typename Frag> __device__ __forceinline__ Frag frag(const char* sl, int piece) { return *reinterpret_cast<const Frag*>(sl + piece * PIECE); }
+// LDS-DMA, MFMA and fragment read: row_panel.h, with the rules they follow
+using rp::dma16; using rp::dma16v; using rp::dma_landed_barrier; using rp::mfma; using rp::frag;
 
 // KS = K / 32 MFMA k-steps (10 or 20); NPASS = N / 320 column passes (1 or 2), unrolled: the accumulators of a pass are dead
 // before the next one starts, and a runtime loop around this much unrolled code made the register allocator spill (ff_block.hip)
@@ -215,19 +197,8 @@ __global__ void __launch_bounds__(NT) panel_linear_kernel(const PLP p) {
 template <typename T, int KS, int NPASS>
 int launch(const PLP& p, int rows, hipStream_t st) {
   auto kern = panel_linear_kernel<T, KS, NPASS>;
-  {
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_done[kMaxDev] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev < 0 || dev >= kMaxDev || !attr_done[dev]) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e != hipSuccess) FYC_FAIL(-3, "fyc_panel_linear: %d bytes of dynamic LDS refused: %s", LDS_BYTES, hipGetErrorString(e));
-      if (dev >= 0 && dev < kMaxDev) attr_done[dev] = true;
-    }
-  }
+  static rp::LdsAttr attr;                          // one per instantiation
+  if (int rc = attr.set("fyc_panel_linear", LDS_BYTES, kern)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(rows / ROWS)), dim3(NT), LDS_BYTES, st, p);
   FYC_CHECK_LAUNCH("fyc_panel_linear");
   return 0;
@@ -247,16 +218,7 @@ extern "C" int fyc_panel_linear_supported(const fyc_panel_linear_args* a) {
   if (a->gn_parts != nullptr && (a->gn_tile_rows <= 0 || a->gn_slots < 1 || a->gn_slots > 4 || a->gn_stat_samples <= 0 || a->gn_rows_per_sample % a->gn_stat_samples != 0)) return 0;
   if ((a->gn_cs != nullptr || a->gn_parts != nullptr) && (a->gn_rows_per_sample <= 0 || a->gn_rows_per_sample % ROWS != 0 || a->rows % a->gn_rows_per_sample != 0 ||
                               a->gn_groups <= 0 || a->K % a->gn_groups != 0 || a->gn_stat_samples <= 0)) return 0;
-  static std::mutex mu;
-  static int64_t lds_cap = -1;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (lds_cap < 0) {
-      int64_t caps[8];
-      lds_cap = (fyc_device_caps(caps) == 0) ? caps[1] : 0;
-    }
-  }
-  return (lds_cap > 0 && lds_cap < LDS_BYTES) ? 0 : 1;
+  return rp::lds_fits(LDS_BYTES) ? 1 : 0;
 }
 
 extern "C" int fyc_panel_linear(const fyc_panel_linear_args* a, void* stream) {
@@ -265,8 +227,7 @@ extern "C" int fyc_panel_linear(const fyc_panel_linear_args* a, void* stream) {
               a->rows, a->K, a->N, a->gn_rows_per_sample);
   FYC_REQUIRE((a->gn_cs == nullptr && a->gn_parts == nullptr) || (a->gn_gamma != nullptr && a->gn_beta != nullptr), "fyc_panel_linear: gn_cs / gn_parts need gn_gamma / gn_beta");
   FYC_REQUIRE(a->x != a->out && a->residual != a->x, "fyc_panel_linear: out must not alias x (residual may alias out)");
-  FYC_REQUIRE(((uintptr_t)a->x % 16) == 0 && ((uintptr_t)a->out % 16) == 0 && ((uintptr_t)a->wstream % 16) == 0 && ((uintptr_t)a->bias % 16) == 0 &&
-              ((uintptr_t)a->residual % 16) == 0 && ((uintptr_t)a->gn_cs % 16) == 0 && ((uintptr_t)a->gn_parts % 8) == 0, "fyc_panel_linear: operands must be 16-byte aligned");
+  FYC_REQUIRE(rp::aligned16(a->x, a->out, a->wstream, a->bias, a->residual, a->gn_cs) && ((uintptr_t)a->gn_parts % 8) == 0, "fyc_panel_linear: operands must be 16-byte aligned");
   PLP p;
   p.x = (const bf16_t*)a->x; p.res = (const bf16_t*)a->residual; p.out = (bf16_t*)a->out; p.ws = (const char*)a->wstream; p.bias = a->bias;
   p.gn_cs = a->gn_cs; p.gn_gamma = a->gn_gamma; p.gn_beta = a->gn_beta; p.gn_rows_per_sample = a->gn_rows_per_sample;

@@ -16,7 +16,7 @@
 // frame before the score product - x'[c] = x[c] cos[f][c mod h] -/+ x[c +/- h] sin[f][c mod h], h = d/2, the
 // rotate_half pairing of the reference's RoPE (rope.py:102-116) - in f32 on the loaded values and rounded
 // once to the operand type.  V is untouched.  The ROPE = false instantiations are the kernels without it.
-#include "fyc_common.h"
+#include "row_panel.h"
 
 namespace {
 
@@ -27,10 +27,6 @@ struct TAttnP {
   const char* zero;
   const float* rope_cos; const float* rope_sin;
 };
-
-template <typename T> struct TMma;
-template <> struct TMma<bf16_t> { __device__ static __forceinline__ f32x4 k32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); } };
-template <> struct TMma<f16_t> { __device__ static __forceinline__ f32x4 k32(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); } };
 
 // rotate_half on the 8 head channels dd .. dd+7 of one frame's q or k row (`row` = the head's first channel of that row).  h = d/2 is
 // a multiple of 4, so each 4-channel run of the fragment lies wholly below or above h and its partner run starts h channels away: at
@@ -175,7 +171,7 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
     for (int kt = 0; kt < NFT; ++kt) {
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) a = TMma<T>::k32(kf[kt][ks], qf[LAZY ? 0 : qt][ks], a);
+      for (int ks = 0; ks < KS; ++ks) a = rp::mfma(kf[kt][ks], qf[LAZY ? 0 : qt][ks], a);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (kt * 16 + 4 * g + r >= F) a[r] = -INFINITY;
@@ -215,8 +211,8 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int pp = 0; pp < NP; ++pp) {
-        if constexpr (LAZY) acc = TMma<T>::k32(vfrag<T, DP, NFT>(vt, pp, t, g, r16), pf[pp], acc);
-        else acc = TMma<T>::k32(vf[pp][t], pf[pp], acc);
+        if constexpr (LAZY) acc = rp::mfma(vfrag<T, DP, NFT>(vt, pp, t, g, r16), pf[pp], acc);
+        else acc = rp::mfma(vf[pp][t], pf[pp], acc);
       }
       const int dd = t * 16 + 4 * g;
       if (fq < F && dd < p.d) {

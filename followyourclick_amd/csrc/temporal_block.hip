@@ -13,9 +13,7 @@
 // per-frame bias pe_f W^T.  Row order inside the tile: row = pixel * 16 + frame, so a 16-row MFMA block is one pixel.
 //
 // Built for the level where it pays (C = 320, 8 heads of 40, 16 frames, bf16); other shapes keep the unfused schedule.
-#include <mutex>
-
-#include "fyc_common.h"
+#include "row_panel.h"
 
 namespace {
 
@@ -40,10 +38,6 @@ constexpr int X_BYTES = ROWS * XP, W_BYTES = 2 * 128 * WP, Q_BYTES = ROWS * QP, 
 constexpr int LDS_BYTES = X_BYTES + W_BYTES + Q_BYTES + S_BYTES;
 static_assert(C_ * OP <= W_BYTES, "the w_out slice of a head reuses the w_qkv K-tile buffers");
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-
-template <typename T> struct BMma;
-template <> struct BMma<bf16_t> { __device__ static __forceinline__ f32x4 k32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); } };
-template <> struct BMma<f16_t> { __device__ static __forceinline__ f32x4 k32(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); } };
 
 // T: the 16-bit element type of x / out / the weights (bf16_t or f16_t; TBlockP's pointers are typed bf16_t for both: same arithmetic)
 template <typename T>
@@ -145,7 +139,7 @@ __global__ void __launch_bounds__(512) temporal_block_kernel(const TBlockP p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) qacc[i][j] = BMma<T>::k32(bf[j], af[i], qacc[i][j]);
+          for (int j = 0; j < 2; ++j) qacc[i][j] = rp::mfma(bf[j], af[i], qacc[i][j]);
       }
       if (kt + 1 < KT) {
         wstore((kt + 1) & 1, wreg[kt + 1]);
@@ -211,8 +205,8 @@ __global__ void __launch_bounds__(512) temporal_block_kernel(const TBlockP p) {
         vf[t] = __builtin_bit_cast(Frag, pk);
       }
       f32x4 s = {0.f, 0.f, 0.f, 0.f};                        // S^T: key frame 4g + r, query frame r16
-      s = BMma<T>::k32(kf[0], qf[0], s);
-      s = BMma<T>::k32(kf[1], qf[1], s);
+      s = rp::mfma(kf[0], qf[0], s);
+      s = rp::mfma(kf[1], qf[1], s);
       float mx = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -229,7 +223,7 @@ __global__ void __launch_bounds__(512) temporal_block_kernel(const TBlockP p) {
       // this wave's reads of its 16 rows (q, k, v above) are complete: the MFMAs that consumed them have been issued in order.
       f32x4 o[3];
 #pragma unroll
-      for (int t = 0; t < 3; ++t) o[t] = BMma<T>::k32(vf[t], pf, (f32x4){0.f, 0.f, 0.f, 0.f});
+      for (int t = 0; t < 3; ++t) o[t] = rp::mfma(vf[t], pf, (f32x4){0.f, 0.f, 0.f, 0.f});
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
@@ -256,7 +250,7 @@ __global__ void __launch_bounds__(512) temporal_block_kernel(const TBlockP p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 5; ++j) oacc[i][j] = BMma<T>::k32(bf[j], af[i], oacc[i][j]);
+        for (int j = 0; j < 5; ++j) oacc[i][j] = rp::mfma(bf[j], af[i], oacc[i][j]);
     }
     // (the barrier at the top of the next head orders these reads before sW / sQ are overwritten)
   }
@@ -291,16 +285,7 @@ __global__ void __launch_bounds__(512) temporal_block_kernel(const TBlockP p) {
 extern "C" int fyc_temporal_block_supported(const fyc_temporal_block_args* a) {
   if (!(a != nullptr && (a->dtype == FYC_BF16 || a->dtype == FYC_F16) && a->C == C_ && a->heads == H_ && a->d == D_ && a->frames == F_ && a->pixels > 0 &&
         a->pixels % PIX == 0 && a->clips > 0)) return 0;
-  static std::mutex mu;                            // LDS per CU of this process's device, queried once (0: no device answered)
-  static int64_t lds_cap = -1;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (lds_cap < 0) {
-      int64_t caps[8];
-      lds_cap = (fyc_device_caps(caps) == 0) ? caps[1] : 0;
-    }
-  }
-  return (lds_cap > 0 && lds_cap < LDS_BYTES) ? 0 : 1;   // less LDS than the 153 KB tile needs: the engine keeps the unfused schedule
+  return rp::lds_fits(LDS_BYTES) ? 1 : 0;                // less LDS than the 153 KB tile needs: the engine keeps the unfused schedule
 }
 
 extern "C" int64_t fyc_temporal_block_wstream_bytes(void) { return fyc_temporal_block_rr_wstream_bytes(); }
@@ -315,20 +300,8 @@ extern "C" int fyc_temporal_block(const fyc_temporal_block_args* a, void* stream
   p.x = (const bf16_t*)a->x; p.out = (bf16_t*)a->out; p.w_qkv = (const bf16_t*)a->w_qkv; p.colsum = a->colsum; p.bias = a->bias;
   p.pe_bias = a->pe_bias; p.w_out = (const bf16_t*)a->w_out; p.b_out = a->b_out; p.clips = a->clips; p.pixels = a->pixels;
   p.scale_log2e = a->scale * 1.44269504088896340736f; p.eps = a->eps;
-  {  // dynamic LDS above 64 KB needs the function attribute once per device; one process may drive several GPUs from several threads
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_done[kMaxDev] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev < 0 || dev >= kMaxDev || !attr_done[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(temporal_block_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(temporal_block_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e != hipSuccess) FYC_FAIL(-3, "fyc_temporal_block: %d bytes of dynamic LDS refused: %s", LDS_BYTES, hipGetErrorString(e));
-      if (dev >= 0 && dev < kMaxDev) attr_done[dev] = true;      // only after success: a failed call is retried
-    }
-  }
+  static rp::LdsAttr attr;
+  if (int rc = attr.set("fyc_temporal_block", LDS_BYTES, temporal_block_kernel<bf16_t>, temporal_block_kernel<f16_t>)) return rc;
   if (a->dtype == FYC_F16) hipLaunchKernelGGL(temporal_block_kernel<f16_t>, dim3((unsigned)(a->clips * (a->pixels / PIX))), dim3(512), LDS_BYTES, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(temporal_block_kernel<bf16_t>, dim3((unsigned)(a->clips * (a->pixels / PIX))), dim3(512), LDS_BYTES, (hipStream_t)stream, p);
   FYC_CHECK_LAUNCH("fyc_temporal_block");

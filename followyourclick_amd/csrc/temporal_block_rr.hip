@@ -15,7 +15,7 @@
 //     the same for q and k, whose product only needs it to be consistent): slot 8 g + e of k-step 0 = feature 4 g + e of block 0
 //     (e < 4) / of block 1 (e >= 4); of k-step 1 = block 2 (e < 4) / zero.  No shuffle, no LDS round trip;
 //   * the weights arrive as one pre-packed stream (engine/weights.py::pack_temporal_block): per head two stages of 1-KiB MFMA
-//     fragments by asm-issued global_load_lds into a 2-deep LDS ring, dealt out between the MFMAs of the previous stage:
+//     fragments by asm-issued LDS-DMA (row_panel.h::dma16) into a 2-deep LDS ring, dealt out between the MFMAs of the previous stage:
 //       stage A: Wq', Wk' fragments (60) + the f32 bias table [frame][q 48 | k 48] (bias + positional encoding, 6 pieces)
 //       stage B: Wv' fragments (30) + Wo' fragments of the head (40) + the f32 v bias table [48][frame] (3 pieces)
 //   * epilogue: residual tile by DMA into the idle ring (row pitch padded against bank conflicts), + bias + accumulators, one
@@ -23,17 +23,16 @@
 //
 // Built for C = 320, 8 heads of 40, 16 frames, bf16 (the 64x64 level of the 512^2 workload: 10 launches per UNet call).
 // Compiled WITHOUT -amdgpu-mfma-vgpr-form (see _build.py): the accumulators must live in AGPRs for the 512-register budget.
-#include <mutex>
 #include <type_traits>
 
-#include "fyc_common.h"
+#include "row_panel.h"
 
 namespace {
 
 constexpr int C_ = 320, H_ = 8, D_ = 40, F_ = 16, PIX = 8, ROWS = PIX * F_, NT = 256;
 constexpr int KS = C_ / 32;                    // 10 MFMA k-steps over C
 constexpr int NB = C_ / 16;                    // 20 column blocks of the output
-constexpr int PIECE = 1024;
+using rp::PIECE;
 constexpr int A_TAB = 60, A_PIECES = 66;       // stage A: pieces s * 6 + b (b < 3 q blocks, b >= 3 k blocks), table at 60
 constexpr int B_WO = 30, B_TAB = 70, B_PIECES = 73;   // stage B: pieces s * 3 + b (v blocks), 30 + t * 20 + j (Wo'), table at 70
 constexpr int STAGE_BYTES = B_PIECES * PIECE;  // 74752 (stage A is padded to the same stride in the stream)
@@ -56,33 +55,13 @@ struct TRP {
   float scale_log2e, eps;
 };
 
-// 1 KiB global -> LDS by DMA from inline asm (see ff_block.hip::dma16 for why not the builtin)
-__device__ __forceinline__ void dma16(const char* gbase, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(gbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma16v(const void* gsrc, unsigned lds_dst) {                        // per-lane source address
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma_landed_barrier() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
+// LDS-DMA, MFMA, fragment read and the row reductions: row_panel.h, with the rules they follow
+using rp::dma16; using rp::dma16v; using rp::dma_landed_barrier; using rp::frag; using rp::rows_sum; using rp::rows_max;
 #ifdef TB_NO_MFMA                                              // ablation build: DMA + LDS reads + barriers only, wrong results
 template <typename Frag> __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 c) { c[0] += __builtin_bit_cast(f32x4, a)[0] + __builtin_bit_cast(f32x4, b)[0]; return c; }
 #else
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+using rp::mfma;
 #endif
-template <typename Frag> __device__ __forceinline__ Frag frag(const char* sl, int piece) { return *reinterpret_cast<const Frag*>(sl + piece * PIECE); }
-
-// reductions over the four 16-lane rows of a wave by v_permlane16_swap / v_permlane32_swap: plain VALU.  No LDS-queue instruction
-// (ds_bpermute = __shfl_xor) may sit between asm-issued DMAs: profiles/r03_ff_block_race.txt
-__device__ __forceinline__ float rows_sum(float v) { return swap32_sum(swap16_sum(v)); }   // (fyc_common.h: opaque swap results, as for the maxima)
-__device__ __forceinline__ float rows_max(float v) { return swap32_max(swap16_max(v)); }   // (fyc_common.h: the plain fmaxf form is miscompiled)
 template <typename T> __device__ __forceinline__ typename Pair16<T>::Vec8 op8(const f32x4& a, const f32x4& b) {          // two 4-row results -> one 8-slot operand
   return __builtin_bit_cast(typename Pair16<T>::Vec8, (u32x4){Pair16<T>::pack(a[0], a[1]), Pair16<T>::pack(a[2], a[3]), Pair16<T>::pack(b[0], b[1]), Pair16<T>::pack(b[2], b[3])});
 }
@@ -373,25 +352,12 @@ int64_t fyc_temporal_block_rr_lds_bytes() { return LDS_BYTES; }
 
 // called by fyc_temporal_block (temporal_block.hip) after its argument checks when a->wstream is set
 int fyc_temporal_block_rr_launch(const fyc_temporal_block_args* a, void* stream) {
-  FYC_REQUIRE(((uintptr_t)a->x % 16) == 0 && ((uintptr_t)a->out % 16) == 0 && ((uintptr_t)a->wstream % 16) == 0 && ((uintptr_t)a->b_out % 16) == 0,
-              "fyc_temporal_block: operands must be 16-byte aligned");
+  FYC_REQUIRE(rp::aligned16(a->x, a->out, a->wstream, a->b_out), "fyc_temporal_block: operands must be 16-byte aligned");
   TRP p;
   p.x = (const bf16_t*)a->x; p.out = (bf16_t*)a->out; p.ws = (const char*)a->wstream; p.b_out = a->b_out; p.pixels = a->pixels;
   p.scale_log2e = a->scale * 1.44269504088896340736f; p.eps = a->eps;
-  {
-    constexpr int kMaxDev = 64;
-    static std::mutex mu;
-    static bool attr_done[kMaxDev] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev < 0 || dev >= kMaxDev || !attr_done[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tblock_rr_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(tblock_rr_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      if (e != hipSuccess) FYC_FAIL(-3, "fyc_temporal_block: %d bytes of dynamic LDS refused: %s", LDS_BYTES, hipGetErrorString(e));
-      if (dev >= 0 && dev < kMaxDev) attr_done[dev] = true;
-    }
-  }
+  static rp::LdsAttr attr;
+  if (int rc = attr.set("fyc_temporal_block", LDS_BYTES, tblock_rr_kernel<bf16_t>, tblock_rr_kernel<f16_t>)) return rc;
   if (a->dtype == FYC_F16) hipLaunchKernelGGL(tblock_rr_kernel<f16_t>, dim3((unsigned)(a->clips * (a->pixels / PIX))), dim3(NT), LDS_BYTES, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(tblock_rr_kernel<bf16_t>, dim3((unsigned)(a->clips * (a->pixels / PIX))), dim3(NT), LDS_BYTES, (hipStream_t)stream, p);
   FYC_CHECK_LAUNCH("fyc_temporal_block (register-resident)");

@@ -137,3 +137,31 @@ def test_source_digest_identifies_the_kernel_sources():
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
     stamped = [json.load(open(os.path.join(prof, f))).get("source_sha256") for f in sorted(os.listdir(prof)) if f.endswith("_hbm_traffic.json")]
     assert any(stamped), "no traffic profile carries a source digest"
+
+
+def test_object_digest_covers_every_header(tmp_path, monkeypatch):
+    """_build._digest decides whether an object file is stale.  It hashes every csrc/*.h (it used to hash a hand-kept list, and a header
+    missing from it left stale objects behind): on a copy of csrc/, one byte appended to any header changes the digest of a source that
+    includes it, and touching nothing leaves the digest as it was."""
+    import shutil
+    from followyourclick_amd import _build
+    csrc = tmp_path / "csrc"
+    shutil.copytree(_build.CSRC, csrc)
+    monkeypatch.setattr(_build, "CSRC", str(csrc))
+    names = sorted(os.listdir(csrc))
+    headers = [f for f in names if f.endswith(".h")]
+    assert "row_panel.h" in headers and len(headers) >= 7
+    includes = {f: set(re.findall(r'#include "(\w+\.h)"', (csrc / f).read_text())) for f in names}
+
+    def reaches(f, h, seen=()):
+        return h in includes[f] or any(reaches(g, h, seen + (f,)) for g in includes[f] if g in includes and g not in seen)
+
+    for h in headers:
+        users = [f for f in names if f.endswith(".hip") and reaches(f, h)]
+        assert users, f"no source includes {h}"
+        src = str(csrc / users[0])
+        before = _build._digest(src)
+        assert _build._digest(src) == before
+        with open(csrc / h, "ab") as fh:
+            fh.write(b"\n")
+        assert _build._digest(src) != before, f"{h} is not part of the digest of {users[0]}"
