@@ -23,7 +23,9 @@ extern "C" int fyc_attention(const fyc_attn_args* a, void* stream) {
   // QT = 4 needs 170 VGPRs (2 waves / SIMD), QT = 3 needs 140 (3 waves / SIMD).  Large problems take QT = 3 (measured,
   // profiles/r02_attention_variants.txt); small ones QT = 2 so that the grid still fills the chip.  tuning key 3 forces QT.
   const long long wg3 = (long long)a->batch * a->heads * ((a->n_q + 191) / 192);
-  int qt = (a->n_q >= 1024 && wg3 >= 512 && a->d <= 48) ? 3 : 2;      // larger head dims: 3 tiles no longer fit 2 waves / SIMD
+  // d = 64 (the SD-2.1 head layout) was measured on its own: QT = 3 takes 0.81 - 0.85 of QT = 2's time at n_q >= 2304 and is level with it at 1024
+  // (profiles/sd21_forward.txt); the other head dims above 48 keep QT = 2 (3 tiles no longer fit 2 waves / SIMD, and nothing says otherwise)
+  int qt = (a->n_q >= 1024 && wg3 >= 512 && (a->d <= 48 || a->d == 64)) ? 3 : 2;
   if (g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] >= 2 && g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] <= 4 && (a->d <= 80 || g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] == 2)) qt = g_fyc_tuning[FYC_TUNE_ATTN_VARIANT];
   if (a->dtype == FYC_F16) {
     if (a->d <= 48) return fyca::run_small<f16_t>(p, qt, st);

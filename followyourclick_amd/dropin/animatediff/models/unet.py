@@ -79,15 +79,24 @@ class UNet3DConditionModel(nn.Module):
         mm = dict(motion_module_kwargs or {})
         unsupported = {
             "center_input_sample": center_input_sample, "dual_cross_attention": dual_cross_attention,
-            "use_linear_projection": use_linear_projection, "class_embed_type": class_embed_type, "num_class_embeds": num_class_embeds,
+            "class_embed_type": class_embed_type, "num_class_embeds": num_class_embeds,
             "unet_use_cross_frame_attention": unet_use_cross_frame_attention, "unet_use_temporal_attention": unet_use_temporal_attention,
             "use_pseudo_conv3d": use_pseudo_conv3d,
             "use_text_encoder_2": use_text_encoder_2, "motion_module_decoder_only": motion_module_decoder_only,
             "add_temporal_lora": mm.get("add_temporal_lora", False),
         }
-        # the per-frame GroupNorm / temporal-conv checkpoint families (training configs only, none of the shipped inference YAMLs) are implemented
-        # but stay refused unless FYC_UNET_VARIANTS=1: a script that names them by accident keeps failing loudly
-        variants = [k for k, v in (("use_inflated_groupnorm", use_inflated_groupnorm), ("use_temporal_conv", use_temporal_conv)) if v]
+        # the per-frame GroupNorm / temporal-conv checkpoint families and the SD-2.1 base they are trained on (Linear proj_in / proj_out, one
+        # head count per level) - training configs only, none of the shipped inference YAMLs - are implemented but stay refused unless
+        # FYC_UNET_VARIANTS=1: a script that names them by accident keeps failing loudly
+        if not isinstance(attention_head_dim, int):
+            attention_head_dim = tuple(int(h) for h in attention_head_dim)
+            if len(attention_head_dim) != len(block_out_channels):
+                raise ValueError(f"attention_head_dim has {len(attention_head_dim)} entries for {len(block_out_channels)} blocks")
+        # a list of equal entries is an int (reference unet.py:190-191 expands an int to exactly that list)
+        head = attention_head_dim if isinstance(attention_head_dim, int) or len(set(attention_head_dim)) > 1 else attention_head_dim[0]
+        variants = [k for k, v in (("use_inflated_groupnorm", use_inflated_groupnorm), ("use_temporal_conv", use_temporal_conv),
+                                   ("use_linear_projection", use_linear_projection),
+                                   (f"attention_head_dim={list(attention_head_dim) if not isinstance(head, int) else head}", not isinstance(head, int))) if v]
         if variants and os.environ.get("FYC_UNET_VARIANTS", "0") == "0":
             raise NotImplementedError(f"UNet3DConditionModel on the MI355X engine: options {variants} are outside the shipped inference configs and off by "
                                       "default; set FYC_UNET_VARIANTS=1 to build these model families (INTEGRATION.md)")
@@ -102,11 +111,11 @@ class UNet3DConditionModel(nn.Module):
         blocks = mm.get("attention_block_types", ("Temporal_Self", "Temporal_Self"))
         if any(b != "Temporal_Self" for b in blocks) or mm.get("temporal_attention_dim_div", 1) != 1:
             raise NotImplementedError("motion module: only Temporal_Self attention blocks with dim_div 1")
-        head = attention_head_dim if isinstance(attention_head_dim, int) else attention_head_dim[0]
+        # upcast_attention is recorded in `.config` and changes nothing: every attention path forms and soft-maxes its scores in f32
         self.engine_config = UNet3DConfig(
             sample_size=sample_size or 64, in_channels=in_channels, out_channels=out_channels,
             block_out_channels=tuple(block_out_channels), layers_per_block=layers_per_block, cross_attention_dim=cross_attention_dim,
-            attention_head_dim=head, norm_num_groups=norm_num_groups, norm_eps=norm_eps, down_block_types=tuple(down_block_types),
+            attention_head_dim=head, use_linear_projection=bool(use_linear_projection), norm_num_groups=norm_num_groups, norm_eps=norm_eps, down_block_types=tuple(down_block_types),
             up_block_types=tuple(up_block_types), use_motion_module=bool(use_motion_module),
             motion_module_resolutions=tuple(motion_module_resolutions), motion_module_mid_block=bool(motion_module_mid_block),
             motion_num_attention_heads=mm.get("num_attention_heads", 8), motion_num_transformer_block=mm.get("num_transformer_block", 2),
@@ -284,8 +293,9 @@ class UNet3DConditionModel(nn.Module):
 
     @classmethod
     def from_pretrained_2d(cls, pretrained_model_path, subfolder=None, unet_additional_kwargs=None):
-        """2-D SD-1.5 UNet weights -> 3-D model (reference unet.py:674-726): reads config.json +
-        diffusion_pytorch_model.bin, zero-extends conv_in to the concat-conditioning channel count."""
+        """2-D SD-1.5 / SD-2.1 UNet weights -> 3-D model (reference unet.py:674-726): reads config.json +
+        diffusion_pytorch_model.bin, zero-extends conv_in to the concat-conditioning channel count.  An SD-2.1 config.json
+        (attention_head_dim as a list, use_linear_projection, upcast_attention) is taken as it is."""
         if subfolder is not None:
             pretrained_model_path = os.path.join(pretrained_model_path, subfolder)
         config_file = os.path.join(pretrained_model_path, "config.json")

@@ -1,6 +1,6 @@
 """`diffusers.models.UNet2DConditionModel` on the MI355X engine (first-image synthesis of scripts/inference.py:194-204).
 
-The 2-D SD-1.5 UNet is the spatial half of the 3-D model: same resnets, spatial transformers, up/down-samplers and
+The 2-D SD-1.5 / SD-2.1 UNet is the spatial half of the 3-D model: same resnets, spatial transformers, up/down-samplers and
 state-dict names, no motion modules, no fps/flow embeddings, 4 input channels.  It therefore runs on the same engine as a
 one-frame clip (per-image GroupNorm == cross-frame GroupNorm with F = 1).  Call surface: reference
 diffusers/models/unet_2d_condition.py:92-123 (constructor), :337-345 (forward).
@@ -44,8 +44,9 @@ class UNet2DConditionModel(UNet3DConditionModel):
             down3, up3, mid3 = [_TO_3D[b] for b in down_block_types], [_TO_3D[b] for b in up_block_types], _TO_3D[mid_block_type]
         except KeyError as e:
             raise NotImplementedError(f"UNet2DConditionModel on the MI355X engine: block type {e} is not implemented") from None
-        if only_cross_attention or upcast_attention or downsample_padding != 1 or mid_block_scale_factor != 1:
-            raise NotImplementedError("only_cross_attention / upcast_attention / non-default downsample_padding, mid_block_scale_factor")
+        # upcast_attention (SD-2.1) is accepted and changes nothing: the attention kernels form and soft-max their scores in f32 anyway
+        if only_cross_attention or downsample_padding != 1 or mid_block_scale_factor != 1:
+            raise NotImplementedError("only_cross_attention / non-default downsample_padding, mid_block_scale_factor")
         kw3 = dict(cfg2d, down_block_types=tuple(down3), up_block_types=tuple(up3), mid_block_type=mid3)
         super().__init__(**kw3, use_motion_module=False, compute_dtype=compute_dtype)
         for k, v in cfg2d.items():          # `.config` and attributes show the 2-D constructor arguments

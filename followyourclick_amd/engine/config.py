@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Tuple
+from typing import Tuple, Union
 
 
 @dataclass
@@ -15,7 +15,12 @@ class UNet3DConfig:
     block_out_channels: Tuple[int, ...] = (320, 640, 1280, 1280)
     layers_per_block: int = 2
     cross_attention_dim: int = 768
-    attention_head_dim: int = 8            # = number of heads (reference unet_blocks.py:437-440)
+    # = number of heads (reference unet_blocks.py:437-440); a tuple holds one count per down block (SD-2.1: (5, 10, 20, 20)): entry i in down
+    # block i, the last entry in the mid block, the reversed tuple in the up blocks (reference unet.py:190-191, 212, 250, 282, 312)
+    attention_head_dim: Union[int, Tuple[int, ...]] = 8
+    # proj_in / proj_out of the spatial transformers are Linear (C, C) instead of 1x1 Conv2d (C, C, 1, 1) (reference attention.py:179-182,
+    # 212-215, 270-300): the same arithmetic on token rows, another state-dict shape
+    use_linear_projection: bool = False
     norm_num_groups: int = 32
     norm_eps: float = 1e-5
     down_block_types: Tuple[str, ...] = ("CrossAttnDownBlock3D", "CrossAttnDownBlock3D", "CrossAttnDownBlock3D", "DownBlock3D")
@@ -58,12 +63,40 @@ class UNet3DConfig:
     def time_embed_dim(self) -> int:
         return self.block_out_channels[0] * 4
 
+    def _heads(self) -> Tuple[int, ...]:
+        h, nb = self.attention_head_dim, len(self.block_out_channels)
+        if isinstance(h, int):
+            return (h,) * nb
+        if len(h) != nb:
+            raise ValueError(f"attention_head_dim has {len(h)} entries for {nb} blocks")
+        return tuple(int(v) for v in h)
+
+    def down_heads(self, i: int) -> int:
+        """head count of the transformers of down block i"""
+        return self._heads()[i]
+
+    def mid_heads(self) -> int:
+        return self._heads()[-1]
+
+    def up_heads(self, i: int) -> int:
+        """head count of the transformers of up block i: the reversed list"""
+        return self._heads()[::-1][i]
+
     def validate(self) -> None:
+        nb = len(self.block_out_channels)
         for c in self.block_out_channels:
             if c % 64:
                 raise ValueError(f"block_out_channels must be multiples of 64 (got {c}): K tiles of the MFMA GEMM are 64 bf16")
-            if c % self.attention_head_dim or (c // self.attention_head_dim) % 8:
-                raise ValueError(f"head dim {c}/{self.attention_head_dim} must be a multiple of 8")
+        # every (width, heads) pair a transformer can have: down block i, the mid block, up block i (width reversed with the heads)
+        rev = self.block_out_channels[::-1]
+        pairs = ([(self.block_out_channels[i], self.down_heads(i), self.down_block_types[i].startswith("CrossAttn")) for i in range(nb)]
+                 + [(self.block_out_channels[-1], self.mid_heads(), True)]
+                 + [(rev[i], self.up_heads(i), self.up_block_types[i].startswith("CrossAttn")) for i in range(nb)])
+        for c, h, attends in pairs:
+            if h < 1 or c % h or (c // h) % 8:
+                raise ValueError(f"head dim {c}/{h} must be a multiple of 8")
+            if attends and c // h > 160:
+                raise ValueError(f"head dim {c}/{h} = {c // h} exceeds 160, the widest the attention kernels are built for")
         if self.use_rope_position_encoding and (self.rope_video_length < 2 or self.rope_train_video_length < 1):
             raise ValueError("rope_video_length must be >= 2 and rope_train_video_length >= 1 (the query factor is ln(train) / ln(video))")
         if self.cross_attention_dim % 8:

@@ -67,7 +67,9 @@ class _S(OrderedDict):
 
     def transformer(self, p, c, cfg: UNet3DConfig):
         self.norm(p + ".norm", c)
-        self.conv(p + ".proj_in", c, c, 1)
+        # use_linear_projection: Linear (C, C) on the token rows instead of a 1x1 Conv2d (reference attention.py:179-182, 212-215)
+        proj = self.lin if cfg.use_linear_projection else (lambda q, o, i: self.conv(q, o, i, 1))
+        proj(p + ".proj_in", c, c)
         t = p + ".transformer_blocks.0"
         self.attn(t + ".attn1", c, c)
         self.norm(t + ".norm1", c)
@@ -75,7 +77,7 @@ class _S(OrderedDict):
         self.norm(t + ".norm2", c)
         self.ff(t + ".ff", c)
         self.norm(t + ".norm3", c)
-        self.conv(p + ".proj_out", c, c, 1)
+        proj(p + ".proj_out", c, c)
 
     def motion(self, p, c, cfg: UNet3DConfig):
         p += ".temporal_transformer"

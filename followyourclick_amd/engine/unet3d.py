@@ -81,7 +81,6 @@ class UNet3DEngine(EngineBase):
         self.dtype = packed.dtype
         self.ops = ops if ops is not None else ops_mod.get()
         self.device = packed.conv_in_w.device
-        self.heads = self.cfg.attention_head_dim
         self.groups = self.cfg.norm_num_groups
         self.mat_attn = self.dtype == torch.float32  # f32 parity mode: materialised attention through the GEMM (bf16 / f16: fyc_attention)
         self.transformers: List[Packed] = []
@@ -134,7 +133,6 @@ class UNet3DEngine(EngineBase):
         cross-attention K / V^T of all 16 transformers once (they are constant over steps and frames)."""
         cfg, o = self.cfg, self.ops
         Bn, Nk, D = ctx.shape
-        H = self.heads
 
         def to_T(t: Tensor) -> Tensor:
             t = t.to(device=self.device, dtype=torch.float32).contiguous()
@@ -142,7 +140,7 @@ class UNet3DEngine(EngineBase):
             o.cast_from_f32(t, y, rows=t.shape[0] * t.shape[1], cols=D, ld=D)
             return y
 
-        def project(x: Tensor, w: Tensor, n_tok: int, C: int):
+        def project(x: Tensor, w: Tensor, n_tok: int, C: int, H: int):
             d = C // H
             ld = ((n_tok + 7) // 8) * 8
             k = self.new(Bn, H, n_tok, d)
@@ -163,9 +161,9 @@ class UNet3DEngine(EngineBase):
         xi = to_T(ip_tokens) if (cfg.use_ip_cross_attention and ip_tokens is not None) else None
         cache = []
         for t in self.transformers:
-            e = dict(text=project(xt, t.kv2_w, Nk, t.C), n_text=Nk, ip=None)
+            e = dict(text=project(xt, t.kv2_w, Nk, t.C, t.heads), n_text=Nk, ip=None)
             if xi is not None:
-                e["ip"] = project(xi, t.kvip_w, ip_tokens.shape[1], t.C)
+                e["ip"] = project(xi, t.kvip_w, ip_tokens.shape[1], t.C, t.heads)
                 e["n_ip"] = ip_tokens.shape[1]
             cache.append(e)
         self.ctx_cache = cache
@@ -173,8 +171,9 @@ class UNet3DEngine(EngineBase):
     # ---- attention cores -----------------------------------------------------------------------
     def _attend(self, q: Tensor, k: Tensor, vt: Tensor, out: Tensor, *, batch: int, n_q: int, n_k: int, d: int, ldvt: int,
                 C: int, kv_div: int, accumulate: bool = False, o_scale: float = 1.0, q_mod: int = 0) -> None:
-        """q_mod > 0: q holds q_mod batch elements, element b attends with the queries of b % q_mod (shared CFG prefix)"""
-        H, o = self.heads, self.ops
+        """q_mod > 0: q holds q_mod batch elements, element b attends with the queries of b % q_mod (shared CFG prefix).  The head count
+        is the transformer's own: C / d"""
+        H, o = C // d, self.ops
         scale = d ** -0.5
         if not self.mat_attn:
             o.attention(q, k, vt, out, batch=batch, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldvt, scale=scale,
@@ -405,7 +404,7 @@ class UNet3DEngine(EngineBase):
         """Transformer3DModel + BasicTransformerBlock (reference attention.py:217-308, 489-564).
         share = 2: x holds the first 1 / share of the batch `g` describes, the rest being copies of it (the CFG pair).  Everything in
         front of the cross-attention core runs on that part alone; attn2 reads the shared queries for every batch element."""
-        rows_full, C, H, o = g["rows"], t.C, self.heads, self.ops
+        rows_full, C, H, o = g["rows"], t.C, t.heads, self.ops
         BF_full, N = g["B"] * g["F"], g["H"] * g["W"]
         rows, BF = rows_full // share, BF_full // share
         d = C // H

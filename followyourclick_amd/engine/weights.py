@@ -145,11 +145,14 @@ def _ln(sd, p, device):
     return f32(sd[p + ".weight"], device), f32(sd[p + ".bias"], device)
 
 
-def _transformer(sd, p: str, cfg: UNet3DConfig, dtype, device) -> Packed:
+def _transformer(sd, p: str, cfg: UNet3DConfig, dtype, device, heads: int) -> Packed:
+    """proj_in / proj_out arrive as (C, C, 1, 1) convolutions or, with use_linear_projection, as (C, C) Linear weights: pack_linear and
+    _ff flatten either to the same (C, C) operand.  `heads` is this transformer's own head count (UNet3DConfig.down_heads / mid_heads /
+    up_heads)."""
     t = p + ".transformer_blocks.0"
     a1, a2 = t + ".attn1", t + ".attn2"
     d = Packed(
-        C=sd[p + ".proj_in.weight"].shape[0],
+        C=sd[p + ".proj_in.weight"].shape[0], heads=heads,
         norm_g=f32(sd[p + ".norm.weight"], device), norm_b=f32(sd[p + ".norm.bias"], device),
         pin_w=pack_linear(sd[p + ".proj_in.weight"], dtype, device), pin_b=f32(sd[p + ".proj_in.bias"], device),
         ln1=_ln(sd, t + ".norm1", device), ln2=_ln(sd, t + ".norm2", device), ln3=_ln(sd, t + ".norm3", device),
@@ -435,7 +438,7 @@ def pack_unet(sd: Dict[str, Tensor], cfg: UNet3DConfig, dtype, device) -> Packed
         for j in range(cfg.layers_per_block):
             layers.append(Packed(
                 resnet=add_resnet(f"{p}.resnets.{j}"),
-                attn=_transformer(sd, f"{p}.attentions.{j}", cfg, dtype, device) if bt.startswith("CrossAttn") else None,
+                attn=_transformer(sd, f"{p}.attentions.{j}", cfg, dtype, device, cfg.down_heads(i)) if bt.startswith("CrossAttn") else None,
                 motion=_motion(sd, f"{p}.motion_modules.{j}", cfg, dtype, device)
                 if cfg.use_motion_module and (2 ** i) in cfg.motion_module_resolutions else None))
         ds = None
@@ -443,7 +446,7 @@ def pack_unet(sd: Dict[str, Tensor], cfg: UNet3DConfig, dtype, device) -> Packed
             ds = Packed(w=pack_conv3x3(sd[f"{p}.downsamplers.0.conv.weight"], dtype, device), b=f32(sd[f"{p}.downsamplers.0.conv.bias"], device))
         down.append(Packed(layers=layers, down=ds))
     P["down"] = down
-    P["mid"] = Packed(r0=add_resnet("mid_block.resnets.0"), attn=_transformer(sd, "mid_block.attentions.0", cfg, dtype, device),
+    P["mid"] = Packed(r0=add_resnet("mid_block.resnets.0"), attn=_transformer(sd, "mid_block.attentions.0", cfg, dtype, device, cfg.mid_heads()),
                       motion=_motion(sd, "mid_block.motion_modules.0", cfg, dtype, device)
                       if cfg.use_motion_module and cfg.motion_module_mid_block else None,
                       r1=add_resnet("mid_block.resnets.1"))
@@ -454,7 +457,7 @@ def pack_unet(sd: Dict[str, Tensor], cfg: UNet3DConfig, dtype, device) -> Packed
         for j in range(cfg.layers_per_block + 1):
             layers.append(Packed(
                 resnet=add_resnet(f"{p}.resnets.{j}"),
-                attn=_transformer(sd, f"{p}.attentions.{j}", cfg, dtype, device) if bt.startswith("CrossAttn") else None,
+                attn=_transformer(sd, f"{p}.attentions.{j}", cfg, dtype, device, cfg.up_heads(i)) if bt.startswith("CrossAttn") else None,
                 motion=_motion(sd, f"{p}.motion_modules.{j}", cfg, dtype, device)
                 if cfg.use_motion_module and (2 ** (nb - 1 - i)) in cfg.motion_module_resolutions else None))
         us = None
