@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 EXTRA = os.environ.get("FYC_BUILD_EXTRA", "").split()
 LIB = os.path.abspath(os.environ.get("FYC_BUILD_LIB") or os.path.join(HERE, "libfyc_hip.so"))
 OBJ = os.path.join(HERE, "_obj") if not (EXTRA or os.environ.get("FYC_BUILD_LIB")) else LIB + ".obj"
-SOURCES = ["api.hip", "gemm.hip", "gemm_bf16_plain.hip", "gemm_bf16_conv.hip", "gemm_bf16_act.hip", "gemm_f16_plain.hip", "gemm_f16_conv.hip", "gemm_f16_act.hip", "gemm_f32.hip", "gemm_bf16_t3.hip", "gemm_f16_t3.hip", "gemm_f32_t3.hip", "attention.hip", "attention_small.hip", "attention_medium.hip", "attention_large.hip", "attention_small_f16.hip", "attention_medium_f16.hip", "attention_large_f16.hip", "temporal_attn.hip", "temporal_block.hip", "temporal_block_rr.hip", "ff_block.hip", "panel_linear.hip", "norm.hip", "elementwise.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_bf16_plain.hip", "gemm_bf16_conv.hip", "gemm_bf16_act.hip", "gemm_f16_plain.hip", "gemm_f16_conv.hip", "gemm_f16_act.hip", "gemm_f32.hip", "gemm_bf16_t3.hip", "gemm_f16_t3.hip", "gemm_f32_t3.hip", "gemm_f32x3.hip", "gemm_f32x3_t3.hip", "attention.hip", "attention_small.hip", "attention_medium.hip", "attention_large.hip", "attention_small_f16.hip", "attention_medium_f16.hip", "attention_large_f16.hip", "temporal_attn.hip", "temporal_block.hip", "temporal_block_rr.hip", "ff_block.hip", "panel_linear.hip", "norm.hip", "elementwise.hip"]
 # FYC_GEMM_VARIANTS=1: also build the round-4 main-loop experiments of tools/exp/gemm_variants/ (off by default, measured slower)
 VARIANTS = os.environ.get("FYC_GEMM_VARIANTS") == "1"
 VARIANT_DIR = os.path.join(HERE, "..", "tools", "exp", "gemm_variants")
@@ -35,7 +35,9 @@ AGPR_SOURCES = {"ff_block.hip", "panel_linear.hip", "temporal_block_rr.hip"}
 
 # one wave per SIMD: a packed f32 VALU instruction beside MFMAs costs such a wave ~22 cycles more than the two scalar ones it replaces
 # (MI355X_MICROARCH.md), and -O3's SLP vectoriser re-packs scalar f32 code into v_pk_*: off for these files
-NO_SLP_SOURCES = set(filter(None, os.environ.get("FYC_NO_SLP", "ff_block.hip").split(",")))
+# gemm_f32x3*.hip (two waves per SIMD): the x - hi subtractions of the operand split sit between the matrix instructions of the K loop; packed into
+# v_pk_add_f32 they cost the long-K convolutions 2-3 % (profiles/f32x3_bench.txt)
+NO_SLP_SOURCES = set(filter(None, os.environ.get("FYC_NO_SLP", "ff_block.hip,gemm_f32x3.hip,gemm_f32x3_t3.hip").split(",")))
 
 
 # attention: no NaN ever enters the softmax (masked keys are -inf, scores are finite products of finite operands), and hipcc otherwise puts an

@@ -15,6 +15,7 @@ FYC_F32, FYC_BF16, FYC_F16 = 0, 1, 2
 GEMM_PLAIN, GEMM_CONV3X3, GEMM_CONV3X3_UP2, GEMM_CONV_T3 = 0, 1, 2, 3
 EPI_LINEAR, EPI_GEGLU, EPI_HEADS = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2
+PRODUCTS_EXACT, PRODUCTS_SPLIT_BF16 = 0, 1      # fyc_gemm_args.f32_products
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -30,7 +31,7 @@ class GemmArgs(C.Structure):
                 ("rows_per_batch", i32), ("seg_cols", i32), ("heads", i32), ("tokens", i32),
                 ("out_scale", f32), ("dtype", i32), ("tile", i32), ("act", i32), ("ln_stats", vp), ("ln_colsum", vp),
                 ("ln_nparts", i32), ("ln_eps", f32), ("chan_parts", vp), ("cs_rows", i32), ("row_parts", vp), ("row_nparts", i32), ("workspace", vp), ("workspace_bytes", i64),
-                ("t3_frames", i32), ("t3_rows", i32)]
+                ("t3_frames", i32), ("t3_rows", i32), ("f32_products", i32)]
 
 
 class AttnArgs(C.Structure):
@@ -167,7 +168,7 @@ MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 304        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 305        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

@@ -1,5 +1,5 @@
 // Host entry of the GEMM family: argument validation, plan (gemm_plan.h), dispatch.
-// Kernel template: gemm_kernel.h; instantiations: gemm_{bf16,f16}_{plain,conv,act,t3}.hip, gemm_f32.hip, gemm_f32_t3.hip.
+// Kernel template: gemm_kernel.h; instantiations: gemm_{bf16,f16}_{plain,conv,act,t3}.hip, gemm_f32.hip, gemm_f32_t3.hip, gemm_f32x3.hip, gemm_f32x3_t3.hip.
 // The round-4 main-loop experiments that measured slower on every shape (ping-pong wave groups, tile configs 21 / 22 / 23; epilogue
 // under the next tile's K loop, config 31) live in tools/exp/gemm_variants/ and are only part of a library built with
 // FYC_GEMM_VARIANTS=1 (python -m followyourclick_amd._build; tests: tools/exp/gemm_variants/test_gemm_variants_gpu.py).
@@ -109,13 +109,16 @@ __global__ void __launch_bounds__(256) splitk_finish_stats_kernel(const float* _
   }
 }
 
-// the kernel entry of a plan's family
-int run(const GemmPlan& pl, const GemmP& p, int batch, hipStream_t st) {
+// the kernel entry of a plan's family; `products`: fyc_gemm_args::f32_products - the plan is the same for both rules, only the instantiation differs
+int run(const GemmPlan& pl, const GemmP& p, int products, int batch, hipStream_t st) {
 #ifdef FYC_GEMM_VARIANTS
   if (pl.loop == GEMM_LOOP_OV) return run_ov(p, pl.cfg, st);
   if (pl.loop == GEMM_LOOP_PP) return pl.family == GEMM_FAM_PLAIN ? run_pp_plain(p, pl.cfg, st) : run_pp_conv(p, pl.cfg, st);
 #endif
-  if (pl.dtype == FYC_F32) return pl.family == GEMM_FAM_T3 ? run_f32_t3(p, batch, pl.cfg, st) : run_f32(p, batch, pl.cfg, st);
+  if (pl.dtype == FYC_F32) {
+    const int cfg = pl.cfg | (products == FYC_PRODUCTS_SPLIT_BF16 ? CFG_F32X3 : 0);
+    return pl.family == GEMM_FAM_T3 ? run_f32_t3(p, batch, cfg, st) : run_f32(p, batch, cfg, st);
+  }
   const bool f16 = pl.dtype == FYC_F16;
   switch (pl.family) {
     case GEMM_FAM_T3: return f16 ? run_f16_t3(p, batch, pl.cfg, pl.ns, st) : run_bf16_t3(p, batch, pl.cfg, pl.ns, st);
@@ -168,6 +171,8 @@ extern "C" int fyc_gemm_stat_layout(const fyc_gemm_args* a, int32_t* tile_rows, 
 
 extern "C" int fyc_gemm(const fyc_gemm_args* a, void* stream) {
   FYC_REQUIRE(a != nullptr, "fyc_gemm: null args");
+  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || (a->f32_products == FYC_PRODUCTS_SPLIT_BF16 && a->dtype == FYC_F32),
+              "fyc_gemm: f32_products=%d must be 0 (exact) or, with dtype FYC_F32 only, 1 (split bf16) - dtype %d", a->f32_products, a->dtype);
   FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_gemm: fyc_init() not called");
   FYC_REQUIRE(a->dtype == FYC_F32 || gemm_is16(a->dtype), "fyc_gemm: bad dtype %d", a->dtype);
   const int es = gemm_is16(a->dtype) ? 2 : 4, ch = 16 / es;
@@ -275,7 +280,7 @@ extern "C" int fyc_gemm(const fyc_gemm_args* a, void* stream) {
   if (!plan_gemm(a, stats_of(a), false, pl, g_fyc_err)) return -2;
   p.wide = pl.wide; p.colc = pl.colc; p.cs_slots = pl.cs_slots;
   if (pl.splitk > 1) { p.splitk = pl.splitk; p.ws = (float*)a->workspace; }
-  const int rc = run(pl, p, batch, (hipStream_t)stream);
+  const int rc = run(pl, p, a->f32_products, batch, (hipStream_t)stream);
   if (rc != 0 || pl.splitk <= 1) return rc;
   return a->dtype == FYC_F16 ? finish<f16_t>(p, (hipStream_t)stream) : finish<bf16_t>(p, (hipStream_t)stream);
 }

@@ -2,6 +2,7 @@
 #include "gemm_kernel.h"
 namespace fycg {
 int run_f32_t3(const GemmP& p, int batch, int cfg, hipStream_t st) {
+  if (cfg & CFG_F32X3) return run_f32x3_t3(p, batch, cfg & ~CFG_F32X3, st);      // split-bf16 products: gemm_f32x3_t3.hip
   return dispatch_cfg<float, FYC_GEMM_CONV_T3, FYC_EPI_LINEAR, false>(cfg, 2, p, batch, st);
 }
 }  // namespace fycg

@@ -22,7 +22,8 @@
 // ends up with 4 *consecutive output channels* of one row: the epilogue (bias, time-embedding row,
 // residual, GEGLU gate, head split) is vectorised over channels and stores 8/16 B per lane.
 //
-// f32 parity mode uses the same kernel with v_mfma_f32_16x16x4_f32 (exact f32, 1/16 rate).
+// f32 parity mode uses the same kernel with v_mfma_f32_16x16x4_f32 (exact f32, 1/16 rate); its opt-in f32x3 product rule (Mma<f32x3_t>)
+// splits the f32 operands into bf16 halves in registers and runs three v_mfma_f32_16x16x32_bf16 per block and K tile.
 #pragma once
 #include <mutex>
 #include <type_traits>
@@ -129,6 +130,36 @@ template <> struct Mma<float> {
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
     return c;
+  }
+};
+
+// f32x3: the second product rule for f32-STORED operands (fyc_gemm_args::f32_products = FYC_PRODUCTS_SPLIT_BF16).  Every operand value is split in
+// registers, behind the LDS read, into two bf16 numbers hi = RNE_bf16(x), lo = RNE_bf16(x - hi) (the subtraction is exact in f32), and
+//   acc += hi(a) hi(w) + hi(a) lo(w) + lo(a) hi(w)        (lo lo, <= 2^-18 |a w|, is dropped; bf16 x bf16 products are exact in f32)
+// runs on v_mfma_f32_16x16x32_bf16.  One 128-byte K tile = 32 floats = the exact rule's two k-steps: a lane's two f32x4 fragments (chunks g and
+// 4 + g of its row, the same K positions on the A and on the W side) concatenated are the 8 values per operand the bf16 instruction wants - any K
+// order serves a dot product as long as both sides share it.  3 matrix instructions (48 cycles) per 16x16 block and K tile instead of 8 x 32 cycles.
+// A tag only: storage, loaders, LDS image and epilogues are float's (the kernel's T stays float, the tag is its product rule P).
+struct f32x3_t {};
+template <> struct Mma<f32x3_t> {
+  typedef f32x4 Frag;
+  struct Split { bf16x8 hi, lo; };
+  __device__ static __forceinline__ Split split(Frag x0, Frag x1) {
+    u32x4 h, l;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = e < 2 ? x0[2 * e] : x1[2 * e - 4], b = e < 2 ? x0[2 * e + 1] : x1[2 * e - 3];
+      h[e] = pack_bf16x2(a, b);
+      l[e] = pack_bf16x2(a - __uint_as_float(h[e] << 16), b - __uint_as_float(h[e] & 0xffff0000u));
+    }
+    return {__builtin_bit_cast(bf16x8, h), __builtin_bit_cast(bf16x8, l)};
+  }
+  __device__ static __forceinline__ f32x4 mma(Frag, Frag, f32x4 c) { return c; }     // (the per-k-step loops of the other rules: compiled for this one, never run)
+  // the two small terms first: they meet the running sum before the large one does
+  __device__ static __forceinline__ f32x4 mma(const Split& w, const Split& a, f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.lo, a.hi, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi, a.lo, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi, a.hi, c, 0, 0, 0);
   }
 };
 
@@ -1333,9 +1364,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
   }  // !WIDE
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, int MI = 16>
+// P: the product rule, T's own except for f32x3_t on float storage
+template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, int MI = 16, typename P = T>
 __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) {
-  typedef Mma<T> Tr;
+  typedef Mma<P> Tr;
   typedef typename Tr::Frag Frag;
   constexpr int NT = WGM * WGN * 64;
   constexpr int CH = 16 / (int)sizeof(T);  // elements per 16-B chunk
@@ -1348,6 +1380,9 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   static_assert(EPI != FYC_EPI_GEGLU || WTN % 2 == 0, "GEGLU pairs value / gate column blocks inside a wave");
   constexpr bool M32 = (MI == 32);       // 32x32x16 matrix instruction in the K loop (16-bit operands, 128-byte K tiles, even block counts)
   static_assert(MI == 16 || (MI == 32 && sizeof(T) == 2 && RB == 128 && WTM % 2 == 0 && WTN % 2 == 0), "32x32x16 main loop: 16-bit operands, wave tile of whole 32x32 blocks");
+  constexpr bool SPLIT3 = std::is_same<P, f32x3_t>::value;      // split-bf16 products of f32 operands (Mma<f32x3_t>)
+  static_assert(std::is_same<P, T>::value || (SPLIT3 && std::is_same<T, float>::value && RB == 128 && MI == 16 && WGM * WGN == 4),
+                "f32x3: float storage, one 32-float K tile per matrix instruction, the 4-wave tiles of the f32 mode");
   constexpr int A_BYTES = BM * RB, STAGE = (BM + BN) * RB;
   constexpr bool STAGGER = (WGM * WGN == 8) && KSTEPS >= 2 && NS == 2;
   static_assert(A_IT * NT == BM * CPR && B_IT * NT == BN * CPR, "tile/threads mismatch");
@@ -1589,6 +1624,28 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
       for (int j = 0; j < WTN; ++j) acc[i][j] = Tr::mma(bf1[j], af1[i], acc[i][j]);
     __builtin_amdgcn_sched_barrier(0);
   };
+  // f32x3: the fragments of both k-steps of the exact rule, split in registers, are ONE step of the bf16 instruction
+  auto compute_split3 = [&](int stage) {
+    if constexpr (SPLIT3) {
+      const char* sA = smem + stage * STAGE + (wm * WTM * 16 + r16) * RB;
+      const char* sB = smem + stage * STAGE + A_BYTES + (wn * WTN * 16 + r16) * RB;
+      const int coff0 = (g ^ sw) * 16, coff1 = ((4 + g) ^ sw) * 16;
+      Frag af[2][WTM], bf[2][WTN];
+#pragma unroll
+      for (int i = 0; i < WTM; ++i) { af[0][i] = *reinterpret_cast<const Frag*>(sA + i * 16 * RB + coff0); af[1][i] = *reinterpret_cast<const Frag*>(sA + i * 16 * RB + coff1); }
+#pragma unroll
+      for (int j = 0; j < WTN; ++j) { bf[0][j] = *reinterpret_cast<const Frag*>(sB + j * 16 * RB + coff0); bf[1][j] = *reinterpret_cast<const Frag*>(sB + j * 16 * RB + coff1); }
+      typename Tr::Split as[WTM], bs[WTN];
+#pragma unroll
+      for (int i = 0; i < WTM; ++i) as[i] = Tr::split(af[0][i], af[1][i]);
+#pragma unroll
+      for (int j = 0; j < WTN; ++j) bs[j] = Tr::split(bf[0][j], bf[1][j]);
+#pragma unroll
+      for (int i = 0; i < WTM; ++i)
+#pragma unroll
+        for (int j = 0; j < WTN; ++j) acc[i][j] = Tr::mma(bs[j], as[i], acc[i][j]);
+    }
+  };
   // 32x32x16 form: k32-step s = two k16-steps; lane (h = lane / 32, r32 = lane % 32) reads row r32 of a 32-row block, chunk 2 s' + h
   const int r32 = lane & 31, h32 = lane >> 5;
   const int sw32 = swz_key<RB, 32>(r32);
@@ -1748,7 +1805,9 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
       // (one copy of the MFMA code, two of the issue block: the accumulators never cross a divergent join)
       const bool late = STAGGER && p.stagger && wave >= (WGM * WGN) / 2;
       if (!late && i_tile < nwork) issue_next();
-      if constexpr (XSTEP) {
+      if constexpr (SPLIT3) {
+        compute_split3(st_c);
+      } else if constexpr (XSTEP) {
         compute_xstep(st_c, [&]() { if (late && i_tile < nwork) issue_next(); });
       } else {
         if constexpr (M32) compute32(st_c, 0, 1); else compute(st_c, 0, 1, no_mid);
@@ -1795,12 +1854,12 @@ inline int rowbias_slots(int bm, int rpb) {
   return n <= RB_SLOTS ? n : 0;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, int MI = 16>
+template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, int MI = 16, typename P = T>
 int launch(const GemmP& p, int batch, hipStream_t st) {
   constexpr bool PRE_BUILT = WIDE && NS == 2;
   constexpr int smem = NS * (BM + BN) * RB + (PRE_BUILT ? pre_bytes<BM, BN>() : 0);
   static_assert(smem <= 160 * 1024, "LDS budget");
-  auto kern = fyc_gemm_kernel<T, BM, BN, WGM, WGN, MODE, EPI, NS, RB, WIDE, MI>;
+  auto kern = fyc_gemm_kernel<T, BM, BN, WGM, WGN, MODE, EPI, NS, RB, WIDE, MI, P>;
   int dev = 0;
   (void)hipGetDevice(&dev);
   // per-device one-time setup (attribute + CU count), guarded: one process may drive several GPUs from several threads
@@ -1867,12 +1926,12 @@ int launch(const GemmP& p, int batch, hipStream_t st) {
 // All use the 2-deep ring (deeper rings measured no gain, profiles/r01_gemm_tile_sweep*.txt); config 1 is also built 3-deep so
 // that the counted-wait ring logic stays exercised (tests).  The narrow epilogue (WIDE = false: f32 parity mode and bf16
 // problems whose shapes / alignment rule out 16-byte accesses) only exists for configs 1 and 2.
-template <typename T, int MODE, int EPI, bool WIDE>
+template <typename T, int MODE, int EPI, bool WIDE, typename P = T>
 int dispatch_cfg(int cfg, int ns, const GemmP& p, int batch, hipStream_t st) {
   if constexpr (!WIDE) {
     if (cfg != 1 && cfg != 2) cfg = (p.N % 128 == 0 || p.N > 512) ? 1 : 2;
-    if (cfg == 1) return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 128, false>(p, batch, st);
-    return launch<T, 128, 64, 2, 2, MODE, EPI, 2, 128, false>(p, batch, st);
+    if (cfg == 1) return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 128, false, 16, P>(p, batch, st);
+    return launch<T, 128, 64, 2, 2, MODE, EPI, 2, 128, false, 16, P>(p, batch, st);
   } else {
     switch (cfg) {
       case 1: if (ns == 3) return launch<T, 128, 128, 2, 2, MODE, EPI, 3, 128, true>(p, batch, st);
@@ -1922,6 +1981,11 @@ int run_bf16_plain(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_bf16_conv(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_bf16_act(const GemmP& p, int batch, int cfg, hipStream_t st);   // LINEAR + activation: tile configs 1, 2, 6
 int run_f32(const GemmP& p, int batch, int cfg, hipStream_t st);
+// f32 storage, split-bf16 products (f32x3_t): gemm_f32x3.hip, gemm_f32x3_t3.hip.  fyc_gemm reaches them through run_f32 / run_f32_t3 with CFG_F32X3 OR-ed into
+// `cfg` (like the ring depth in fyc_gemm_args::tile): the product rule is no part of the plan, and the entry points of a (dtype, family) stay one per family
+constexpr int CFG_F32X3 = 0x100;
+int run_f32x3(const GemmP& p, int batch, int cfg, hipStream_t st);
+int run_f32x3_t3(const GemmP& p, int batch, int cfg, hipStream_t st);
 // f16 storage (FYC_F16): the same kernels on v_mfma_f32_16x16x32_f16
 int run_f16_plain(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_f16_conv(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);

@@ -16,11 +16,15 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from . import default_f32_products
 
 Tensor = torch.Tensor
 
 
 _DTYPE_CODES = {torch.bfloat16: L.FYC_BF16, torch.float16: L.FYC_F16, torch.float32: L.FYC_F32}
+
+
+_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # HipOps.f32_products -> fyc_gemm_args.f32_products
 
 
 def _dtc(dtype: torch.dtype) -> int:
@@ -66,6 +70,7 @@ class HipOps:
         self._ws_need = {}           # (shape, flags) -> split-K scratch bytes (fyc_gemm_workspace_bytes), see gemm()
         self._q_cache = {}           # host-side layout queries (row parts, split bytes, statistics layout) per shape
         self._inited_dev = None
+        self.f32_products = default_f32_products()      # "exact" | "split": the product rule of gemm() on f32 tensors (set_f32_products)
 
     # -- library ---------------------------------------------------------------------------
     def ensure_init(self, device: torch.device) -> None:
@@ -98,6 +103,15 @@ class HipOps:
         self._ws_need.clear()        # tile / split-K decisions depend on the tuning table
         self._q_cache.clear()
 
+    def set_f32_products(self, mode: str) -> None:
+        """"exact" or "split": the product rule of every later gemm() on f32 tensors that does not pass `products` itself (include/fyc.h,
+        fyc_gemm_args.f32_products); 16-bit tensors are not affected.  A captured graph (FYC_HIPGRAPH=1) replays the mode it was captured in."""
+        if mode not in _PRODUCTS:
+            raise ValueError(f"f32 products {mode!r}: expected 'exact' or 'split'")
+        self.f32_products = mode
+        self._ws_need.clear()
+        self._q_cache.clear()
+
     def _stream(self) -> int:
         """raw hipStream_t of torch's CURRENT stream on the bound device (a `with torch.cuda.stream(...)` block is honoured);
         the raw getter costs ~0.3 us, torch.cuda.current_stream().cuda_stream ~8 us - a third of the host time of a launch"""
@@ -114,13 +128,21 @@ class HipOps:
              stride_w: int = 0, stride_o: int = 0, heads: Optional[dict] = None, tile: int = 0,
              a2: Optional[Tensor] = None, k_split: int = 0, lda2: int = 0, act: int = L.ACT_NONE,
              ln_stats: Optional[Tensor] = None, ln_colsum: Optional[Tensor] = None, ln_nparts: int = 0, ln_eps: float = 1e-5,
-             chan_parts: Optional[Tensor] = None, cs_rows: int = 0, row_parts: Optional[Tensor] = None, row_nparts: int = 0) -> None:
+             chan_parts: Optional[Tensor] = None, cs_rows: int = 0, row_parts: Optional[Tensor] = None, row_nparts: int = 0,
+             products: Optional[str] = None) -> None:
+        """products: None = this instance's f32_products, else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors raises)"""
         self.ensure_init(a.device)
+        if products is not None and products not in _PRODUCTS:
+            raise ValueError(f"gemm: products {products!r}: expected None, 'exact' or 'split'")
+        if a.dtype != torch.float32 and products == "split":
+            raise TypeError(f"gemm: products='split' needs float32 tensors (got {a.dtype})")
         g = self._gemm_args(a, w, out, M=M, N=N, K=K, lda=lda, ldw=ldw, ldo=ldo, bias=bias, rowbias=rowbias, rows_per_batch=rows_per_batch,
                             residual=residual, ldr=ldr, ldrb=ldrb, out_scale=out_scale, epilogue=epilogue, mode=mode, conv=conv, batch=batch,
                             stride_a=stride_a, stride_w=stride_w, stride_o=stride_o, heads=heads, tile=tile, a2=a2, k_split=k_split,
                             lda2=lda2, act=act, ln_stats=ln_stats, ln_colsum=ln_colsum, ln_nparts=ln_nparts, ln_eps=ln_eps,
                             chan_parts=chan_parts, cs_rows=cs_rows, row_parts=row_parts, row_nparts=row_nparts)
+        if a.dtype == torch.float32:
+            g.f32_products = _PRODUCTS[self.f32_products if products is None else products]
         # split-K scratch (small M, long K): the decision depends on the shape and the flags below only - cached, so that the ~300
         # GEMM launches of a DDIM step do not each pay a second ctypes call.  One grown-on-demand buffer: all work of a process is on
         # ONE stream (the engine's), a second stream would need its own HipOps.

@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off. */
-#define FYC_VERSION 304
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT). */
+#define FYC_VERSION 305
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -67,6 +67,15 @@ int fyc_set_tuning(int key, int value);
  * (animatediff/models/resnet.py:19-27, 296-342), Downsample3D (:188-196), Upsample3D (:137-170),
  * and the baddbmm/bmm of the materialised attention used in f32 parity mode and the VAE
  * (diffusers/models/attention.py:342-368, 649-678).
+ *
+ * Products of FYC_F32 operands (version 305, f32_products).  FYC_PRODUCTS_EXACT (0, the default): v_mfma_f32_16x16x4_f32, every product an f32
+ * product - the parity mode, 1/16 of the 16-bit matrix rate.  FYC_PRODUCTS_SPLIT_BF16 (1): every operand value x is split in registers into
+ * hi = RNE_bf16(x) and lo = RNE_bf16(x - hi) and  acc += hi(a) hi(w) + hi(a) lo(w) + lo(a) hi(w)  runs as three v_mfma_f32_16x16x32_bf16 with f32
+ * accumulation (lo lo is dropped): per element  |got - exact| <= (K + 8) 2^-24 S + 2^-15 sum_k |a||w|  in the worst case (every value just above a power of
+ * two, every rounding at half a unit) on top of the storage rounding; about 4e-6 relative L2 per GEMM on random operands.  Operands, packed weights, tiles, split-K, workspace and the layouts of chan_parts / row_parts are those of the
+ * exact rule: no query reads the field.  Non-finite inputs give non-finite outputs in the rows / columns they touch and nowhere else, but an
+ * Inf may come out as NaN (lo = Inf - Inf), and a finite |x| above the largest bf16 number (3.3895e38) rounds to hi = Inf.  Any value other than
+ * 0 / 1, or a non-zero value with a 16-bit dtype, is refused.
  */
 /* CONV3X3_UP2: 3x3 conv over the nearest-neighbour upsampling of the input to (Hout, Wout); 2x is the fast path,
  * any Hout >= Hin works (Upsample3D with a forwarded `upsample_size`, reference resnet.py:152-157, unet.py:644-645) */
@@ -82,6 +91,7 @@ enum { FYC_EPI_LINEAR = 0, FYC_EPI_GEGLU = 1, FYC_EPI_HEADS = 2 };
 /* pointwise activation of the LINEAR epilogue (conditioning encoders): exact erf GELU (CLIP-ViT-H `gelu`, ip_adapter/resampler.py:17)
  * and x*sigmoid(1.702x) (CLIP-ViT-L text encoder `quick_gelu`) */
 enum { FYC_ACT_NONE = 0, FYC_ACT_GELU = 1, FYC_ACT_QUICK_GELU = 2 };
+enum { FYC_PRODUCTS_EXACT = 0, FYC_PRODUCTS_SPLIT_BF16 = 1 };
 
 typedef struct {
   const void* a;         /* PLAIN: [batch][M][lda]; CONV: NHWC input [frames][Hin][Win][Cin]; CONV_T3: [clips * t3_frames * t3_rows][Cin] */
@@ -135,6 +145,8 @@ typedef struct {
   void* workspace; int64_t workspace_bytes;
   /* (version 304) FYC_GEMM_CONV_T3: frames per clip and rows per frame (H*W) of `a`; both zero in every other mode */
   int32_t t3_frames, t3_rows;
+  /* (version 305) FYC_F32 only: FYC_PRODUCTS_* - how the products of the f32 operands are formed (see above); zero = exact */
+  int32_t f32_products;
 } fyc_gemm_args;
 int fyc_gemm(const fyc_gemm_args* a, void* stream);
 /* scratch bytes fyc_gemm can use for these arguments (split-K partial sums); 0 = none needed */

@@ -12,7 +12,7 @@ T = torch.bfloat16
 DEV = torch.device("cuda:0")
 
 
-def run(h, M, N, K, *, epi=0, res=False, ln=False, rowbias=False, stats=False, nb=1, tile=0, reps=6, conv=None, k2=0, segs=0):
+def run(h, M, N, K, *, epi=0, res=False, ln=False, rowbias=False, stats=False, nb=1, tile=0, reps=6, conv=None, k2=0, segs=0, T=T, products=None, batch=1):
     ocols = N // 2 if epi == 1 else N
     sets = []
     for _ in range(nb):
@@ -23,6 +23,13 @@ def run(h, M, N, K, *, epi=0, res=False, ln=False, rowbias=False, stats=False, n
     w = (torch.randn(N, K, device=DEV) / K ** 0.5).to(T)
     bias = torch.randn(N, device=DEV)
     kw = dict(M=M, N=N, K=K, lda=K - k2, ldw=K, ldo=ocols, ldr=N, epilogue=epi, bias=bias, tile=tile)
+    if products is not None:      # f32 operands: "exact" / "split" (HipOps.gemm)
+        kw["products"] = products
+    if batch > 1:                 # the score product of the materialised attention: `batch` heads of [M][K] x [N][K], outputs stacked
+        for i in range(len(sets)):
+            sets[i] = (torch.randn(batch * M, K, device=DEV).to(T), torch.empty(batch * M, N, dtype=T, device=DEV), None)
+        w = (torch.randn(batch * N, K, device=DEV) / K ** 0.5).to(T)
+        kw.update(batch=batch, stride_a=M * K, stride_w=N * K, stride_o=M * N, bias=None)
     if conv:
         Hh, Ww, Cin = conv
         kw.update(lda=Cin, mode=1, conv=dict(Hout=Hh, Wout=Ww, Hin=Hh, Win=Ww, Cin=Cin, stride=1))
@@ -61,7 +68,7 @@ def run(h, M, N, K, *, epi=0, res=False, ln=False, rowbias=False, stats=False, n
     e.record()
     torch.cuda.synchronize()
     us = s.elapsed_time(e) / (reps * nb) * 1e3
-    return us, 2.0 * M * N * K / us / 1e6
+    return us, 2.0 * batch * M * N * K / us / 1e6
 
 
 def sweep(h):
@@ -111,9 +118,28 @@ def sweep(h):
         print(name.ljust(22), f"{M}x{N}x{K}".ljust(24), " ".join(row), flush=True)
 
 
+def f32_products(h):
+    """PROBE_F32=1: the three largest f32 problems of a DDIM step at 16 frames 512^2 (the convolutions of the up path at 64x64 and 32x32, and FF1 at
+    64x64, whose K loop is 10 tiles), and the score product of the materialised attention (8 heads of one frame), in both product rules; cold operands"""
+    cases = [("conv up L0 960->320 rb st", 131072, 320, 8640, dict(rowbias=True, stats=True, conv=(64, 64, 960))),
+             ("conv up L1 1920->640 rb st", 32768, 640, 17280, dict(rowbias=True, stats=True, conv=(32, 32, 1920))),
+             ("FF1 GEGLU L0 ln", 131072, 2560, 320, dict(epi=1, ln=True)),
+             ("scores L0, 8 heads", 4096, 4096, 40, dict(batch=8))]
+    print("f32 operands, cold (4 rotating buffer sets): us per launch and TFLOP/s, exact (v_mfma_f32_16x16x4_f32) vs split-bf16 products")
+    for name, M, N, K, kw in cases:
+        row = []
+        for products in ("exact", "split"):
+            us, tf = run(h, M, N, K, nb=4, reps=3, T=torch.float32, products=products, **kw)
+            row.append((us, tf))
+            torch.cuda.empty_cache()
+        print(name.ljust(28), f"{M}x{N}x{K}".ljust(20), f"exact {row[0][0]:9.1f} us {row[0][1]:6.1f} TF   split {row[1][0]:9.1f} us {row[1][1]:6.1f} TF   x{row[0][0] / row[1][0]:.2f}", flush=True)
+
+
 def main():
     h = ops.get()
     h.ensure_init(DEV)
+    if os.environ.get("PROBE_F32"):
+        return f32_products(h)
     for kv in filter(None, os.environ.get("PROBE_TUNING", "").split(",")):      # e.g. PROBE_TUNING=5=3,0=1
         k, v = kv.split("=")
         h.set_tuning(int(k), int(v))
