@@ -15,7 +15,7 @@ FYC_F32, FYC_BF16, FYC_F16 = 0, 1, 2
 GEMM_PLAIN, GEMM_CONV3X3, GEMM_CONV3X3_UP2, GEMM_CONV_T3 = 0, 1, 2, 3
 EPI_LINEAR, EPI_GEGLU, EPI_HEADS = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2
-PRODUCTS_EXACT, PRODUCTS_SPLIT_BF16 = 0, 1      # fyc_gemm_args.f32_products
+PRODUCTS_EXACT, PRODUCTS_SPLIT_BF16 = 0, 1      # fyc_gemm_args.f32_products, fyc_tattn_args.f32_products
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -43,7 +43,7 @@ class AttnArgs(C.Structure):
 
 class TAttnArgs(C.Structure):
     _fields_ = [("qkv", vp), ("o", vp), ("clips", i32), ("frames", i32), ("pixels", i32), ("heads", i32), ("d", i32),
-                ("scale", f32), ("dtype", i32), ("rope_cos", vp), ("rope_sin", vp)]
+                ("scale", f32), ("dtype", i32), ("rope_cos", vp), ("rope_sin", vp), ("f32_products", i32)]
 
 
 class GnStatsArgs(C.Structure):
@@ -168,7 +168,7 @@ MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 305        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 306        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

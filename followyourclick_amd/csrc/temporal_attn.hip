@@ -10,13 +10,17 @@
 //   S^T = K Q^T (rows = key frames, cols = query frames), full softmax in registers (all keys of a
 //   query are in 4 lanes x 4..16 regs), O^T = V^T P^T with the keys as the 32 MFMA k-slots (two such
 //   MFMAs per output tile for F > 32).
-// f32 path: scalar reference-precision kernel (parity mode only).
+// f32 path: scalar reference-precision kernel (parity mode only); with f32_products = FYC_PRODUCTS_SPLIT_BF16 the matrix-instruction kernel of
+// temporal_attn_f32x3.hip (f32 storage, every product from three bf16 matrix instructions).
 //
 // ROPE (template parameter; rope_cos / rope_sin of fyc_tattn_args, f32 [F][d/2]): q and k are rotated per
 // frame before the score product - x'[c] = x[c] cos[f][c mod h] -/+ x[c +/- h] sin[f][c mod h], h = d/2, the
 // rotate_half pairing of the reference's RoPE (rope.py:102-116) - in f32 on the loaded values and rounded
 // once to the operand type.  V is untouched.  The ROPE = false instantiations are the kernels without it.
 #include "row_panel.h"
+
+// temporal_attn_f32x3.hip: FYC_F32 tensors with f32_products = FYC_PRODUCTS_SPLIT_BF16; fyc_temporal_attention has checked the arguments
+int fyc_tattn_f32x3_launch(const fyc_tattn_args* a, void* stream);
 
 namespace {
 
@@ -296,6 +300,8 @@ int launch_d(const TAttnP& p, hipStream_t st) {
 
 extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
   FYC_REQUIRE(a && a->qkv && a->o, "fyc_temporal_attention: null pointer");
+  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->f32_products == FYC_PRODUCTS_SPLIT_BF16, "fyc_temporal_attention: f32_products=%d (0 = exact, 1 = split bf16)", a->f32_products);
+  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->dtype == FYC_F32, "fyc_temporal_attention: f32_products=%d needs dtype FYC_F32", a->f32_products);
   FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_temporal_attention: fyc_init() not called");
   FYC_REQUIRE(a->clips > 0 && a->frames > 0 && a->pixels > 0 && a->heads > 0, "fyc_temporal_attention: bad sizes");
   FYC_REQUIRE(a->frames <= 64, "fyc_temporal_attention: frames=%d > 64 unsupported", a->frames);
@@ -309,6 +315,7 @@ extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
   const bool rope = a->rope_cos != nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (a->dtype == FYC_F32) {
+    if (a->f32_products == FYC_PRODUCTS_SPLIT_BF16) return fyc_tattn_f32x3_launch(a, stream);      // temporal_attn_f32x3.hip
     const long long total = (long long)p.clips * p.pixels * p.heads * p.frames;
     const dim3 grid((unsigned)((total + 255) / 256));
     if (rope) hipLaunchKernelGGL(tattn_f32_kernel<true>, grid, dim3(256), 0, st, p);

@@ -24,7 +24,7 @@ Tensor = torch.Tensor
 _DTYPE_CODES = {torch.bfloat16: L.FYC_BF16, torch.float16: L.FYC_F16, torch.float32: L.FYC_F32}
 
 
-_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # HipOps.f32_products -> fyc_gemm_args.f32_products
+_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # HipOps.f32_products -> fyc_gemm_args.f32_products, fyc_tattn_args.f32_products
 
 
 def _dtc(dtype: torch.dtype) -> int:
@@ -70,7 +70,7 @@ class HipOps:
         self._ws_need = {}           # (shape, flags) -> split-K scratch bytes (fyc_gemm_workspace_bytes), see gemm()
         self._q_cache = {}           # host-side layout queries (row parts, split bytes, statistics layout) per shape
         self._inited_dev = None
-        self.f32_products = default_f32_products()      # "exact" | "split": the product rule of gemm() on f32 tensors (set_f32_products)
+        self.f32_products = default_f32_products()      # "exact" | "split": the product rule of gemm() and temporal_attention() on f32 tensors (set_f32_products)
 
     # -- library ---------------------------------------------------------------------------
     def ensure_init(self, device: torch.device) -> None:
@@ -104,8 +104,8 @@ class HipOps:
         self._q_cache.clear()
 
     def set_f32_products(self, mode: str) -> None:
-        """"exact" or "split": the product rule of every later gemm() on f32 tensors that does not pass `products` itself (include/fyc.h,
-        fyc_gemm_args.f32_products); 16-bit tensors are not affected.  A captured graph (FYC_HIPGRAPH=1) replays the mode it was captured in."""
+        """"exact" or "split": the product rule of every later gemm() and temporal_attention() on f32 tensors that does not pass `products` itself
+        (include/fyc.h, fyc_gemm_args.f32_products / fyc_tattn_args.f32_products); 16-bit tensors are not affected.  A captured graph (FYC_HIPGRAPH=1) replays the mode it was captured in."""
         if mode not in _PRODUCTS:
             raise ValueError(f"f32 products {mode!r}: expected 'exact' or 'split'")
         self.f32_products = mode
@@ -259,8 +259,14 @@ class HipOps:
         self._call("fyc_repeat", a)
 
     def temporal_attention(self, qkv: Tensor, o: Tensor, *, clips: int, frames: int, pixels: int, heads: int, d: int,
-                           scale: float, rope: Optional[Tuple[Tensor, Tensor]] = None) -> None:
-        """rope = (cos, sin): f32 device tables [frames][d/2]; q and k are rotated per frame before the score product (include/fyc.h)"""
+                           scale: float, rope: Optional[Tuple[Tensor, Tensor]] = None, products: Optional[str] = None) -> None:
+        """rope = (cos, sin): f32 device tables [frames][d/2]; q and k are rotated per frame before the score product (include/fyc.h).
+        products: None = this instance's f32_products (the switch gemm() reads), else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors
+        raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode)"""
+        if products is not None and products not in _PRODUCTS:
+            raise ValueError(f"temporal_attention: products {products!r}: expected None, 'exact' or 'split'")
+        if qkv.dtype != torch.float32 and products == "split":
+            raise TypeError(f"temporal_attention: products='split' needs float32 tensors (got {qkv.dtype})")
         self.ensure_init(qkv.device)
         a = L.TAttnArgs()
         a.qkv, a.o, a.clips, a.frames, a.pixels, a.heads, a.d, a.scale, a.dtype = (_p(qkv), _p(o), clips, frames, pixels,
@@ -271,6 +277,8 @@ class HipOps:
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.device != qkv.device or tuple(t.shape) != (frames, d // 2):
                     raise ValueError(f"temporal_attention: rope tables must be contiguous f32 [{frames}][{d // 2}] tensors on {qkv.device}")
             a.rope_cos, a.rope_sin = cos.data_ptr(), sin.data_ptr()
+        if qkv.dtype == torch.float32:
+            a.f32_products = _PRODUCTS[self.f32_products if products is None else products]
         self._call("fyc_temporal_attention", a)
 
     def _tblock_args(self, x, out, w_qkv, colsum, bias, pe_bias, w_out, b_out, clips, frames, pixels, heads, d, scale, eps):

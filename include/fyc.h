@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT). */
-#define FYC_VERSION 305
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off. */
+#define FYC_VERSION 306
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -193,6 +193,16 @@ int fyc_attention(const fyc_attn_args* a, void* stream);
  * mm_attn_cross.py:148-177).  qkv is the token-major output of the fused to_q|to_k|to_v GEMM,
  * [(b f p)][3C]; o is token-major [(b f p)][C].  The '(b f) d c -> (b d) f c' transposes of the
  * reference are index arithmetic here.  frames <= 64, d a multiple of 8 up to 160.
+ *
+ * Products of FYC_F32 operands (version 306, f32_products; hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) as for fyc_gemm).  FYC_PRODUCTS_EXACT (0, the
+ * default): the scalar f32 kernel, every product an f32 product.  FYC_PRODUCTS_SPLIT_BF16 (1): one wave per (clip, pixel, head) on v_mfma_f32_16x16x32_bf16:
+ *  - q and k are loaded as f32 and, with RoPE, rotated in f32 exactly as specified below; nothing is rounded to a 16-bit type before the split;
+ *  - s[fq][fk] = sum_c hi(q) hi(k) + hi(q) lo(k) + lo(q) hi(k), accumulated in f32;
+ *  - the softmax runs in f32: max, exp2 of the scaled difference, f32 row sum; p is normalised by the row sum in f32 and then split;
+ *  - o[fq][c] = sum_fk hi(p) hi(v) + hi(p) lo(v) + lo(p) hi(v), accumulated in f32 and stored as f32.
+ * Per product the rule is off by at most 2^-15 |a||b| (fyc_gemm's figure): 2^-15 sum_c |q||k| on a score before the scale, 2^-15 sum_fk p |v| on an output
+ * element, on top of the f32 accumulation.  A single frame returns hi(v) + lo(v) (p = 1), not v.  qkv and o must be 16-byte aligned.  Non-finite inputs stay
+ * inside their (clip, pixel, head) task.  Any value other than 0 / 1, or a non-zero value with a 16-bit dtype, is refused.
  */
 typedef struct {
   const void* qkv; void* o;
@@ -206,6 +216,8 @@ typedef struct {
    * (rotate_half), computed in f32 on the loaded values and rounded once to `dtype`; v is untouched.  The reference's query factor
    * log(train_video_length) / log(video_length) for clips longer than the training length goes into `scale`. */
   const float* rope_cos; const float* rope_sin;
+  /* (version 306) FYC_F32 only: FYC_PRODUCTS_* - how the products of the f32 operands are formed (see above); zero = exact */
+  int32_t f32_products;
 } fyc_tattn_args;
 int fyc_temporal_attention(const fyc_tattn_args* a, void* stream);
 
