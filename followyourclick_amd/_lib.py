@@ -15,7 +15,7 @@ FYC_F32, FYC_BF16, FYC_F16 = 0, 1, 2
 GEMM_PLAIN, GEMM_CONV3X3, GEMM_CONV3X3_UP2, GEMM_CONV_T3 = 0, 1, 2, 3
 EPI_LINEAR, EPI_GEGLU, EPI_HEADS = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2
-PRODUCTS_EXACT, PRODUCTS_SPLIT_BF16 = 0, 1      # fyc_gemm_args.f32_products, fyc_tattn_args.f32_products
+PRODUCTS_EXACT, PRODUCTS_SPLIT_BF16 = 0, 1      # fyc_gemm_args.f32_products, fyc_tattn_args.f32_products, fyc_attn_args.f32_products
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -38,7 +38,7 @@ class AttnArgs(C.Structure):
     _fields_ = [("q", vp), ("k", vp), ("vt", vp), ("o", vp),
                 ("batch", i32), ("heads", i32), ("n_q", i32), ("n_k", i32), ("d", i32),
                 ("ldo", i32), ("ldvt", i32), ("kv_batch_div", i32), ("o_accumulate", i32),
-                ("scale", f32), ("o_scale", f32), ("dtype", i32), ("q_batch_mod", i32)]
+                ("scale", f32), ("o_scale", f32), ("dtype", i32), ("q_batch_mod", i32), ("f32_products", i32)]
 
 
 class TAttnArgs(C.Structure):
@@ -168,7 +168,7 @@ MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 306        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 307        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

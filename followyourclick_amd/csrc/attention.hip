@@ -2,16 +2,24 @@
 // instantiations: attention_small.hip, attention_medium.hip, attention_large.hip).
 #include "attention_kernel.h"
 
+// attention_f32x3.hip: FYC_F32 tensors with f32_products = FYC_PRODUCTS_SPLIT_BF16; fyc_attention has checked the arguments
+int fyc_attn_f32x3_launch(const fyc_attn_args* a, void* stream);
+
 extern "C" int fyc_attention(const fyc_attn_args* a, void* stream) {
   FYC_REQUIRE(a && a->q && a->k && a->vt && a->o, "fyc_attention: null pointer");
+  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->f32_products == FYC_PRODUCTS_SPLIT_BF16, "fyc_attention: f32_products=%d (0 = exact, 1 = split bf16)", a->f32_products);
+  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->dtype == FYC_F32, "fyc_attention: f32_products=%d needs dtype FYC_F32", a->f32_products);
+  FYC_REQUIRE(a->dtype != FYC_F32 || a->f32_products == FYC_PRODUCTS_SPLIT_BF16,
+              "fyc_attention: dtype FYC_F32 needs f32_products = FYC_PRODUCTS_SPLIT_BF16 (there is no exact fused f32 kernel: the exact f32 mode uses materialised attention)");
+  FYC_REQUIRE(a->dtype == FYC_F32 || a->dtype == FYC_BF16 || a->dtype == FYC_F16, "fyc_attention: bad dtype %d", a->dtype);
   FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_attention: fyc_init() not called");
-  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16, "fyc_attention: bf16 / f16 only (f32 parity mode uses materialised attention)");
   FYC_REQUIRE(a->batch > 0 && a->heads > 0 && a->n_q > 0 && a->n_k > 0, "fyc_attention: bad sizes");
   FYC_REQUIRE(a->d % 8 == 0 && a->d >= 8 && a->d <= 160, "fyc_attention: head dim %d (multiple of 8, <= 160)", a->d);
   FYC_REQUIRE(a->ldvt % 8 == 0 && a->ldvt >= a->n_k, "fyc_attention: ldvt=%d must be a multiple of 8 and >= n_k", a->ldvt);
   FYC_REQUIRE(a->ldo % 4 == 0, "fyc_attention: ldo must be a multiple of 4");
   FYC_REQUIRE(a->kv_batch_div >= 1, "fyc_attention: kv_batch_div");
   FYC_REQUIRE(a->q_batch_mod >= 0 && a->q_batch_mod <= a->batch, "fyc_attention: q_batch_mod %d (0 .. batch)", a->q_batch_mod);
+  if (a->dtype == FYC_F32) return fyc_attn_f32x3_launch(a, stream);      // attention_f32x3.hip (its QT rule is written there, beside the kernel's budgets)
   fyca::AttnP p;
   p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.vt = (const bf16_t*)a->vt; p.o = (bf16_t*)a->o;
   p.batch = a->batch; p.heads = a->heads; p.n_q = a->n_q; p.n_k = a->n_k; p.d = a->d; p.ldo = a->ldo; p.ldvt = a->ldvt;

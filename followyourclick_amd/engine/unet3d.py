@@ -82,7 +82,7 @@ class UNet3DEngine(EngineBase):
         self.ops = ops if ops is not None else ops_mod.get()
         self.device = packed.conv_in_w.device
         self.groups = self.cfg.norm_num_groups
-        self.mat_attn = self.dtype == torch.float32  # f32 parity mode: materialised attention through the GEMM (bf16 / f16: fyc_attention)
+        self.mat_attn = self.dtype == torch.float32  # f32 tensors: materialised attention through the GEMM unless the product rule is "split" (_attend decides per call); bf16 / f16: fyc_attention
         self.transformers: List[Packed] = []
         for blk in self.P.down:
             self.transformers += [l.attn for l in blk.layers if l.attn is not None]
@@ -175,7 +175,12 @@ class UNet3DEngine(EngineBase):
         is the transformer's own: C / d"""
         H, o = C // d, self.ops
         scale = d ** -0.5
-        if not self.mat_attn:
+        # f32 tensors: the fused kernel exists with split-bf16 products only (include/fyc.h, fyc_attn_args.f32_products).  Decided per call, not in
+        # __init__: set_f32_products() may flip the mode of a live engine; FYC_F32_FLASH=0 keeps the materialised sequence in split mode (A/B).
+        # Every head dim and key count of the UNet families measured 4.5 x - 47 x faster fused, slowest fused round against fastest materialised round
+        # (profiles/f32x3_attention.txt section 2): no shape family stays materialised.
+        flash = not self.mat_attn or (getattr(o, "f32_products", "exact") == "split" and os.environ.get("FYC_F32_FLASH", "1") != "0")
+        if flash:
             o.attention(q, k, vt, out, batch=batch, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldvt, scale=scale,
                         kv_batch_div=kv_div, accumulate=accumulate, o_scale=o_scale, **({"q_batch_mod": q_mod} if q_mod else {}))
             return

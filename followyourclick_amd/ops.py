@@ -24,7 +24,7 @@ Tensor = torch.Tensor
 _DTYPE_CODES = {torch.bfloat16: L.FYC_BF16, torch.float16: L.FYC_F16, torch.float32: L.FYC_F32}
 
 
-_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # HipOps.f32_products -> fyc_gemm_args.f32_products, fyc_tattn_args.f32_products
+_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # HipOps.f32_products -> fyc_gemm_args.f32_products, fyc_tattn_args.f32_products, fyc_attn_args.f32_products (f32 attention: "split" only)
 
 
 def _dtc(dtype: torch.dtype) -> int:
@@ -104,8 +104,10 @@ class HipOps:
         self._q_cache.clear()
 
     def set_f32_products(self, mode: str) -> None:
-        """"exact" or "split": the product rule of every later gemm() and temporal_attention() on f32 tensors that does not pass `products` itself
-        (include/fyc.h, fyc_gemm_args.f32_products / fyc_tattn_args.f32_products); 16-bit tensors are not affected.  A captured graph (FYC_HIPGRAPH=1) replays the mode it was captured in."""
+        """"exact" or "split": the product rule of every later gemm(), temporal_attention() and attention() on f32 tensors that does not pass `products` itself
+        (include/fyc.h, fyc_gemm_args.f32_products / fyc_tattn_args.f32_products / fyc_attn_args.f32_products); 16-bit tensors are not affected.  attention() on f32
+        tensors exists in "split" only: in "exact" the engine takes the materialised path and a direct call raises.  A captured graph (FYC_HIPGRAPH=1) replays the
+        mode it was captured in."""
         if mode not in _PRODUCTS:
             raise ValueError(f"f32 products {mode!r}: expected 'exact' or 'split'")
         self.f32_products = mode
@@ -235,14 +237,26 @@ class HipOps:
     # -- attention ---------------------------------------------------------------------------
     def attention(self, q: Tensor, k: Tensor, vt: Tensor, o: Tensor, *, batch: int, heads: int, n_q: int, n_k: int,
                   d: int, ldo: int, ldvt: int, scale: float, kv_batch_div: int = 1, accumulate: bool = False,
-                  o_scale: float = 1.0, q_batch_mod: int = 0) -> None:
-        """q_batch_mod > 0: q holds q_batch_mod batch elements, element b attends with the q of b % q_batch_mod"""
+                  o_scale: float = 1.0, q_batch_mod: int = 0, products: Optional[str] = None) -> None:
+        """q_batch_mod > 0: q holds q_batch_mod batch elements, element b attends with the q of b % q_batch_mod.
+        products: None = this instance's f32_products (the switch gemm() reads), else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors
+        raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode).  f32 tensors run the fused kernel with split-bf16 products
+        only (include/fyc.h): a resolved "exact" raises - the exact f32 mode is the materialised sequence gemm / softmax_rows / gemm (engine/unet3d.py::_attend)"""
+        if products is not None and products not in _PRODUCTS:
+            raise ValueError(f"attention: products {products!r}: expected None, 'exact' or 'split'")
+        if q.dtype != torch.float32 and products == "split":
+            raise TypeError(f"attention: products='split' needs float32 tensors (got {q.dtype})")
+        if q.dtype == torch.float32 and (self.f32_products if products is None else products) == "exact":
+            raise L.FycError("attention: float32 tensors run fused with products='split' only; with exact f32 products use the materialised path "
+                             "(gemm, softmax_rows, gemm: engine/unet3d.py::_attend)")
         self.ensure_init(q.device)
         a = L.AttnArgs()
         a.q, a.k, a.vt, a.o = _p(q), _p(k), _p(vt), _p(o)
         a.batch, a.heads, a.n_q, a.n_k, a.d, a.ldo, a.ldvt = batch, heads, n_q, n_k, d, ldo, ldvt
         a.kv_batch_div, a.o_accumulate, a.scale, a.o_scale, a.dtype = kv_batch_div, int(accumulate), scale, o_scale, _dt(q)
         a.q_batch_mod = q_batch_mod
+        if q.dtype == torch.float32:
+            a.f32_products = L.PRODUCTS_SPLIT_BF16
         self._call("fyc_attention", a)
 
     def attention_q_batch_mod_supported(self) -> bool:

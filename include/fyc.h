@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off. */
-#define FYC_VERSION 306
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off; 307 = the same rule for the fused spatial attention: f32_products APPENDED to fyc_attention's arguments - zero = off (every 16-bit launch is unchanged); FYC_F32 tensors are taken with FYC_PRODUCTS_SPLIT_BF16 only. */
+#define FYC_VERSION 307
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -174,6 +174,23 @@ int fyc_chan_stats_reduce(const fyc_chan_stats_reduce_args* a, void* stream);
  * index = (b / kv_batch_div) * heads + h  (text K/V are shared by the F frames of a clip).
  * q_batch_mod > 0: the q of batch element b is read from batch element b % q_batch_mod (q holds q_batch_mod elements): the two
  * halves of a classifier-free-guidance pair share their queries up to the first cross-attention and differ in the text K / V only.
+ *
+ * FYC_F32 tensors (version 307, f32_products; hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) as for fyc_gemm and fyc_temporal_attention).  The same layouts in f32, the
+ * same kv_batch_div / q_batch_mod / o_accumulate / o_scale, d a multiple of 8 up to 160, ldvt % 8 == 0, ldo % 4 == 0, q / k / vt / o 16-byte aligned.  Only
+ * f32_products = FYC_PRODUCTS_SPLIT_BF16 runs (csrc/attention_f32x3.hip); FYC_PRODUCTS_EXACT with FYC_F32 is refused - there is no exact fused kernel, the exact f32
+ * mode goes through the materialised sequence fyc_gemm / fyc_softmax_rows / fyc_gemm.  The rule:
+ *  - q' = q * f32(scale * log2e), one f32 rounding; q' and k are split, nothing is rounded to 16 bits before the split;
+ *  - t[i][j] = sum_c hi(q') hi(k) + hi(q') lo(k) + lo(q') hi(k), accumulated in f32: the score in log2 units;
+ *  - p = exp2(t - m) in f32, m a running maximum that may lag the true maximum of the keys seen so far by at most 6 log2 units (as in the 16-bit kernel: p <= 64);
+ *    keys >= n_k have p = 0;
+ *  - p is split unnormalised: O[i][c] = sum_j hi(p) hi(v) + hi(p) lo(v) + lo(p) hi(v) and l[i] = sum_j hi(p) + lo(p), both f32, both scaled by exp2(m_old - m_new)
+ *    when m moves;
+ *  - o = O * (1 / l), stored as f32; with o_accumulate: prev + o_scale * o in f32.
+ * Consequences: with ONE key the output is hi(v) + lo(v) bit for bit (p = l = 1; the sum is an f32 number) - which tells the rule from exact arithmetic.  The pad keys of
+ * vt (n_k <= key < ldvt) must be finite AFTER the split: |x| no larger than the largest bf16 number 3.3895e38 (a larger finite f32 rounds to hi = Inf, and 0 * Inf is
+ * NaN); the engine writes zeros.  Non-finite operands stay inside their (batch, head).  No atomics: two launches give the same bits.
+ * f32_products: any value other than 0 / 1, a non-zero value with a 16-bit dtype, and FYC_PRODUCTS_EXACT with FYC_F32 are refused, before anything that needs a device
+ * or fyc_init.
  */
 typedef struct {
   const void* q; const void* k; const void* vt; void* o;
@@ -183,8 +200,10 @@ typedef struct {
   int32_t kv_batch_div;
   int32_t o_accumulate;
   float scale, o_scale;
-  int32_t dtype;         /* FYC_BF16 / FYC_F16 */
+  int32_t dtype;         /* FYC_BF16 / FYC_F16; FYC_F32 with f32_products = FYC_PRODUCTS_SPLIT_BF16 */
   int32_t q_batch_mod;   /* (version 302) 0 = off */
+  /* (version 307) FYC_PRODUCTS_*: zero with the 16-bit dtypes (today's launches), FYC_PRODUCTS_SPLIT_BF16 with FYC_F32 (see above) */
+  int32_t f32_products;
 } fyc_attn_args;
 int fyc_attention(const fyc_attn_args* a, void* stream);
 
