@@ -1,14 +1,11 @@
 // Host entry of the fused attention: argument validation and dispatch (kernel template: attention_kernel.h;
-// instantiations: attention_small.hip, attention_medium.hip, attention_large.hip).
+// instantiations: attention_small.hip, attention_medium.hip, attention_large.hip; f32 tensors: attention_f32x3.hip).
 #include "attention_kernel.h"
-
-// attention_f32x3.hip: FYC_F32 tensors with f32_products = FYC_PRODUCTS_SPLIT_BF16; fyc_attention has checked the arguments
-int fyc_attn_f32x3_launch(const fyc_attn_args* a, void* stream);
+#include "split_bf16.h"      // FYC_REQUIRE_F32_PRODUCTS
 
 extern "C" int fyc_attention(const fyc_attn_args* a, void* stream) {
   FYC_REQUIRE(a && a->q && a->k && a->vt && a->o, "fyc_attention: null pointer");
-  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->f32_products == FYC_PRODUCTS_SPLIT_BF16, "fyc_attention: f32_products=%d (0 = exact, 1 = split bf16)", a->f32_products);
-  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->dtype == FYC_F32, "fyc_attention: f32_products=%d needs dtype FYC_F32", a->f32_products);
+  FYC_REQUIRE_F32_PRODUCTS("fyc_attention", a);
   FYC_REQUIRE(a->dtype != FYC_F32 || a->f32_products == FYC_PRODUCTS_SPLIT_BF16,
               "fyc_attention: dtype FYC_F32 needs f32_products = FYC_PRODUCTS_SPLIT_BF16 (there is no exact fused f32 kernel: the exact f32 mode uses materialised attention)");
   FYC_REQUIRE(a->dtype == FYC_F32 || a->dtype == FYC_BF16 || a->dtype == FYC_F16, "fyc_attention: bad dtype %d", a->dtype);
@@ -19,14 +16,14 @@ extern "C" int fyc_attention(const fyc_attn_args* a, void* stream) {
   FYC_REQUIRE(a->ldo % 4 == 0, "fyc_attention: ldo must be a multiple of 4");
   FYC_REQUIRE(a->kv_batch_div >= 1, "fyc_attention: kv_batch_div");
   FYC_REQUIRE(a->q_batch_mod >= 0 && a->q_batch_mod <= a->batch, "fyc_attention: q_batch_mod %d (0 .. batch)", a->q_batch_mod);
-  if (a->dtype == FYC_F32) return fyc_attn_f32x3_launch(a, stream);      // attention_f32x3.hip (its QT rule is written there, beside the kernel's budgets)
-  fyca::AttnP p;
+  fyca::AttnP p;      // one fill for every dtype: the kernels cast the element pointers to their type
   p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.vt = (const bf16_t*)a->vt; p.o = (bf16_t*)a->o;
   p.batch = a->batch; p.heads = a->heads; p.n_q = a->n_q; p.n_k = a->n_k; p.d = a->d; p.ldo = a->ldo; p.ldvt = a->ldvt;
   p.kv_batch_div = a->kv_batch_div; p.o_accumulate = a->o_accumulate; p.q_batch_mod = a->q_batch_mod;
   p.sl2e = a->scale * 1.44269504088896340736f; p.o_scale = a->o_scale;
   p.nqb = 0; p.zero = (const char*)g_fyc_zero_page;
   hipStream_t st = (hipStream_t)stream;
+  if (a->dtype == FYC_F32) return fyca::run_f32x3(p, st);      // attention_f32x3.hip (its QT rule is written there, beside the kernel's budgets)
   // Queries per wave = 16 * QT.  More queries amortise the K / V^T fragment reads over more MFMAs but cost registers: at d = 40
   // QT = 4 needs 170 VGPRs (2 waves / SIMD), QT = 3 needs 140 (3 waves / SIMD).  Large problems take QT = 3 (measured,
   // profiles/r02_attention_variants.txt); small ones QT = 2 so that the grid still fills the chip.  tuning key 3 forces QT.

@@ -2,7 +2,7 @@
 // the MFMA orientation of attention_kernel.h - a workgroup of 4 wave64 on 64 QT queries of one (batch, head), K and V^T key tiles global -> LDS by
 // global_load_lds into a 3-deep ring with counted vmcnt waits, S^T = K Q^T so that a lane's 8 exponentiated scores of a 32-key block are the B operand of
 // O^T = V^T P^T - with f32 storage: every operand fragment is split in registers behind its LDS read into hi = RNE_bf16(x) and lo = RNE_bf16(x - hi)
-// (gemm_kernel.h::Mma<f32x3_t>, temporal_attn_f32x3.hip) and every matrix instruction of the 16-bit kernel becomes three, lo hi, hi lo, hi hi.
+// (split_bf16.h: the rule, shared with temporal_attn_f32x3.hip) and every matrix instruction of the 16-bit kernel becomes three, lo hi, hi lo, hi hi.
 //
 // What does not carry over from the 16-bit kernel, and what the budgets decided (resource report and timings: profiles/f32x3_attention.txt):
 //   * no -m in a padding slot of the head dim (that trick rounds m to bf16): t - m is an f32 subtraction;
@@ -13,58 +13,15 @@
 //   * key tiles are 32 keys high for every head dim: an f32 tile is twice the bytes of a 16-bit one, and at 32 keys three ring stages are 48 KB at d = 40,
 //     60 KB at d = 64, 72 KB at d = 80 and 132 KB at d = 160 - two or three workgroups per CU up to d = 80, one above (rp::LdsAttr above 64 KB);
 //   * Q is split once per wave and stays resident as hi + lo; a K or V^T fragment is split once per key block and serves all QT query tiles: QT = 4 is built
-//     up to d = 80 and pays 3 - 4 % at 4096 queries (the dispatch rule and its measurement: fyc_attn_f32x3_launch below);
+//     up to d = 80 and pays 3 - 4 % at 4096 queries (the dispatch rule and its measurement: fyca::run_f32x3 below);
 //   * every lane issues every DMA of a tile (lanes outside the data fetch 16 bytes of the zero page), so the counted wait is a compile-time number.
-#include "row_panel.h"
-
-int fyc_attn_f32x3_launch(const fyc_attn_args* a, void* stream);
+#include "attention_common.h"      // fyca::AttnP (filled by fyc_attention, attention.hip), glds16, wait_vmcnt, RESCALE_THR
+#include "split_bf16.h"            // sb::Split, split8, split8_sum, mma3: the rule
 
 namespace {
 
-struct AttnSplitP {
-  const float* q; const float* k; const float* vt; float* o;
-  int batch, heads, n_q, n_k, d, ldo, ldvt, kv_batch_div, o_accumulate, q_batch_mod;
-  float sl2e, o_scale;   // f32(scale * log2(e))
-  int nqb;               // query blocks per (b, h)
-  const char* zero;
-};
-
-constexpr float RESCALE_THR = 6.0f;   // log2 units, attention_kernel.h: probabilities stay <= 64 between moves of the running max
-
-struct Split { bf16x8 hi, lo; };
-// gemm_kernel.h::Mma<f32x3_t>::split: 8 f32 -> hi and lo bf16x8 (x - hi is exact in f32)
-__device__ __forceinline__ Split split8(f32x4 x0, f32x4 x1) {
-  u32x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float a = e < 2 ? x0[2 * e] : x1[2 * e - 4], b = e < 2 ? x0[2 * e + 1] : x1[2 * e - 3];
-    h[e] = pack_bf16x2(a, b);
-    l[e] = pack_bf16x2(a - __uint_as_float(h[e] << 16), b - __uint_as_float(h[e] & 0xffff0000u));
-  }
-  return {__builtin_bit_cast(bf16x8, h), __builtin_bit_cast(bf16x8, l)};
-}
-// the same, and sum += hi(x) + lo(x) over the 8 values (each sum is an f32 number: lo is a rounding of the f32 number x - hi)
-__device__ __forceinline__ Split split8_sum(f32x4 x0, f32x4 x1, float& sum) {
-  const Split s = split8(x0, x1);
-  const u32x4 h = __builtin_bit_cast(u32x4, s.hi), l = __builtin_bit_cast(u32x4, s.lo);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    sum += __uint_as_float(h[e] << 16) + __uint_as_float(l[e] << 16);
-    sum += __uint_as_float(h[e] & 0xffff0000u) + __uint_as_float(l[e] & 0xffff0000u);
-  }
-  return s;
-}
-// c += hi(w) hi(a) + hi(w) lo(a) + lo(w) hi(a), the small terms first
-__device__ __forceinline__ f32x4 mma3(const Split& w, const Split& a, f32x4 c) {
-  c = rp::mfma(w.lo, a.hi, c);
-  c = rp::mfma(w.hi, a.lo, c);
-  return rp::mfma(w.hi, a.hi, c);
-}
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+using namespace sb;
+using fyca::AttnP, fyca::glds16, fyca::wait_vmcnt, fyca::RESCALE_THR;
 
 // LDS geometry of one ring stage, shared by the kernel and its launcher.  K tile: KB keys x (DP / 4 + 1) 16-byte chunks (4 channels each; the odd pitch
 // spreads the 16 key rows of a fragment read over the banks), directly behind it the V^T tile: DVT * 16 channel rows x 8 chunks (4 keys each), chunk XOR row & 7.
@@ -81,7 +38,7 @@ struct Geo {
 
 // DP32: head dim padded to 32-channel k-steps.  DVT: 16-row blocks of O^T = ceil(d / 16).  QT: 16-query tiles per wave.
 template <int DP32, int DVT, int QT>
-__global__ void __launch_bounds__(256) fyc_attn_f32x3_kernel(const AttnSplitP p) {
+__global__ void __launch_bounds__(256) fyc_attn_f32x3_kernel(const AttnP p) {
   typedef Geo<DP32, DVT> G;
   constexpr int KS = DP32, KB = G::KB, PC = G::PC, K_CHUNKS = G::K_CHUNKS, STAGE = G::STAGE, LOADS = G::LOADS, NS = G::NS;
   static_assert(LOADS <= 15, "the counted wait is an immediate");
@@ -105,9 +62,9 @@ __global__ void __launch_bounds__(256) fyc_attn_f32x3_kernel(const AttnSplitP p)
   const int b = bh / p.heads, h = bh - b * p.heads;
   const int kvb = (b / p.kv_batch_div) * p.heads + h;
   const int bh_q = p.q_batch_mod > 0 ? (b % p.q_batch_mod) * p.heads + h : bh;
-  const float* Q = p.q + (long long)bh_q * p.n_q * p.d;
-  const float* K = p.k + (long long)kvb * p.n_k * p.d;
-  const float* VT = p.vt + (long long)kvb * p.d * p.ldvt;
+  const float* Q = reinterpret_cast<const float*>(p.q) + (long long)bh_q * p.n_q * p.d;
+  const float* K = reinterpret_cast<const float*>(p.k) + (long long)kvb * p.n_k * p.d;
+  const float* VT = reinterpret_cast<const float*>(p.vt) + (long long)kvb * p.d * p.ldvt;
   const char* zero = p.zero;
   const int ntiles = (p.n_k + KB - 1) / KB;
   const int nfull = p.n_k / KB;            // tiles 0 .. nfull-1 hold KB keys
@@ -290,7 +247,7 @@ __global__ void __launch_bounds__(256) fyc_attn_f32x3_kernel(const AttnSplitP p)
     const float inv = 1.0f / l;
     const int query = qbase + qt * 16 + r16;
     if (query >= p.n_q) continue;
-    float* orow = p.o + ((long long)b * p.n_q + query) * p.ldo + h * p.d;
+    float* orow = reinterpret_cast<float*>(p.o) + ((long long)b * p.n_q + query) * p.ldo + h * p.d;
 #pragma unroll
     for (int dv = 0; dv < DVT; ++dv) {
       const int dd = dv * 16 + 4 * g;
@@ -307,7 +264,7 @@ __global__ void __launch_bounds__(256) fyc_attn_f32x3_kernel(const AttnSplitP p)
 }
 
 template <int DP32, int DVT, int QT>
-int launch_k(const AttnSplitP& p0, hipStream_t st) {
+int launch_k(const AttnP& p0, hipStream_t st) {
   constexpr int LDS_BYTES = Geo<DP32, DVT>::LDS_BYTES;
   static_assert(LDS_BYTES <= 160 * 1024, "the ring fits one CU");
   FYC_REQUIRE(rp::lds_fits(LDS_BYTES), "fyc_attention(f32, split products): %d bytes of LDS do not fit this device", LDS_BYTES);
@@ -315,7 +272,7 @@ int launch_k(const AttnSplitP& p0, hipStream_t st) {
     static rp::LdsAttr attr;                          // one per instantiation
     if (int rc = attr.set("fyc_attention(f32, split products)", LDS_BYTES, fyc_attn_f32x3_kernel<DP32, DVT, QT>)) return rc;
   }
-  AttnSplitP p = p0;
+  AttnP p = p0;
   p.nqb = (p.n_q + 64 * QT - 1) / (64 * QT);
   hipLaunchKernelGGL((fyc_attn_f32x3_kernel<DP32, DVT, QT>), dim3((unsigned)(p.batch * p.heads * p.nqb)), dim3(256), LDS_BYTES, st, p);
   FYC_CHECK_LAUNCH("fyc_attention(f32, split products)");
@@ -323,7 +280,7 @@ int launch_k(const AttnSplitP& p0, hipStream_t st) {
 }
 
 template <int DP32, int DVT>
-int launch_q(const AttnSplitP& p, int qt, hipStream_t st) {
+int launch_q(const AttnP& p, int qt, hipStream_t st) {
   if constexpr (DVT <= 5) {      // d <= 80
     if (qt == 4) return launch_k<DP32, DVT, 4>(p, st);
   }
@@ -332,25 +289,18 @@ int launch_q(const AttnSplitP& p, int qt, hipStream_t st) {
 
 }  // namespace
 
-// fyc_attention has checked pointers, sizes, head dim, pitches, kv_batch_div, q_batch_mod and the zero page
-int fyc_attn_f32x3_launch(const fyc_attn_args* a, void* stream) {
-  FYC_REQUIRE(rp::aligned16(a->q, a->k, a->vt, a->o), "fyc_attention: f32_products = FYC_PRODUCTS_SPLIT_BF16 needs 16-byte aligned q, k, vt and o");
-  FYC_REQUIRE((long long)a->d * a->ldvt * 4 < (1ll << 32), "fyc_attention: f32_products = FYC_PRODUCTS_SPLIT_BF16: one head of vt (%d x %d f32) must stay below 4 GiB", a->d, a->ldvt);
-  AttnSplitP p;
-  p.q = (const float*)a->q; p.k = (const float*)a->k; p.vt = (const float*)a->vt; p.o = (float*)a->o;
-  p.batch = a->batch; p.heads = a->heads; p.n_q = a->n_q; p.n_k = a->n_k; p.d = a->d; p.ldo = a->ldo; p.ldvt = a->ldvt;
-  p.kv_batch_div = a->kv_batch_div; p.o_accumulate = a->o_accumulate; p.q_batch_mod = a->q_batch_mod;
-  p.sl2e = a->scale * 1.44269504088896340736f; p.o_scale = a->o_scale;
-  p.nqb = 0; p.zero = (const char*)g_fyc_zero_page;
-  hipStream_t st = (hipStream_t)stream;
+// fyc_attention has checked pointers, sizes, head dim, pitches, kv_batch_div, q_batch_mod and the zero page, and has filled p
+int fyca::run_f32x3(const AttnP& p, hipStream_t st) {
+  FYC_REQUIRE(rp::aligned16(p.q, p.k, p.vt, p.o), "fyc_attention: f32_products = FYC_PRODUCTS_SPLIT_BF16 needs 16-byte aligned q, k, vt and o");
+  FYC_REQUIRE((long long)p.d * p.ldvt * 4 < (1ll << 32), "fyc_attention: f32_products = FYC_PRODUCTS_SPLIT_BF16: one head of vt (%d x %d f32) must stay below 4 GiB", p.d, p.ldvt);
   // Queries per wave = 16 QT.  A K / V^T fragment is read and split once per key block and serves QT query tiles: QT = 4 halves the LDS reads and the split's
   // VALU work per matrix instruction, at 230 - 310 registers against 150 - 224 (d = 40 .. 80).  Measured (profiles/f32x3_attention.txt section 2, the two forced
   // with tuning key 3): at 4096 queries QT = 4 takes 0.96 - 0.97 of QT = 2's time (d = 40 and 64, also where 256-query blocks leave CUs without a workgroup);
   // at 1024 it is between 0.98 (d = 80) and 1.08 (d = 64), at 256 level, at 64 queries 1.39 (three waves of four idle).  Hence QT = 4 from 2048 queries on, up to
   // d = 80 (above, Q and O^T of four tiles do not fit the register file beside the fragments: not built).  Tuning key 3 forces 2 or 4.
-  int qt = (a->d <= 80 && a->n_q >= 2048) ? 4 : 2;
-  if (g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] == 2 || (g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] == 4 && a->d <= 80)) qt = g_fyc_tuning[FYC_TUNE_ATTN_VARIANT];
-  switch ((a->d + 15) / 16) {      // 16-row blocks of O^T -> (k-steps of 32 channels, blocks)
+  int qt = (p.d <= 80 && p.n_q >= 2048) ? 4 : 2;
+  if (g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] == 2 || (g_fyc_tuning[FYC_TUNE_ATTN_VARIANT] == 4 && p.d <= 80)) qt = g_fyc_tuning[FYC_TUNE_ATTN_VARIANT];
+  switch ((p.d + 15) / 16) {      // 16-row blocks of O^T -> (k-steps of 32 channels, blocks)
     case 1: return launch_q<1, 1>(p, qt, st);
     case 2: return launch_q<1, 2>(p, qt, st);
     case 3: return launch_q<2, 3>(p, qt, st);

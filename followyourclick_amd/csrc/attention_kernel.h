@@ -27,18 +27,9 @@
 #pragma once
 #include <type_traits>
 
-#include "fyc_common.h"
+#include "attention_common.h"      // AttnP, glds16, wait_vmcnt, RESCALE_THR
 
 namespace fyca {
-
-struct AttnP {
-  const bf16_t* q; const bf16_t* k; const bf16_t* vt; bf16_t* o;   // 16-bit elements of the kernel's T (bf16 or f16: same pointer arithmetic)
-  int batch, heads, n_q, n_k, d, ldo, ldvt, kv_batch_div, o_accumulate;
-  int q_batch_mod;       // > 0: the q of batch element b is read from b % q_batch_mod (K / V / O stay per b)
-  float sl2e, o_scale;   // scale * log2(e)
-  int nqb;               // query blocks per (b,h)
-  const char* zero;
-};
 
 // 64 x bf16 1.0 (a V^T row of ones), then {1.0, 0 x 7} (the K column of ones): sources of the direct-to-LDS loads
 #define FYC_1 0x3F80
@@ -76,12 +67,6 @@ template <> struct AttnMma<f16_t> {
   }
 };
 
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 #ifndef FYC_ATTN_BUILTIN_ISSUE
 // The (up to) four exec-masked DMAs of a full K / V^T tile as ONE statement: the lane masks are computed once per kernel (SGPR pairs), a DMA
 // whose mask is empty in this wave is branched over (so that the counted vmcnt waits stay exact), M0 and EXEC leave as they came.  The
@@ -116,8 +101,6 @@ __device__ __forceinline__ void dma4_masked(unsigned long long m0_, unsigned lon
 #else
 #define FYC_ATTN_PRIO(x) do { } while (0)
 #endif
-
-constexpr float RESCALE_THR = 6.0f;   // log2 units: probabilities stay <= 64 between moves of the running max
 
 // max over the 4 lane quads that share a query column: xor 16 inside each 32-lane half (ds_swizzle bit mode, no LDS
 // traffic), then across the halves (v_permlane32_swap)

@@ -17,20 +17,10 @@
 // frame before the score product - x'[c] = x[c] cos[f][c mod h] -/+ x[c +/- h] sin[f][c mod h], h = d/2, the
 // rotate_half pairing of the reference's RoPE (rope.py:102-116) - in f32 on the loaded values and rounded
 // once to the operand type.  V is untouched.  The ROPE = false instantiations are the kernels without it.
-#include "row_panel.h"
-
-// temporal_attn_f32x3.hip: FYC_F32 tensors with f32_products = FYC_PRODUCTS_SPLIT_BF16; fyc_temporal_attention has checked the arguments
-int fyc_tattn_f32x3_launch(const fyc_tattn_args* a, void* stream);
+#include "split_bf16.h"      // rp::mfma (row_panel.h), FYC_REQUIRE_F32_PRODUCTS
+#include "temporal_attn.h"   // TAttnP, fyc_tattn_f32x3_launch
 
 namespace {
-
-struct TAttnP {
-  const void* qkv; void* o;
-  int clips, frames, pixels, heads, d;
-  float scale;
-  const char* zero;
-  const float* rope_cos; const float* rope_sin;
-};
 
 // rotate_half on the 8 head channels dd .. dd+7 of one frame's q or k row (`row` = the head's first channel of that row).  h = d/2 is
 // a multiple of 4, so each 4-channel run of the fragment lies wholly below or above h and its partner run starts h channels away: at
@@ -300,8 +290,7 @@ int launch_d(const TAttnP& p, hipStream_t st) {
 
 extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
   FYC_REQUIRE(a && a->qkv && a->o, "fyc_temporal_attention: null pointer");
-  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->f32_products == FYC_PRODUCTS_SPLIT_BF16, "fyc_temporal_attention: f32_products=%d (0 = exact, 1 = split bf16)", a->f32_products);
-  FYC_REQUIRE(a->f32_products == FYC_PRODUCTS_EXACT || a->dtype == FYC_F32, "fyc_temporal_attention: f32_products=%d needs dtype FYC_F32", a->f32_products);
+  FYC_REQUIRE_F32_PRODUCTS("fyc_temporal_attention", a);
   FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_temporal_attention: fyc_init() not called");
   FYC_REQUIRE(a->clips > 0 && a->frames > 0 && a->pixels > 0 && a->heads > 0, "fyc_temporal_attention: bad sizes");
   FYC_REQUIRE(a->frames <= 64, "fyc_temporal_attention: frames=%d > 64 unsupported", a->frames);
@@ -315,7 +304,7 @@ extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
   const bool rope = a->rope_cos != nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (a->dtype == FYC_F32) {
-    if (a->f32_products == FYC_PRODUCTS_SPLIT_BF16) return fyc_tattn_f32x3_launch(a, stream);      // temporal_attn_f32x3.hip
+    if (a->f32_products == FYC_PRODUCTS_SPLIT_BF16) return fyc_tattn_f32x3_launch(p, st);      // temporal_attn_f32x3.hip
     const long long total = (long long)p.clips * p.pixels * p.heads * p.frames;
     const dim3 grid((unsigned)((total + 255) / 256));
     if (rope) hipLaunchKernelGGL(tattn_f32_kernel<true>, grid, dim3(256), 0, st, p);

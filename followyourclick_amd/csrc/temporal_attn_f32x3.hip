@@ -2,8 +2,8 @@
 // work split of temporal_attn.hip's 16-bit kernel - one wave64 per (clip, pixel, head) task, S^T = K Q^T and O^T = V^T P^T on
 // v_mfma_f32_16x16x32_bf16, the softmax in registers, -inf for the key frames outside the problem, the zero page for the lanes outside it - with
 // f32 storage: a lane's eight head channels are two 16-byte loads, every operand fragment is split in registers into hi = RNE_bf16(x) and
-// lo = RNE_bf16(x - hi), and every matrix instruction of the 16-bit kernel becomes three, lo hi, hi lo, hi hi, in the order of
-// gemm_kernel.h::Mma<f32x3_t>::mma (the two small terms meet the running sum first).  RoPE rotates q and k in f32 before the split.
+// lo = RNE_bf16(x - hi), and every matrix instruction of the 16-bit kernel becomes three, lo hi, hi lo, hi hi (split_bf16.h: the rule, shared
+// with attention_f32x3.hip; the two small terms meet the running sum first).  RoPE rotates q and k in f32 before the split.
 //
 // What the budgets decided (resource report: profiles/f32x3_tattn.txt):
 //   K stays resident as hi + lo for all key tiles (160 registers at F = 64, d = 160); the Q fragment of a k-step is loaded, rotated and split
@@ -13,36 +13,12 @@
 //   frames 4g .. 4g+3 of a channel instead of eight 4-byte gathers, and re-reading it for every query tile (NFT times) is cheap.  Row pitch
 //   16 NFT + 4 floats: the 16 channels of a 16-byte read phase land on 16 distinct bank quads.  4 tasks x DP x (16 NFT + 4) x 4 bytes is at
 //   most 136 KB for every family but (DP 160, NFT 4) = 170 KB: that one runs two tasks per 128-thread block (85 KB).
-#include "row_panel.h"
+#include "split_bf16.h"      // sb::Split, split8, mma3: the rule
+#include "temporal_attn.h"   // TAttnP (filled by fyc_temporal_attention, temporal_attn.hip)
 
 namespace {
 
-struct TSplitP {
-  const float* qkv; float* o;
-  int clips, frames, pixels, heads, d;
-  float scale;
-  const float* zero;
-  const float* rope_cos; const float* rope_sin;
-};
-
-struct Split { bf16x8 hi, lo; };
-// gemm_kernel.h::Mma<f32x3_t>::split: 8 f32 -> hi and lo bf16x8 (x - hi is exact in f32)
-__device__ __forceinline__ Split split8(f32x4 x0, f32x4 x1) {
-  u32x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float a = e < 2 ? x0[2 * e] : x1[2 * e - 4], b = e < 2 ? x0[2 * e + 1] : x1[2 * e - 3];
-    h[e] = pack_bf16x2(a, b);
-    l[e] = pack_bf16x2(a - __uint_as_float(h[e] << 16), b - __uint_as_float(h[e] & 0xffff0000u));
-  }
-  return {__builtin_bit_cast(bf16x8, h), __builtin_bit_cast(bf16x8, l)};
-}
-// c += hi(w) hi(a) + hi(w) lo(a) + lo(w) hi(a), the small terms first
-__device__ __forceinline__ f32x4 mma3(const Split& w, const Split& a, f32x4 c) {
-  c = rp::mfma(w.lo, a.hi, c);
-  c = rp::mfma(w.hi, a.lo, c);
-  return rp::mfma(w.hi, a.hi, c);
-}
+using namespace sb;
 
 // the 8 head channels dd .. dd+7 of one frame's q or k row (`row` = the head's first channel of that row), rotated (rotate_half, include/fyc.h:
 // two rounded products and a rounded sum in f32 - the library is built with -ffp-contract=off) and split.  h = d/2 is a multiple of 4: each
@@ -69,7 +45,7 @@ __device__ __forceinline__ Split load_qk(const float* row, int dd, int hh, const
 }
 
 template <int DP, int DVT, int NFT, int TPB, bool ROPE>
-__global__ void __launch_bounds__(64 * TPB) tattn_f32x3_kernel(const TSplitP p) {
+__global__ void __launch_bounds__(64 * TPB) tattn_f32x3_kernel(const TAttnP p) {
   constexpr int KS = DP / 32;
   constexpr int NP = (NFT + 1) / 2;      // k = 32 MFMAs per output tile of P V: one per pair of 16-frame key tiles
   constexpr int PITCH = NFT * 16 + 4;    // floats per channel row of the V^T tile
@@ -83,9 +59,9 @@ __global__ void __launch_bounds__(64 * TPB) tattn_f32x3_kernel(const TSplitP p) 
   const long long bp = task / p.heads;
   const int pix = (int)(bp % p.pixels), b = (int)(bp / p.pixels);
   const int F = p.frames, C = p.heads * p.d, ld = 3 * C;
-  const float* base = p.qkv + ((long long)b * F * p.pixels + pix) * ld + h * p.d;
+  const float* base = reinterpret_cast<const float*>(p.qkv) + ((long long)b * F * p.pixels + pix) * ld + h * p.d;
   const long long fstride = (long long)p.pixels * ld;  // elements between consecutive frames of a pixel
-  const float* zero = p.zero;
+  const float* zero = reinterpret_cast<const float*>(p.zero);
   const int hh = p.d >> 1;
 
   // K fragments, resident: lane (frame = 16*tile + r16, quad g) holds 8 consecutive head channels as hi and lo
@@ -120,7 +96,7 @@ __global__ void __launch_bounds__(64 * TPB) tattn_f32x3_kernel(const TSplitP p) 
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // same wave wrote and reads: LDS ops of a wave complete in order
 
   const float sl2e = p.scale * 1.44269504088896340736f;
-  float* obase = p.o + ((long long)b * F * p.pixels + pix) * C + h * p.d;
+  float* obase = reinterpret_cast<float*>(p.o) + ((long long)b * F * p.pixels + pix) * C + h * p.d;
   const long long ofstride = (long long)p.pixels * C;
 
 #pragma unroll
@@ -187,7 +163,7 @@ __global__ void __launch_bounds__(64 * TPB) tattn_f32x3_kernel(const TSplitP p) 
 }
 
 template <int DP, int DVT, int NFT, bool ROPE>
-int launch_k(const TSplitP& p, hipStream_t st) {
+int launch_k(const TAttnP& p, hipStream_t st) {
   constexpr int PITCH = NFT * 16 + 4;
   constexpr int TPB = 4 * DP * PITCH * 4 <= 160 * 1024 ? 4 : 2;      // tasks per block: what the 160 KiB of a CU hold
   constexpr int LDS_BYTES = TPB * DP * PITCH * 4;
@@ -204,7 +180,7 @@ int launch_k(const TSplitP& p, hipStream_t st) {
 }
 
 template <int DP, int DVT, bool ROPE>
-int launch_t(const TSplitP& p, hipStream_t st) {
+int launch_t(const TAttnP& p, hipStream_t st) {
   if (p.frames <= 16) return launch_k<DP, DVT, 1, ROPE>(p, st);
   if (p.frames <= 32) return launch_k<DP, DVT, 2, ROPE>(p, st);
   if (p.frames <= 48) return launch_k<DP, DVT, 3, ROPE>(p, st);
@@ -212,7 +188,7 @@ int launch_t(const TSplitP& p, hipStream_t st) {
 }
 
 template <bool ROPE>
-int launch_d(const TSplitP& p, hipStream_t st) {      // the head-dim families of temporal_attn.hip
+int launch_d(const TAttnP& p, hipStream_t st) {      // the head-dim families of temporal_attn.hip
   if (p.d <= 32) return launch_t<32, 2, ROPE>(p, st);
   if (p.d <= 48) return launch_t<64, 3, ROPE>(p, st);
   if (p.d <= 64) return launch_t<64, 4, ROPE>(p, st);
@@ -224,14 +200,8 @@ int launch_d(const TSplitP& p, hipStream_t st) {      // the head-dim families o
 
 }  // namespace
 
-// fyc_temporal_attention has checked sizes, head dim, frames <= 64, the tables and the zero page
-int fyc_tattn_f32x3_launch(const fyc_tattn_args* a, void* stream) {
-  FYC_REQUIRE(rp::aligned16(a->qkv, a->o), "fyc_temporal_attention: f32_products = FYC_PRODUCTS_SPLIT_BF16 needs 16-byte aligned qkv and o");
-  TSplitP p;
-  p.qkv = (const float*)a->qkv; p.o = (float*)a->o;
-  p.clips = a->clips; p.frames = a->frames; p.pixels = a->pixels; p.heads = a->heads; p.d = a->d;
-  p.scale = a->scale; p.zero = (const float*)g_fyc_zero_page;
-  p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
-  hipStream_t st = (hipStream_t)stream;
-  return a->rope_cos != nullptr ? launch_d<true>(p, st) : launch_d<false>(p, st);
+// fyc_temporal_attention has checked sizes, head dim, frames <= 64, the tables and the zero page, and has filled p
+int fyc_tattn_f32x3_launch(const TAttnP& p, hipStream_t st) {
+  FYC_REQUIRE(rp::aligned16(p.qkv, p.o), "fyc_temporal_attention: f32_products = FYC_PRODUCTS_SPLIT_BF16 needs 16-byte aligned qkv and o");
+  return p.rope_cos != nullptr ? launch_d<true>(p, st) : launch_d<false>(p, st);
 }

@@ -24,7 +24,25 @@ Tensor = torch.Tensor
 _DTYPE_CODES = {torch.bfloat16: L.FYC_BF16, torch.float16: L.FYC_F16, torch.float32: L.FYC_F32}
 
 
-_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # HipOps.f32_products -> fyc_gemm_args.f32_products, fyc_tattn_args.f32_products, fyc_attn_args.f32_products (f32 attention: "split" only)
+_PRODUCTS = {"exact": L.PRODUCTS_EXACT, "split": L.PRODUCTS_SPLIT_BF16}      # the words of HipOps.f32_products and of the `products` keyword -> the f32_products field (resolve_f32_products)
+
+
+def resolve_f32_products(op: str, dtype: torch.dtype, products: Optional[str], instance_mode: str, *, fused_exact: bool = True) -> int:
+    """The f32_products field of fyc_gemm_args / fyc_tattn_args / fyc_attn_args (include/fyc.h) for one call of entry point `op` on activations of `dtype`:
+    the `products` keyword, or with None the HipOps instance's mode, on f32 tensors; 0 on 16-bit tensors whatever the mode.  An unknown word raises ValueError,
+    "split" with 16-bit tensors TypeError.  fused_exact=False (attention): there is no fused kernel with exact f32 products, f32 tensors that resolve to
+    "exact" raise FycError.  A pure function: the emulators of tests/ take the same decision from it."""
+    if products is not None and products not in _PRODUCTS:
+        raise ValueError(f"{op}: products {products!r}: expected None, 'exact' or 'split'")
+    if dtype != torch.float32:
+        if products == "split":
+            raise TypeError(f"{op}: products='split' needs float32 tensors (got {dtype})")
+        return L.PRODUCTS_EXACT
+    mode = instance_mode if products is None else products
+    if mode == "exact" and not fused_exact:
+        raise L.FycError(f"{op}: float32 tensors run fused with products='split' only; with exact f32 products use the materialised path "
+                         "(gemm, softmax_rows, gemm: engine/unet3d.py::_attend)")
+    return _PRODUCTS[mode]
 
 
 def _dtc(dtype: torch.dtype) -> int:
@@ -70,7 +88,7 @@ class HipOps:
         self._ws_need = {}           # (shape, flags) -> split-K scratch bytes (fyc_gemm_workspace_bytes), see gemm()
         self._q_cache = {}           # host-side layout queries (row parts, split bytes, statistics layout) per shape
         self._inited_dev = None
-        self.f32_products = default_f32_products()      # "exact" | "split": the product rule of gemm() and temporal_attention() on f32 tensors (set_f32_products)
+        self.f32_products = default_f32_products()      # "exact" | "split": the product rule of gemm(), attention() and temporal_attention() on f32 tensors (set_f32_products, resolve_f32_products)
 
     # -- library ---------------------------------------------------------------------------
     def ensure_init(self, device: torch.device) -> None:
@@ -134,17 +152,13 @@ class HipOps:
              products: Optional[str] = None) -> None:
         """products: None = this instance's f32_products, else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors raises)"""
         self.ensure_init(a.device)
-        if products is not None and products not in _PRODUCTS:
-            raise ValueError(f"gemm: products {products!r}: expected None, 'exact' or 'split'")
-        if a.dtype != torch.float32 and products == "split":
-            raise TypeError(f"gemm: products='split' needs float32 tensors (got {a.dtype})")
+        f32_products = resolve_f32_products("gemm", a.dtype, products, self.f32_products)
         g = self._gemm_args(a, w, out, M=M, N=N, K=K, lda=lda, ldw=ldw, ldo=ldo, bias=bias, rowbias=rowbias, rows_per_batch=rows_per_batch,
                             residual=residual, ldr=ldr, ldrb=ldrb, out_scale=out_scale, epilogue=epilogue, mode=mode, conv=conv, batch=batch,
                             stride_a=stride_a, stride_w=stride_w, stride_o=stride_o, heads=heads, tile=tile, a2=a2, k_split=k_split,
                             lda2=lda2, act=act, ln_stats=ln_stats, ln_colsum=ln_colsum, ln_nparts=ln_nparts, ln_eps=ln_eps,
                             chan_parts=chan_parts, cs_rows=cs_rows, row_parts=row_parts, row_nparts=row_nparts)
-        if a.dtype == torch.float32:
-            g.f32_products = _PRODUCTS[self.f32_products if products is None else products]
+        g.f32_products = f32_products
         # split-K scratch (small M, long K): the decision depends on the shape and the flags below only - cached, so that the ~300
         # GEMM launches of a DDIM step do not each pay a second ctypes call.  One grown-on-demand buffer: all work of a process is on
         # ONE stream (the engine's), a second stream would need its own HipOps.
@@ -242,21 +256,13 @@ class HipOps:
         products: None = this instance's f32_products (the switch gemm() reads), else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors
         raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode).  f32 tensors run the fused kernel with split-bf16 products
         only (include/fyc.h): a resolved "exact" raises - the exact f32 mode is the materialised sequence gemm / softmax_rows / gemm (engine/unet3d.py::_attend)"""
-        if products is not None and products not in _PRODUCTS:
-            raise ValueError(f"attention: products {products!r}: expected None, 'exact' or 'split'")
-        if q.dtype != torch.float32 and products == "split":
-            raise TypeError(f"attention: products='split' needs float32 tensors (got {q.dtype})")
-        if q.dtype == torch.float32 and (self.f32_products if products is None else products) == "exact":
-            raise L.FycError("attention: float32 tensors run fused with products='split' only; with exact f32 products use the materialised path "
-                             "(gemm, softmax_rows, gemm: engine/unet3d.py::_attend)")
+        f32_products = resolve_f32_products("attention", q.dtype, products, self.f32_products, fused_exact=False)
         self.ensure_init(q.device)
         a = L.AttnArgs()
         a.q, a.k, a.vt, a.o = _p(q), _p(k), _p(vt), _p(o)
         a.batch, a.heads, a.n_q, a.n_k, a.d, a.ldo, a.ldvt = batch, heads, n_q, n_k, d, ldo, ldvt
         a.kv_batch_div, a.o_accumulate, a.scale, a.o_scale, a.dtype = kv_batch_div, int(accumulate), scale, o_scale, _dt(q)
-        a.q_batch_mod = q_batch_mod
-        if q.dtype == torch.float32:
-            a.f32_products = L.PRODUCTS_SPLIT_BF16
+        a.q_batch_mod, a.f32_products = q_batch_mod, f32_products
         self._call("fyc_attention", a)
 
     def attention_q_batch_mod_supported(self) -> bool:
@@ -277,10 +283,7 @@ class HipOps:
         """rope = (cos, sin): f32 device tables [frames][d/2]; q and k are rotated per frame before the score product (include/fyc.h).
         products: None = this instance's f32_products (the switch gemm() reads), else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors
         raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode)"""
-        if products is not None and products not in _PRODUCTS:
-            raise ValueError(f"temporal_attention: products {products!r}: expected None, 'exact' or 'split'")
-        if qkv.dtype != torch.float32 and products == "split":
-            raise TypeError(f"temporal_attention: products='split' needs float32 tensors (got {qkv.dtype})")
+        f32_products = resolve_f32_products("temporal_attention", qkv.dtype, products, self.f32_products)
         self.ensure_init(qkv.device)
         a = L.TAttnArgs()
         a.qkv, a.o, a.clips, a.frames, a.pixels, a.heads, a.d, a.scale, a.dtype = (_p(qkv), _p(o), clips, frames, pixels,
@@ -291,8 +294,7 @@ class HipOps:
                 if t.dtype != torch.float32 or not t.is_contiguous() or t.device != qkv.device or tuple(t.shape) != (frames, d // 2):
                     raise ValueError(f"temporal_attention: rope tables must be contiguous f32 [{frames}][{d // 2}] tensors on {qkv.device}")
             a.rope_cos, a.rope_sin = cos.data_ptr(), sin.data_ptr()
-        if qkv.dtype == torch.float32:
-            a.f32_products = _PRODUCTS[self.f32_products if products is None else products]
+        a.f32_products = f32_products
         self._call("fyc_temporal_attention", a)
 
     def _tblock_args(self, x, out, w_qkv, colsum, bias, pe_bias, w_out, b_out, clips, frames, pixels, heads, d, scale, eps):

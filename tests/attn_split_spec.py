@@ -2,7 +2,7 @@
 HipOps.attention(products="split")), the cases of tests/test_attn_split_gpu.py as data, and the per-element bound they are judged by.  A helper, not a test
 module; no GPU is touched here.
 
-The rule, with hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) (tests/f32x3_spec.py::split_bf16):
+The rule, with hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) (tests/f32x3_spec.py: split_bf16, and split_product for the three-term products below):
   * q' = q * f32(scale * log2e), one f32 rounding; q' and k are split, nothing is rounded to 16 bits before the split;
   * t[i][j] = sum_c hi(q') hi(k) + hi(q') lo(k) + lo(q') hi(k) in f32: the score in log2 units;
   * p = exp2(t - m) in f32; m is the row maximum, or (lag > 0) a value up to RESCALE_THR = 6 log2 units below it: where the kernel's running maximum ends up depends
@@ -10,15 +10,15 @@ The rule, with hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) (tests/f32x3_spe
   * p is split UNNORMALISED: O[i][c] = sum_j hi(p) hi(v) + hi(p) lo(v) + lo(p) hi(v), l[i] = sum_j hi(p) + lo(p), both f32;
   * o = O * (1 / l) stored as f32; with accumulate: prev + o_scale * o in f32.
 
-The bound, against the f64 attention of the UNSPLIT operands (kernel_compare.softmax_bound_terms: plain f64, no rounding of the weights), constant 1:
-    |got - ref| <= ulp_f32(ref) + rest + (2^-15 + 2^-17) (w @ |v|) + 6 ln2 2^-24 (w @ |v| + |o|)
-  * rest = softmax_bound_terms(dtype="f32", kind="flash", dq = 2^-16 |q|, dk = 2^-16 |k|): the bound of an f32 flash evaluation (weights unnormalised before l, so
+The bound, against the f64 attention of the UNSPLIT operands (kernel_compare.softmax_bound_terms: plain f64, no rounding of the weights), constant 1, with
+f32x3_spec's PRODUCT = 2^-15, OPERAND = 2^-16 and REMAINDER = 2^-17 (derived in its docstring):
+    |got - ref| <= ulp_f32(ref) + rest + (PRODUCT + REMAINDER) (w @ |v|) + 6 ln2 2^-24 (w @ |v| + |o|)
+  * rest = softmax_bound_terms(dtype="f32", kind="flash", dq = OPERAND |q|, dk = OPERAND |k|): the bound of an f32 flash evaluation (weights unnormalised before l, so
     their error moves the output only along v_j - o; (d + 8) 2^-24 on the score sum, 4 u + 2 u |s - max| on the exponential, (n_k + 8) 2^-24 on the P V sum and the
     epilogue) whose q and k are uncertain by dq and dk.  The split score product is an f32 sum of 3 d exact products that is off from q'.k by at most
-    2^-15 sum |q'||k| (f32x3_spec's docstring: 2^-17 + 2^-17 for the two remainders, 2^-16 for the dropped lo lo product), and dq.|k| + |q|.dk + dq.dk >= 2^-15 sum |q||k|
-    charges exactly that.  The f32 roundings of q' = q sl2e and of sl2e itself are two of the "+ 8".
-  * 2^-15 (w @ |v|): the three-term P V products, as for the score.
-  * 2^-17 (w @ |v|): l is the sum of hi(p) + lo(p), each off from the p that the exponential produced by at most 2^-17 p: the normalisation is off by that much.
+    PRODUCT sum |q'||k|, and dq.|k| + |q|.dk + dq.dk >= PRODUCT sum |q||k| charges exactly that.  The f32 roundings of q' = q sl2e and of sl2e itself are two of the "+ 8".
+  * PRODUCT (w @ |v|): the three-term P V products, as for the score.
+  * REMAINDER (w @ |v|): l is the sum of hi(p) + lo(p), each off from the p that the exponential produced by at most REMAINDER p: the normalisation is off by that much.
   * 6 ln2 2^-24 (w @ |v| + |o|), added here, not fitted: softmax_bound_terms charges the rounding of the subtraction in exp2(t - m) as 2 u |s - max| for m = the TRUE
     maximum.  The kernel's m may lag it by up to RESCALE_THR = 6 log2 units, so |t - m| is up to 6 larger and the rounded difference is off by up to 6 u more
     log2 units: a relative 6 ln2 u on a weight, different from key to key, so it does not cancel in the normalisation; sum_j w_j e_j (v_j - o) <= max |e| (w @ |v| + |o|).
@@ -47,14 +47,15 @@ import numpy as np
 import torch
 
 import attention_cases as A
+import f32x3_spec as X
 import kernel_compare as KC
 from emu_ops import EmuOps, _flat, _strided
-from f32x3_spec import split_bf16
+from followyourclick_amd.ops import resolve_f32_products
 
 RTOL = A.RTOL_TEMPORAL["f32"]
 RESCALE_THR = 6.0
 BF16_MAX = float(torch.finfo(torch.bfloat16).max)
-DEFECTS = ("drop_q_lok", "drop_lop_v")
+DEFECTS = X.ATTN_DEFECTS
 P_IS_ONE = "p = 1 on the only / the selected key (no lo half), and the score product decides nothing"
 
 # rel-L2 of emulate(c) (lag 0) against the f64 reference on the group-D cases, computed on the CPU (tests/test_attn_split.py::test_group_d_tolerances_are_the_recorded_ones)
@@ -98,7 +99,7 @@ def by_group(*groups):
 
 
 def effective_qt(c):
-    """attention_f32x3.hip: `int qt = (a->d <= 80 && a->n_q >= 2048) ? 4 : 2;` then tuning key 3 if it is 2, or 4 with d <= 80"""
+    """attention_f32x3.hip: `int qt = (p.d <= 80 && p.n_q >= 2048) ? 4 : 2;` then tuning key 3 if it is 2, or 4 with d <= 80"""
     qt = 4 if (c.d <= 80 and c.n_q >= 2048) else 2
     if c.qt == 2 or (c.qt == 4 and c.d <= 80):
         qt = c.qt
@@ -106,7 +107,7 @@ def effective_qt(c):
 
 
 def split_traits(c):
-    dvt = (c.d + 15) // 16                              # switch ((a->d + 15) / 16): 16-row blocks of O^T
+    dvt = (c.d + 15) // 16                              # switch ((p.d + 15) / 16): 16-row blocks of O^T
     dp32 = (dvt + 1) // 2                               # case 1, 2 -> 1; 3, 4 -> 2; 5, 6 -> 3; 7, 8 -> 4; 9, 10 -> 5 k-steps of 32 channels
     qt = effective_qt(c)
     loads = (32 * (dp32 * 8 + 1) + dvt * 128 + 255) // 256      # Geo::LOADS
@@ -132,19 +133,12 @@ def split_flash(q, k, v, *, scale, lag=0.0, defect=None):
     """the rule on q [..][n_q][d], k, v [..][n_k][d] f32 -> o f32 [..][n_q][d] (before accumulate)"""
     assert q.dtype == k.dtype == v.dtype == torch.float32
     sl2e = float(np.float32(scale) * np.float32(1.44269504088896340736))
-    (qh, ql), (kh, kl), (vh, vl) = split_bf16(q * sl2e), split_bf16(k), split_bf16(v)
-    kht, klt = kh.transpose(-1, -2), kl.transpose(-1, -2)
-    t = ql @ kht                                          # the small terms first, as the kernel's matrix instructions add them
-    if defect != "drop_q_lok":
-        t = qh @ klt + t
-    t = t + qh @ kht
+    drop_qk, drop_pv = X.ATTN_DROPS.get(defect, (None, None))
+    t = X.split_product(q * sl2e, k.transpose(-1, -2), drop=drop_qk)
     m = t[..., :32].max(dim=-1, keepdim=True).values if defect == "freeze_max" else t.max(dim=-1, keepdim=True).values - lag
-    ph, pl = split_bf16(torch.exp2(t - m))
-    o = ph @ vl
-    if defect != "drop_lop_v":
-        o = o + pl @ vh
-    o = o + ph @ vh
-    return o * (1.0 / (ph + pl).sum(dim=-1, keepdim=True))
+    p = torch.exp2(t - m)
+    ph, pl = X.split_bf16(p)
+    return X.split_product(p, v, drop=drop_pv) * (1.0 / (ph + pl).sum(dim=-1, keepdim=True))
 
 
 class SplitAttnEmuOps(EmuOps):
@@ -156,17 +150,12 @@ class SplitAttnEmuOps(EmuOps):
 
     def attention(self, q, k, vt, o, *, batch, heads, n_q, n_k, d, ldo, ldvt, scale, kv_batch_div=1, accumulate=False, o_scale=1.0, q_batch_mod=0, products=None,
                   defect=None, lag=0.0):
-        if products not in (None, "exact", "split"):
-            raise ValueError(f"attention: products {products!r}: expected None, 'exact' or 'split'")
-        if q.dtype != torch.float32 and products == "split":
-            raise TypeError(f"attention: products='split' needs float32 tensors (got {q.dtype})")
+        resolve_f32_products("attention", q.dtype, products, self.f32_products, fused_exact=False)      # the refusals; what is left: 16-bit tensors, or f32 and "split"
         qB = q_batch_mod or batch
         Q = _flat(q)[: qB * heads * n_q * d].reshape(qB, heads, n_q, d)[torch.arange(batch) % qB]
         if q.dtype != torch.float32:
             return super().attention(Q.contiguous(), k, vt, o, batch=batch, heads=heads, n_q=n_q, n_k=n_k, d=d, ldo=ldo, ldvt=ldvt, scale=scale, kv_batch_div=kv_batch_div,
                                      accumulate=accumulate, o_scale=o_scale)
-        if (self.f32_products if products is None else products) == "exact":
-            raise RuntimeError("attention: float32 tensors run fused with products='split' only; with exact f32 products use the materialised path")
         kvB = (batch + kv_batch_div - 1) // kv_batch_div
         idx = torch.arange(batch) // kv_batch_div
         K = _flat(k)[: kvB * heads * n_k * d].reshape(kvB, heads, n_k, d)[idx]
@@ -203,9 +192,9 @@ def reference(c):
         for h in range(c.H):
             kv = A.kv_of(c, b)
             q, k, v = ops.q_full[A.q_of(c, b), h].double(), ops.k[kv, h].double(), ops.vt[kv, h, :, : c.n_k].double().T.contiguous()
-            ob, rb, w = KC.softmax_bound_terms(q, k, v, scale=c.scale, dtype="f32", kind="flash", dq=2.0 ** -16 * q.abs(), dk=2.0 ** -16 * k.abs())
+            ob, rb, w = KC.softmax_bound_terms(q, k, v, scale=c.scale, dtype="f32", kind="flash", dq=X.OPERAND * q.abs(), dk=X.OPERAND * k.abs())
             wv = w @ v.abs()
-            o[b, :, h], rest[b, :, h] = ob, rb + (2.0 ** -15 + 2.0 ** -17) * wv + RESCALE_THR * KC.LN2 * 2.0 ** -24 * (wv + ob.abs())
+            o[b, :, h], rest[b, :, h] = ob, rb + (X.PRODUCT + X.REMAINDER) * wv + RESCALE_THR * KC.LN2 * 2.0 ** -24 * (wv + ob.abs())
     o, rest = o.reshape(c.rows, c.cols), rest.reshape(c.rows, c.cols)
     ref = ops.buf.clone()
     if c.accumulate:
@@ -230,8 +219,8 @@ def materialised_bound(c):
         for h in range(c.H):
             kv = A.kv_of(c, b)
             q, k, v = ops.q_full[A.q_of(c, b), h].double(), ops.k[kv, h].double(), ops.vt[kv, h, :, : c.n_k].double().T.contiguous()
-            o[b, :, h], rb, w = KC.softmax_bound_terms(q, k, v, scale=c.scale, dtype="f32", kind="temporal", dq=2.0 ** -16 * q.abs(), dk=2.0 ** -16 * k.abs())
-            rest[b, :, h] = rb + 2.0 ** -15 * (w @ v.abs())
+            o[b, :, h], rb, w = KC.softmax_bound_terms(q, k, v, scale=c.scale, dtype="f32", kind="temporal", dq=X.OPERAND * q.abs(), dk=X.OPERAND * k.abs())
+            rest[b, :, h] = rb + X.PRODUCT * (w @ v.abs())
     o, rest = o.reshape(c.rows, c.cols), rest.reshape(c.rows, c.cols)
     if c.accumulate:
         prev = A.window(c, ops.buf).double()
@@ -251,7 +240,7 @@ def hi_plus_lo_of_v(c, ops):
     """what a one-key problem returns in the split rule, [rows][cols]: hi(v) + lo(v) of the only key, for every query; and v itself"""
     assert c.n_k == 1 and not c.accumulate
     v = torch.stack([ops.vt[A.kv_of(c, b), :, :, 0] for b in range(c.B)])[:, None].expand(c.B, c.n_q, c.H, c.d).reshape(c.rows, c.cols).contiguous()
-    hi, lo = split_bf16(v)
+    hi, lo = X.split_bf16(v)
     return hi + lo, v
 
 

@@ -1,9 +1,13 @@
-"""Torch specification of fyc_gemm's split-bf16 product rule for f32 operands (include/fyc.h: f32_products = FYC_PRODUCTS_SPLIT_BF16), the GPU
-cases of tests/test_f32x3_gpu.py as data, and the per-element bound they are judged by.  A helper, not a test module; no GPU is touched here.
+"""Torch specification of the split-bf16 product rule of the f32x3 tier (include/fyc.h: f32_products = FYC_PRODUCTS_SPLIT_BF16) - the one home of the rule in
+torch: split_bf16, split_product and the three error constants below serve fyc_gemm's specification here and those of fyc_temporal_attention
+(tests/tattn_split_spec.py) and fyc_attention (tests/attn_split_spec.py) - then fyc_gemm's GPU cases (tests/test_f32x3_gpu.py) as data and the per-element bound
+they are judged by, and the HipOps recorder of the CPU tests of the three entry points.  A helper, not a test module; no GPU is touched here.
 
 The rule: hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) - the subtraction is exact in f32 - and
     acc += hi(a) hi(w) + hi(a) lo(w) + lo(a) hi(w)
-in f32 (the three bf16 x bf16 products are exact in f32); lo(a) lo(w) is dropped.
+in f32 (the three bf16 x bf16 products are exact in f32); lo(a) lo(w) is dropped.  The kernels' statements of it: csrc/split_bf16.h, csrc/gemm_kernel.h::Mma<f32x3_t>.
+The constants the derivation below arrives at: REMAINDER = 2^-17 (|x - hi - lo| / |x|), PRODUCT = 2^-15 (one three-term product against a w), and
+OPERAND = 2^-16 = PRODUCT / 2, the uncertainty charged to EACH of two operands so that their product is charged PRODUCT (the attention specs' dq, dk).
 
 The bound, against the f64 reference of the UNSPLIT operands, is the one the feature was specified with:
     |got - ref| <= ulp_f32(ref) + (K + 8) 2^-24 S + 2^-16 S_aw,        S_aw = |out_scale| sum_k |a| |w|  <=  S
@@ -29,6 +33,7 @@ from kernel_compare import BoundTerms
 from tconv_spec import TconvEmuOps
 
 LINEAR, GEGLU, HEADS = 0, 1, 2
+REMAINDER, OPERAND, PRODUCT = 2.0 ** -17, 2.0 ** -16, 2.0 ** -15      # (module docstring)
 
 
 def split_bf16(x):
@@ -37,6 +42,32 @@ def split_bf16(x):
     hi = x.to(torch.bfloat16).float()
     lo = (x - hi).to(torch.bfloat16).float()
     return hi, lo
+
+
+def split_product(x, y_t, drop=None):
+    """x @ y_t by the rule, f32: hi(x) lo(y) + lo(x) hi(y) + hi(x) hi(y), the two small terms first, as the kernels' matrix instructions add them
+    (csrc/split_bf16.h::mma3 with y as the A operand).  drop = "hi_lo" / "lo_hi" leaves out hi(x) lo(y) / lo(x) hi(y): the defects the specs must catch."""
+    assert drop in (None, "hi_lo", "lo_hi")
+    (xh, xl), (yh, yl) = split_bf16(x), split_bf16(y_t)
+    hi_lo, lo_hi = xh @ yl, xl @ yh
+    small = lo_hi if drop == "hi_lo" else hi_lo if drop == "lo_hi" else hi_lo + lo_hi
+    return small + xh @ yh
+
+
+# the emulator defects of the two attention specs -> what their score product (x = q, y = k) and their P V product (x = p, y = v) leave out
+ATTN_DEFECTS = ("drop_q_lok", "drop_lop_v")
+ATTN_DROPS = {"drop_q_lok": ("hi_lo", None), "drop_lop_v": (None, "lo_hi")}
+
+
+def hip_ops_recorder(monkeypatch):
+    """a HipOps that launches nothing and takes CPU tensors: ensure_init is a no-op, _call keeps the argument struct in .calls"""
+    from followyourclick_amd import ops
+    monkeypatch.setattr(ops, "_p", lambda t: None if t is None else t.data_ptr())
+    h = ops.HipOps()
+    h.calls = []
+    h.ensure_init = lambda device: None
+    h._call = lambda name, args: h.calls.append((name, args))
+    return h
 
 
 class SplitEmuOps(TconvEmuOps):

@@ -2,7 +2,7 @@
 FYC_PRODUCTS_SPLIT_BF16; HipOps.temporal_attention(products="split")), the cases of tests/test_tattn_split_gpu.py as data, and the per-element bound they
 are judged by.  A helper, not a test module; no GPU is touched here.
 
-The rule, with hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) (tests/f32x3_spec.py::split_bf16):
+The rule, with hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) (tests/f32x3_spec.py: split_bf16, and split_product for the three-term products below):
   * q and k are taken as f32 and, with RoPE, rotated in f32 (two rounded products, one rounded sum); nothing is rounded to 16 bits before the split;
   * s[fq][fk] = sum_c hi(q) hi(k) + hi(q) lo(k) + lo(q) hi(k) in f32;
   * softmax in f32: max, exp2((s - max) * (scale * log2e)), f32 row sum; p is normalised by the row sum, then split;
@@ -10,10 +10,10 @@ The rule, with hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) (tests/f32x3_spe
 
 The bound, against the f64 attention of the UNSPLIT operands, needs no measurement.  kernel_compare.softmax_bound_terms(dtype="f32", kind="temporal") is the
 bound of an f32 evaluation whose q and k are uncertain by dq and dk; the split rule's score product is an f32 sum of 3 d exact products that is off from q.k by at
-most 2^-15 sum |q||k| (f32x3_spec's docstring: 2^-17 + 2^-17 for the two remainders, 2^-16 for the dropped lo lo product), which is what
-    dq = 2^-16 |q|,  dk = 2^-16 |k|       (+ 3 u (|x cos| + |x' sin|) under RoPE, as attention_cases._temporal_reference charges the exact f32 kernel)
-charge it: dq.|k| + |q|.dk + dq.dk >= 2^-15 sum |q||k|.  The P V product is off by at most 2^-15 sum_fk w |v| in the same way, and the reference is stored as f32:
-    |got - ref| <= ulp_f32(ref) + rest(dq, dk) + 2^-15 (w @ |v|).
+most PRODUCT sum |q||k| (the constants and their derivation: f32x3_spec's docstring; PRODUCT = 2^-15, OPERAND = 2^-16), which is what
+    dq = OPERAND |q|,  dk = OPERAND |k|       (+ 3 u (|x cos| + |x' sin|) under RoPE, as attention_cases._temporal_reference charges the exact f32 kernel)
+charge it: dq.|k| + |q|.dk + dq.dk >= PRODUCT sum |q||k|.  The P V product is off by at most PRODUCT sum_fk w |v| in the same way, and the reference is stored as f32:
+    |got - ref| <= ulp_f32(ref) + rest(dq, dk) + PRODUCT (w @ |v|).
 The global tolerance is the exact f32 kernel's, attention_cases.RTOL_TEMPORAL["f32"] = RTOL_TEMPORAL_ROPE["f32"] = 2e-5.
 Exact f32 products pass this bound too: what tells the rules apart is a single-frame problem, where p = 1 and the split rule returns hi(v) + lo(v), not v.
 
@@ -27,12 +27,13 @@ import numpy as np
 import torch
 
 import attention_cases as A
+import f32x3_spec as X
 import kernel_compare as KC
-from f32x3_spec import split_bf16
+from followyourclick_amd.ops import resolve_f32_products
 from rope_spec import RopeEmuOps, rotate_half
 
 RTOL = {False: A.RTOL_TEMPORAL["f32"], True: A.RTOL_TEMPORAL_ROPE["f32"]}      # by RoPE
-DEFECTS = ("drop_q_lok", "drop_lop_v")
+DEFECTS = X.ATTN_DEFECTS
 
 
 def _in_f32(c):
@@ -54,20 +55,12 @@ def split_attention(q, k, v, *, scale, rope=None, defect=None):
     if rope is not None:
         cos, sin = (torch.cat((t, t), dim=-1).float() for t in rope)
         q, k = (t * cos + rotate_half(t) * sin for t in (q, k))
-    (qh, ql), (kh, kl), (vh, vl) = split_bf16(q), split_bf16(k), split_bf16(v)
-    kht, klt = kh.transpose(-1, -2), kl.transpose(-1, -2)
-    s = ql @ kht                                          # the small terms first, as the kernel's matrix instructions add them
-    if defect != "drop_q_lok":
-        s = qh @ klt + s
-    s = s + qh @ kht
+    drop_qk, drop_pv = X.ATTN_DROPS.get(defect, (None, None))
+    s = X.split_product(q, k.transpose(-1, -2), drop=drop_qk)
     sl2e = float(np.float32(scale) * np.float32(1.44269504088896340736))
     p = torch.exp2((s - s.max(dim=-1, keepdim=True).values) * sl2e)
     p = p * (1.0 / p.sum(dim=-1, keepdim=True))
-    ph, pl = split_bf16(p)
-    o = ph @ vl
-    if defect != "drop_lop_v":
-        o = o + pl @ vh
-    return o + ph @ vh
+    return X.split_product(p, v, drop=drop_pv)
 
 
 class SplitTAttnEmuOps(RopeEmuOps):
@@ -78,11 +71,7 @@ class SplitTAttnEmuOps(RopeEmuOps):
         self.f32_products = f32_products
 
     def temporal_attention(self, qkv, o, *, clips, frames, pixels, heads, d, scale, rope=None, products=None, defect=None):
-        if products not in (None, "exact", "split"):
-            raise ValueError(f"temporal_attention: products {products!r}: expected None, 'exact' or 'split'")
-        if qkv.dtype != torch.float32 and products == "split":
-            raise TypeError(f"temporal_attention: products='split' needs float32 tensors (got {qkv.dtype})")
-        if qkv.dtype != torch.float32 or (self.f32_products if products is None else products) == "exact":
+        if resolve_f32_products("temporal_attention", qkv.dtype, products, self.f32_products) == 0:
             return super().temporal_attention(qkv, o, clips=clips, frames=frames, pixels=pixels, heads=heads, d=d, scale=scale, rope=rope)
         Cc = heads * d
         x = qkv.reshape(-1)[: clips * frames * pixels * 3 * Cc].reshape(clips, frames, pixels, 3, heads, d)
@@ -103,7 +92,7 @@ def hi_plus_lo_of_v(c, ops):
     """what a single-frame problem returns in the split rule, [rows][cols]: hi(v) + lo(v)"""
     assert c.F == 1
     v = ops.qkv.reshape(c.rows, 3, c.cols)[:, 2]
-    hi, lo = split_bf16(v.contiguous())
+    hi, lo = X.split_bf16(v.contiguous())
     return hi + lo, v
 
 
@@ -116,17 +105,17 @@ def reference(c):
         return _refs[c.problem]
     ops = A.operands(c)
     q, k, v = A._split(c, ops)
-    dq, dk = 2.0 ** -16 * q.double().abs(), 2.0 ** -16 * k.double().abs()
+    dq, dk = X.OPERAND * q.double().abs(), X.OPERAND * k.double().abs()
     if c.rope:
         (q, mq), (k, mk) = (A._rotate(t.float(), *ops.tables) for t in (q, k))
-        dq, dk = 2.0 ** -16 * q.double().abs() + 3 * KC.U["f32"] * mq.double(), 2.0 ** -16 * k.double().abs() + 3 * KC.U["f32"] * mk.double()
+        dq, dk = X.OPERAND * q.double().abs() + 3 * KC.U["f32"] * mq.double(), X.OPERAND * k.double().abs() + 3 * KC.U["f32"] * mk.double()
     o = torch.empty(c.clips, c.P, c.H, c.F, c.d, dtype=torch.float64)
     rest = torch.empty_like(o)
     for b in range(c.clips):
         for p in range(c.P):
             o[b, p], rest[b, p], w = KC.softmax_bound_terms(q[b, p].double(), k[b, p].double(), v[b, p].double(), scale=c.scale, dtype="f32", kind="temporal",
                                                             dq=dq[b, p], dk=dk[b, p])
-            rest[b, p] += 2.0 ** -15 * (w @ v[b, p].double().abs())
+            rest[b, p] += X.PRODUCT * (w @ v[b, p].double().abs())
     o, rest = (t.permute(0, 3, 1, 2, 4).reshape(c.rows, c.cols) for t in (o, rest))
     ref = ops.buf.clone()
     A.window(c, ref).copy_(o.float())

@@ -10,6 +10,7 @@ import torch
 
 import attention_cases as A
 import attn_split_spec as S
+from f32x3_spec import hip_ops_recorder
 from kernel_compare import Guard, compare
 
 
@@ -84,17 +85,6 @@ def test_case_list_reaches_every_instantiation():
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------------------------------
-def _recorder(monkeypatch):
-    """a HipOps that launches nothing and takes CPU tensors: ensure_init is a no-op, _call keeps the argument struct"""
-    from followyourclick_amd import ops
-    monkeypatch.setattr(ops, "_p", lambda t: None if t is None else t.data_ptr())
-    h = ops.HipOps()
-    h.calls = []
-    h.ensure_init = lambda device: None
-    h._call = lambda name, args: h.calls.append((name, args))
-    return h
-
-
 KW = dict(batch=1, heads=1, n_q=2, n_k=8, d=8, ldo=8, ldvt=8, scale=1.0)
 
 
@@ -138,7 +128,7 @@ def test_bad_field_is_refused_by_the_library_without_gpu(dtype, products):
 def test_the_field_follows_keyword_instance_and_dtype(monkeypatch):
     monkeypatch.delenv("FYC_F32_PRODUCTS", raising=False)
     monkeypatch.delenv("FYC_COMPUTE_DTYPE", raising=False)
-    h = _recorder(monkeypatch)
+    h = hip_ops_recorder(monkeypatch)
     assert h.f32_products == "exact"
 
     def field(dtype, **kw):

@@ -1,5 +1,6 @@
 """The split-bf16 product rule of fyc_gemm for f32 operands (include/fyc.h: f32_products), without a GPU: the split itself, the specification emulator
-against the bound the GPU cases are judged by (tests/f32x3_spec.py), the environment switches, and the argument check of the C entry point."""
+against the bound the GPU cases are judged by (tests/f32x3_spec.py), the environment switches, what keyword, instance mode and dtype make of the field in each of the
+tier's three entry points, and the argument check of the C entry point."""
 import ctypes
 import os
 
@@ -145,6 +146,46 @@ def test_hipops_takes_the_mode_from_the_environment(monkeypatch):
     assert h.f32_products == "split" and not h._ws_need and not h._q_cache
     with pytest.raises(ValueError):
         h.set_f32_products("f16")
+
+
+# ---- keyword, instance mode and dtype -> the field, for the three entry points of the tier ---------------------------------------------------------
+# (f32 tensors?, `products` keyword, HipOps.f32_products) -> the f32_products field that reaches the library, or the exception.  attention() has no fused kernel
+# with exact f32 products: where the table says 0 for f32 tensors it raises FycError instead.
+_FIELD = {(True, None, "exact"): 0, (True, None, "split"): 1, (True, "exact", "exact"): 0, (True, "exact", "split"): 0, (True, "split", "exact"): 1, (True, "split", "split"): 1,
+          (False, None, "exact"): 0, (False, None, "split"): 0, (False, "exact", "exact"): 0, (False, "exact", "split"): 0, (False, "split", "exact"): TypeError, (False, "split", "split"): TypeError,
+          (True, "f16", "exact"): ValueError, (True, "f16", "split"): ValueError, (False, "f16", "exact"): ValueError, (False, "f16", "split"): ValueError}
+# the smallest tensors each wrapper accepts: entry point -> (library function, dtype -> positional tensors, keywords)
+_CALLS = {
+    "gemm": ("fyc_gemm", lambda dt: (torch.zeros(8, 8, dtype=dt), torch.zeros(8, 8, dtype=dt), torch.zeros(8, 8, dtype=dt)), dict(M=8, N=8, K=8, lda=8, ldw=8, ldo=8)),
+    "attention": ("fyc_attention", lambda dt: (torch.zeros(2, 8, dtype=dt), torch.zeros(8, 8, dtype=dt), torch.zeros(8, 8, dtype=dt), torch.zeros(2, 8, dtype=dt)),
+                  dict(batch=1, heads=1, n_q=2, n_k=8, d=8, ldo=8, ldvt=8, scale=1.0)),
+    "temporal_attention": ("fyc_temporal_attention", lambda dt: (torch.zeros(2, 24, dtype=dt), torch.zeros(2, 8, dtype=dt)), dict(clips=1, frames=2, pixels=1, heads=1, d=8, scale=1.0)),
+}
+
+
+@pytest.mark.parametrize("mode", ["exact", "split"])
+@pytest.mark.parametrize("keyword", [None, "exact", "split", "f16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("op", sorted(_CALLS))
+def test_field_by_entry_point_dtype_keyword_and_mode(monkeypatch, op, dtype, keyword, mode):
+    """one rule for gemm, attention and temporal_attention (ops.resolve_f32_products): what reaches the library, or what is raised before anything is called"""
+    from followyourclick_amd import _lib
+    monkeypatch.delenv("FYC_F32_PRODUCTS", raising=False)
+    monkeypatch.delenv("FYC_COMPUTE_DTYPE", raising=False)
+    h = X.hip_ops_recorder(monkeypatch)
+    h.set_f32_products(mode)
+    want = _FIELD[dtype == torch.float32, keyword, mode]
+    if op == "attention" and dtype == torch.float32 and want == 0:
+        want = _lib.FycError
+    function, tensors, kw = _CALLS[op]
+    if isinstance(want, int):
+        getattr(h, op)(*tensors(dtype), products=keyword, **kw)
+        (name, args), = h.calls
+        assert name == function and args.f32_products == want and args.dtype == {torch.float32: _lib.FYC_F32, torch.bfloat16: _lib.FYC_BF16, torch.float16: _lib.FYC_F16}[dtype]
+    else:
+        with pytest.raises(want, match={ValueError: "products", TypeError: "split", _lib.FycError: "materialised"}[want]):
+            getattr(h, op)(*tensors(dtype), products=keyword, **kw)
+        assert not h.calls
 
 
 # ---- the C entry point ---------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ import torch
 
 import attention_cases as A
 import tattn_split_spec as S
+from f32x3_spec import hip_ops_recorder
 from kernel_compare import Guard, compare
 
 
@@ -68,17 +69,6 @@ def test_case_list_reaches_every_family():
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------------------------------
-def _recorder(monkeypatch):
-    """a HipOps that launches nothing and takes CPU tensors: ensure_init is a no-op, _call keeps the argument struct"""
-    from followyourclick_amd import ops
-    monkeypatch.setattr(ops, "_p", lambda t: None if t is None else t.data_ptr())
-    h = ops.HipOps()
-    h.calls = []
-    h.ensure_init = lambda device: None
-    h._call = lambda name, args: h.calls.append((name, args))
-    return h
-
-
 KW = dict(clips=1, frames=2, pixels=1, heads=1, d=8, scale=1.0)
 
 
@@ -115,7 +105,7 @@ def test_bad_f32_products_are_refused_by_the_library_without_gpu(dtype, products
 def test_the_field_follows_keyword_instance_and_dtype(monkeypatch):
     monkeypatch.delenv("FYC_F32_PRODUCTS", raising=False)
     monkeypatch.delenv("FYC_COMPUTE_DTYPE", raising=False)
-    h = _recorder(monkeypatch)
+    h = hip_ops_recorder(monkeypatch)
     assert h.f32_products == "exact"
 
     def field(dtype, **kw):
@@ -137,7 +127,7 @@ def test_environment_switches_set_the_mode_temporal_attention_uses(monkeypatch, 
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    h = _recorder(monkeypatch)
+    h = hip_ops_recorder(monkeypatch)
     h.temporal_attention(*_tensors(torch.float32), **KW)
     assert h.calls[-1][1].f32_products == want
     h.temporal_attention(*_tensors(torch.bfloat16), **KW)
