@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 EXTRA = os.environ.get("FYC_BUILD_EXTRA", "").split()
 LIB = os.path.abspath(os.environ.get("FYC_BUILD_LIB") or os.path.join(HERE, "libfyc_hip.so"))
 OBJ = os.path.join(HERE, "_obj") if not (EXTRA or os.environ.get("FYC_BUILD_LIB")) else LIB + ".obj"
-SOURCES = ["api.hip", "gemm.hip", "gemm_bf16_plain.hip", "gemm_bf16_conv.hip", "gemm_bf16_act.hip", "gemm_f16_plain.hip", "gemm_f16_conv.hip", "gemm_f16_act.hip", "gemm_f32.hip", "gemm_bf16_t3.hip", "gemm_f16_t3.hip", "gemm_f32_t3.hip", "gemm_f32x3.hip", "gemm_f32x3_t3.hip", "attention.hip", "attention_small.hip", "attention_medium.hip", "attention_large.hip", "attention_small_f16.hip", "attention_medium_f16.hip", "attention_large_f16.hip", "attention_f32x3.hip", "temporal_attn.hip", "temporal_attn_f32x3.hip", "temporal_block.hip", "temporal_block_rr.hip", "ff_block.hip", "panel_linear.hip", "norm.hip", "elementwise.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_bf16_plain.hip", "gemm_bf16_conv.hip", "gemm_bf16_act.hip", "gemm_f16_plain.hip", "gemm_f16_conv.hip", "gemm_f16_act.hip", "gemm_f32.hip", "gemm_bf16_t3.hip", "gemm_f16_t3.hip", "gemm_f32_t3.hip", "gemm_f32x3.hip", "gemm_f32x3_t3.hip", "attention.hip", "attention_small.hip", "attention_medium.hip", "attention_large.hip", "attention_small_f16.hip", "attention_medium_f16.hip", "attention_large_f16.hip", "attention_f32x3.hip", "attention_wide.hip", "attention_wide_f16.hip", "attention_wide_f32x3.hip", "temporal_attn.hip", "temporal_attn_f32x3.hip", "temporal_block.hip", "temporal_block_rr.hip", "ff_block.hip", "panel_linear.hip", "norm.hip", "elementwise.hip"]
 # FYC_GEMM_VARIANTS=1: also build the round-4 main-loop experiments of tools/exp/gemm_variants/ (off by default, measured slower)
 VARIANTS = os.environ.get("FYC_GEMM_VARIANTS") == "1"
 VARIANT_DIR = os.path.join(HERE, "..", "tools", "exp", "gemm_variants")
@@ -30,7 +30,8 @@ if VARIANTS:
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-value",
          "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 # ff_block.hip / panel_linear.hip / temporal_block_rr.hip run one wave per SIMD with the whole 512-register file: the accumulators must be AGPRs
-AGPR_SOURCES = {"ff_block.hip", "panel_linear.hip", "temporal_block_rr.hip"}
+# attention_wide*.hip: Q' and the O^T accumulators of a 512-wide head are 128 - 384 registers
+AGPR_SOURCES = {"ff_block.hip", "panel_linear.hip", "temporal_block_rr.hip", "attention_wide.hip", "attention_wide_f16.hip", "attention_wide_f32x3.hip"}
 
 
 # one wave per SIMD: a packed f32 VALU instruction beside MFMAs costs such a wave ~22 cycles more than the two scalar ones it replaces

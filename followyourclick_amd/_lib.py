@@ -41,6 +41,10 @@ class AttnArgs(C.Structure):
                 ("scale", f32), ("o_scale", f32), ("dtype", i32), ("q_batch_mod", i32), ("f32_products", i32)]
 
 
+class AttnMaskArgs(C.Structure):      # (ABI 308) fyc_attention_masked: the attention's arguments as they are, the causal flag behind them
+    _fields_ = [("attn", AttnArgs), ("causal", i32)]
+
+
 class TAttnArgs(C.Structure):
     _fields_ = [("qkv", vp), ("o", vp), ("clips", i32), ("frames", i32), ("pixels", i32), ("heads", i32), ("d", i32),
                 ("scale", f32), ("dtype", i32), ("rope_cos", vp), ("rope_sin", vp), ("f32_products", i32)]
@@ -154,7 +158,7 @@ class PackGegluArgs(C.Structure):
 
 # name -> args struct for every `int fyc_<op>(const args*, void* stream)` entry point
 OPS = {
-    "fyc_gemm": GemmArgs, "fyc_attention": AttnArgs, "fyc_temporal_attention": TAttnArgs,
+    "fyc_gemm": GemmArgs, "fyc_attention": AttnArgs, "fyc_attention_masked": AttnMaskArgs, "fyc_temporal_attention": TAttnArgs,
     "fyc_gn_stats": GnStatsArgs, "fyc_gn_apply": GnApplyArgs, "fyc_layernorm": LayerNormArgs,
     "fyc_softmax_rows": SoftmaxArgs, "fyc_concat_channels": ConcatArgs, "fyc_silu_f32": SiluArgs,
     "fyc_cast_from_f32": CastArgs, "fyc_cast_to_f32": CastArgs, "fyc_unet_input": UnetInputArgs,
@@ -168,7 +172,7 @@ MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes"]
 
 _lib = None
-FYC_VERSION = 307        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
+FYC_VERSION = 308        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
 
 
 class FycError(RuntimeError):

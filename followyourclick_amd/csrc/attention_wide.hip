@@ -1,0 +1,3 @@
+// bf16 instantiations of the chunk-walking attention kernel (attention_wide.h): head dims above 160 and the causal mask.
+#include "attention_wide.h"
+int fyca::run_wide_bf16(const AttnP& p, bool causal, hipStream_t st) { return run_wide_impl<bf16_t>(p, causal, st); }

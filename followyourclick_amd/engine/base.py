@@ -44,6 +44,35 @@ class ChanStats:
         self.rows, self.stat_rows, self.cs = rows, stat_rows, cs
 
 
+# The attention call sites beside the UNet - the VAE's mid block (one head of 512) and the encoders (CLIP text: causal; CLIP vision; Resampler) - as one
+# fyc_attention launch for the whole batch (ABI 308) instead of zeros + score GEMM + fyc_softmax_rows + P V GEMM.  Per (shape family, dtype word): is the fused
+# launch the default?  A family is fused by default iff its slowest fused round beat its fastest materialised round (profiles/wide_attention.txt section 2, the
+# criterion of profiles/f32x3_attention.txt); one that lost stays materialised and is reached with FYC_SIDE_FLASH=force.
+SIDE_FLASH_DEFAULT = {
+    ("vae", "bf16"): False, ("vae", "f16"): False, ("vae", "f32"): False,      # d = 512, 16 x 4096 / 4 x 9216 tokens: fused takes 2.0 - 2.6 x (16-bit), 1.8 - 2.2 x (f32 split) the materialised time
+    ("clip_text", "bf16"): True, ("clip_text", "f16"): True, ("clip_text", "f32"): True,
+    ("clip_vision", "bf16"): True, ("clip_vision", "f16"): True, ("clip_vision", "f32"): True,
+    ("resampler", "bf16"): True, ("resampler", "f16"): True, ("resampler", "f32"): True,
+}
+_DT_WORD = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32"}
+
+
+def side_flash(ops, dtype, family: str, d: int, causal: bool = False) -> bool:
+    """Does this call site take the fused launch?  Read at every call, like FYC_F32_FLASH.  The precondition: 16-bit tensors, or f32 with the ops' f32_products ==
+    "split" (exact f32 stays materialised: there is no exact fused kernel), and an ops object that answers both capability queries - the CPU emulator of the tests
+    and an A/B library of an earlier ABI do not, and keep the materialised sequence call for call.  FYC_SIDE_FLASH: unset / 1 = fused where SIDE_FLASH_DEFAULT says
+    so, 0 = never, force = wherever the precondition holds."""
+    sw = os.environ.get("FYC_SIDE_FLASH", "1")
+    if sw == "0":
+        return False
+    if dtype == torch.float32 and getattr(ops, "f32_products", "exact") != "split":
+        return False
+    can_causal, max_d = getattr(ops, "attention_causal_supported", None), getattr(ops, "attention_max_head_dim", None)
+    if can_causal is None or max_d is None or d % 8 or d > max_d() or (d > 160 and d % 32) or (causal and not can_causal()):
+        return False
+    return sw == "force" or SIDE_FLASH_DEFAULT[family, _DT_WORD[dtype]]
+
+
 class EngineBase:
     """Expects self.ops, self.dtype, self.device and self.groups (GroupNorm group count)."""
     fuse_stats = True           # producers write channel sums in their epilogues

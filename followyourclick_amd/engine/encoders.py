@@ -22,7 +22,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from .. import _lib as L
-from .base import EngineBase
+from .base import EngineBase, side_flash
 from .weights import Packed, f32, pack_linear
 
 Tensor = torch.Tensor
@@ -159,6 +159,10 @@ class _EncoderBase(EngineBase):
                   C: int, causal: bool = False) -> None:
         """softmax(q k^T d^-1/2 [+causal mask]) v per batch element; q (B,H,n_q,d), k (B,H,n_k,d), vt (B,H,d,ldk) -> out rows (B*n_q, C)"""
         o = self.ops
+        family = "clip_text" if causal else ("clip_vision" if n_q == n_k else "resampler")
+        if side_flash(o, q.dtype, family, d, causal):      # one fused launch for the whole batch (engine/base.py: precondition, FYC_SIDE_FLASH, the measured default)
+            o.attention(q, k, vt, out, batch=B, heads=H, n_q=n_q, n_k=n_k, d=d, ldo=C, ldvt=ldk, scale=d ** -0.5, **({"causal": True} if causal else {}))
+            return
         for b in range(B):
             S = self.zeros(H, n_q, ldk)
             o.gemm(q[b], k[b], S, M=n_q, N=n_k, K=d, lda=d, ldw=d, ldo=ldk, batch=H, stride_a=n_q * d, stride_w=n_k * d,

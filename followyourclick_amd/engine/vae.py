@@ -14,7 +14,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops as ops_mod
-from .base import EngineBase
+from .base import EngineBase, side_flash
 from .config import VAEDecoderConfig
 from .weights import Packed, pad_channels
 
@@ -53,7 +53,8 @@ class VAEDecoderEngine(EngineBase):
         return self.conv_cs(h, r.c2_w, r.c2_b, frames, H, W, residual=sc)
 
     def attention(self, a: Packed, x: Tensor, frames: int, H: int, W: int, cs=None) -> Tensor:
-        """single head, d = C (512): scores materialised through the batched GEMM, softmax in f32"""
+        """single head, d = C (512): one fused fyc_attention launch for all frames where engine/base.py::side_flash says so (16-bit, or f32 with split products;
+        FYC_SIDE_FLASH), otherwise scores materialised through the batched GEMM, softmax in f32"""
         o = self.ops
         rows, N = frames * H * W, H * W
         C = a.o_w.shape[0]
@@ -63,6 +64,10 @@ class VAEDecoderEngine(EngineBase):
         vt = self.zeros(frames, 1, C, ld) if ld != N else self.new(frames, 1, C, ld)
         o.gemm(h, a.qkv_w, None, M=rows, N=3 * C, K=C, lda=C, ldw=C, bias=a.qkv_b, epilogue=L.EPI_HEADS,
                heads=dict(seg_cols=C, heads=1, tokens=N, outs=[q, k, vt], transposed=[0, 0, 1], ld=[0, 0, ld]))
+        if side_flash(o, h.dtype, "vae", C):
+            att = self.new(rows, C)
+            o.attention(q, k, vt, att, batch=frames, heads=1, n_q=N, n_k=N, d=C, ldo=C, ldvt=ld, scale=C ** -0.5)
+            return self.lin(att, a.o_w, rows, bias=a.o_b, residual=x)
         S = self.zeros(frames, N, ld) if ld != N else self.new(frames, N, ld)
         o.gemm(q, k, S, M=N, N=N, K=C, lda=C, ldw=C, ldo=ld, batch=frames, stride_a=N * C, stride_w=N * C, stride_o=N * ld,
                out_scale=C ** -0.5)

@@ -251,22 +251,36 @@ class HipOps:
     # -- attention ---------------------------------------------------------------------------
     def attention(self, q: Tensor, k: Tensor, vt: Tensor, o: Tensor, *, batch: int, heads: int, n_q: int, n_k: int,
                   d: int, ldo: int, ldvt: int, scale: float, kv_batch_div: int = 1, accumulate: bool = False,
-                  o_scale: float = 1.0, q_batch_mod: int = 0, products: Optional[str] = None) -> None:
+                  o_scale: float = 1.0, q_batch_mod: int = 0, products: Optional[str] = None, causal: bool = False) -> None:
         """q_batch_mod > 0: q holds q_batch_mod batch elements, element b attends with the q of b % q_batch_mod.
+        causal: key j counts for query i iff j <= i (n_q == n_k, q_batch_mod == 0): fyc_attention_masked.  d: a multiple of 8 up to 160, or of 32 up to attention_max_head_dim().
         products: None = this instance's f32_products (the switch gemm() reads), else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors
         raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode).  f32 tensors run the fused kernel with split-bf16 products
         only (include/fyc.h): a resolved "exact" raises - the exact f32 mode is the materialised sequence gemm / softmax_rows / gemm (engine/unet3d.py::_attend)"""
         f32_products = resolve_f32_products("attention", q.dtype, products, self.f32_products, fused_exact=False)
         self.ensure_init(q.device)
-        a = L.AttnArgs()
+        m = L.AttnMaskArgs()
+        a = m.attn
         a.q, a.k, a.vt, a.o = _p(q), _p(k), _p(vt), _p(o)
         a.batch, a.heads, a.n_q, a.n_k, a.d, a.ldo, a.ldvt = batch, heads, n_q, n_k, d, ldo, ldvt
         a.kv_batch_div, a.o_accumulate, a.scale, a.o_scale, a.dtype = kv_batch_div, int(accumulate), scale, o_scale, _dt(q)
         a.q_batch_mod, a.f32_products = q_batch_mod, f32_products
-        self._call("fyc_attention", a)
+        if not causal:
+            self._call("fyc_attention", a)      # (the entry every earlier ABI has: an A/B library takes these calls unchanged)
+            return
+        m.causal = 1
+        self._call("fyc_attention_masked", m)
 
     def attention_q_batch_mod_supported(self) -> bool:
         return True
+
+    def attention_causal_supported(self) -> bool:
+        """attention(causal=True) exists (ABI 308; an A/B library of an earlier ABI, FYC_LIB_PATH, has no fyc_attention_masked)"""
+        return self.abi_version >= 308
+
+    def attention_max_head_dim(self) -> int:
+        """the largest d attention() takes: 512 (multiples of 32 above 160) from ABI 308 on, 160 before"""
+        return 512 if self.abi_version >= 308 else 160
 
     def repeat(self, src: Tensor, dst: Tensor, *, times: int) -> None:
         """dst = `times` back-to-back copies of src (both contiguous, any dtype)"""

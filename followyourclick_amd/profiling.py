@@ -77,6 +77,14 @@ class TimedOps:
         fn = getattr(self.inner, "attention_q_batch_mod_supported", None)
         return bool(fn and fn())
 
+    def attention_causal_supported(self):
+        fn = getattr(self.inner, "attention_causal_supported", None)
+        return bool(fn and fn())
+
+    def attention_max_head_dim(self):
+        fn = getattr(self.inner, "attention_max_head_dim", None)
+        return int(fn()) if fn else 160
+
     def repeat(self, src, dst, **kw):
         n = src.numel() * src.element_size()
         return self._timed("repeat", 0.0, (1.0 + kw["times"]) * n, self.inner.repeat, src, dst, **kw)

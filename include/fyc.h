@@ -29,8 +29,8 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off; 307 = the same rule for the fused spatial attention: f32_products APPENDED to fyc_attention's arguments - zero = off (every 16-bit launch is unchanged); FYC_F32 tensors are taken with FYC_PRODUCTS_SPLIT_BF16 only. */
-#define FYC_VERSION 307
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off; 307 = the same rule for the fused spatial attention: f32_products APPENDED to fyc_attention's arguments - zero = off (every 16-bit launch is unchanged); FYC_F32 tensors are taken with FYC_PRODUCTS_SPLIT_BF16 only; 308 = causal mask and head dims up to 512 for the fused spatial attention, no struct changed: one new entry point, fyc_attention_masked, whose fyc_attn_mask_args is a fyc_attn_args followed by `causal` (zero = fyc_attention, call for call); fyc_attention itself takes head dims 160 < d <= 512 in multiples of 32 in every dtype it takes, and with d <= 160 every launch is unchanged. */
+#define FYC_VERSION 308
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
  * packed weight streams (16-bit elements), v_mfma_*_f16 instead of v_mfma_*_bf16; the packers cast to the `dtype` they are given */
@@ -175,8 +175,18 @@ int fyc_chan_stats_reduce(const fyc_chan_stats_reduce_args* a, void* stream);
  * q_batch_mod > 0: the q of batch element b is read from batch element b % q_batch_mod (q holds q_batch_mod elements): the two
  * halves of a classifier-free-guidance pair share their queries up to the first cross-attention and differ in the text K / V only.
  *
+ * fyc_attention_masked (version 308): fyc_attention with a causal mask.  fyc_attn_mask_args = { fyc_attn_args attn; int32_t causal; }: fyc_attn_args keeps the layout of
+ * version 307 (a 307 host's struct is still the whole struct), the flag sits behind it.  causal = 0 is fyc_attention(&attn), call for call.
+ * causal = 1: key j counts for query i iff j <= i (the CLIP text tower); needs n_q == n_k and q_batch_mod == 0.  A masked key enters neither the running
+ * maximum nor l - it is excluded, not given a small weight - and key 0 is visible to every query, so no row is empty.  Key tiles wholly above a query block's diagonal
+ * are not visited.  Head dim (version 308): a multiple of 8 up to 160, or a multiple of 32 with 160 < d <= 512 (the VAE mid block's single head of 512).  causal = 1 and
+ * d > 160 run the chunk-walking kernel of csrc/attention_wide.h in every dtype, with the rule of that dtype: 16-bit - q' = T(q * f32(scale * log2e)), f32 scores in the
+ * MFMA accumulators, p = exp2(t - m) in f32 with the lagging maximum, p rounded to T for the PV product, l = the f32 sum of the rounded p; FYC_F32 - the rule below.
+ * q / k / vt / o must be 16-byte aligned there.  causal other than 0 / 1, causal = 1 with n_q != n_k or q_batch_mod > 0, d > 160 that is no multiple of 32 and d > 512 are
+ * refused before anything that needs a device or fyc_init.
+ *
  * FYC_F32 tensors (version 307, f32_products; hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) as for fyc_gemm and fyc_temporal_attention).  The same layouts in f32, the
- * same kv_batch_div / q_batch_mod / o_accumulate / o_scale, d a multiple of 8 up to 160, ldvt % 8 == 0, ldo % 4 == 0, q / k / vt / o 16-byte aligned.  Only
+ * same kv_batch_div / q_batch_mod / o_accumulate / o_scale / causal, the same head dims, ldvt % 8 == 0, ldo % 4 == 0, q / k / vt / o 16-byte aligned.  Only
  * f32_products = FYC_PRODUCTS_SPLIT_BF16 runs (csrc/attention_f32x3.hip); FYC_PRODUCTS_EXACT with FYC_F32 is refused - there is no exact fused kernel, the exact f32
  * mode goes through the materialised sequence fyc_gemm / fyc_softmax_rows / fyc_gemm.  The rule:
  *  - q' = q * f32(scale * log2e), one f32 rounding; q' and k are split, nothing is rounded to 16 bits before the split;
@@ -206,6 +216,9 @@ typedef struct {
   int32_t f32_products;
 } fyc_attn_args;
 int fyc_attention(const fyc_attn_args* a, void* stream);
+/* (version 308) causal: 0 = off (= fyc_attention); 1 = key j counts for query i iff j <= i (attn.n_q == attn.n_k, attn.q_batch_mod == 0) */
+typedef struct { fyc_attn_args attn; int32_t causal; } fyc_attn_mask_args;
+int fyc_attention_masked(const fyc_attn_mask_args* a, void* stream);
 
 /* ---- temporal self-attention core of the motion module ------------------------------------
  * For every (clip b, pixel p, head h): softmax over the F frames (motion_module.py:371-464 with
