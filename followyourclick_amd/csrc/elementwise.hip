@@ -82,6 +82,47 @@ __global__ void __launch_bounds__(256) unet_input_kernel(const float* __restrict
   }
 }
 
+// the guided prediction of one element from the unconditional, conditional and (optional) per-frame unconditional one: the one f32
+// expression of the step kernels and of the moments pass of the guidance rescale
+__device__ __forceinline__ float cfg_guided(float u, float cnd, bool has_single, float s1, float video_scale, float guidance) {
+  if (has_single) return s1 + video_scale * (u - s1) + guidance * (cnd - u);
+  return u + guidance * (cnd - u);
+}
+
+// guidance + DDIM update of pixel-row i = (b, f, p): the body of both step kernels.  RESCALE: the guided prediction of sample b is
+// multiplied by factor[b] (guidance rescale, fyc_cfg_ddim_step_rescaled) before anything else sees it
+template <typename T, bool RESCALE>
+__device__ __forceinline__ void cfg_ddim_row(long long i, const T* __restrict__ pred, float* __restrict__ lat, float sa, float sb,
+                                             float sap, float sbp, int B, int F, int HW, int CL, int ld, int cfg, float guidance,
+                                             int pred_type, int clip, const T* __restrict__ single, float video_scale,
+                                             const float* __restrict__ noise, float sigma, int reclip,
+                                             const float* __restrict__ factor) {
+  const int p = (int)(i % HW);
+  const long long bf = i / HW;
+  const int f = (int)(bf % F), b = (int)(bf / F);
+  const T* pu = pred + i * ld;                                   // uncond (or the only) half
+  const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
+  for (int c = 0; c < CL; ++c) {
+    float v = ElemIO<T>::ld(pu + c);
+    if (cfg) {
+      const float u = v, cnd = ElemIO<T>::ld(pc + c);
+      v = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
+      if (RESCALE) v *= factor[b];
+    }
+    float* lp = lat + (((long long)b * CL + c) * F + f) * HW + p;
+    const float x = *lp;
+    float x0, eps;
+    if (pred_type == 1) { x0 = sa * x - sb * v; eps = sa * v + sb * x; }
+    else if (pred_type == 0) { x0 = (x - sb * v) / sa; eps = v; }
+    else { x0 = v; eps = v; }
+    if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    if (reclip) eps = (x - sa * x0) / sb;                        // use_clipped_model_output (scheduling_ddim.py:342-344)
+    float nx = sap * x0 + sbp * eps;
+    if (noise) nx += sigma * noise[(((long long)b * CL + c) * F + f) * HW + p];      // eta > 0 (:346-363)
+    *lp = nx;
+  }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) cfg_ddim_kernel(const T* __restrict__ pred, float* __restrict__ lat,
                                                        const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
@@ -90,32 +131,101 @@ __global__ void __launch_bounds__(256) cfg_ddim_kernel(const T* __restrict__ pre
                                                        const float* __restrict__ noise, float sigma, int reclip) {
   const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
   const long long total = (long long)B * F * HW;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const long long bf = i / HW;
-    const int f = (int)(bf % F), b = (int)(bf / F);
-    const T* pu = pred + i * ld;                                   // uncond (or the only) half
-    const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
-    for (int c = 0; c < CL; ++c) {
-      float v = ElemIO<T>::ld(pu + c);
-      if (cfg) {
-        const float u = v, cnd = ElemIO<T>::ld(pc + c);
-        if (single) { const float s1 = ElemIO<T>::ld(single + i * ld + c); v = s1 + video_scale * (u - s1) + guidance * (cnd - u); }
-        else v = u + guidance * (cnd - u);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
+    cfg_ddim_row<T, false>(i, pred, lat, sa, sb, sap, sbp, B, F, HW, CL, ld, cfg, guidance, pred_type, clip, single, video_scale, noise,
+                           sigma, reclip, nullptr);
+}
+
+// the same step with the per-sample factor of the guidance rescale (cfg is on: the host refuses the rest)
+template <typename T>
+__global__ void __launch_bounds__(256) cfg_ddim_rescaled_kernel(const T* __restrict__ pred, float* __restrict__ lat,
+                                                                const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
+                                                                float guidance, int pred_type, int clip,
+                                                                const T* __restrict__ single, float video_scale,
+                                                                const float* __restrict__ noise, float sigma, int reclip,
+                                                                const float* __restrict__ factor) {
+  const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
+  const long long total = (long long)B * F * HW;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
+    cfg_ddim_row<T, true>(i, pred, lat, sa, sb, sap, sbp, B, F, HW, CL, ld, 1, guidance, pred_type, clip, single, video_scale, noise,
+                          sigma, reclip, factor);
+}
+
+// Moments pass of the guidance rescale.  Block (b, part) owns rows [part * CFG_MOMENT_ROWS, +CFG_MOMENT_ROWS) of the F * HW pixel-rows
+// of sample b - a run fixed by the shape; thread t takes rows t, t + 256, ... of the run.  c and v are the f32 values the step kernel
+// forms; {sum c, sum c^2, sum v, sum v^2} are accumulated in f64 (the squares of f32 values are exact there), reduced over the block by a
+// fixed tree in LDS and written as one partial [4] per block: no atomics, the same bits every time.
+// VEC: c_latent == 4 and rows that start on a 4-element boundary - one 8-byte (16-bit) or 16-byte (f32) load per row and half
+constexpr int CFG_MOMENT_ROWS = 1024;
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) cfg_moments_kernel(const T* __restrict__ pred, double* __restrict__ parts, int B, int rows, int CL,
+                                                          int ld, int nparts, float guidance, const T* __restrict__ single,
+                                                          float video_scale) {
+  __shared__ double red[4][256];
+  const int b = blockIdx.x / nparts, part = blockIdx.x - b * nparts, t = threadIdx.x;
+  const int r_end = min(rows, (part + 1) * CFG_MOMENT_ROWS);
+  double sc = 0.0, scc = 0.0, sv = 0.0, svv = 0.0;
+  for (int r = part * CFG_MOMENT_ROWS + t; r < r_end; r += 256) {
+    const long long i = (long long)b * rows + r;
+    const T* pu = pred + i * ld;
+    const T* pc = pred + ((long long)B * rows + i) * ld;
+    const T* ps = single ? single + i * ld : nullptr;
+    if (VEC) {
+      float u[4], cn[4], s1[4] = {0.f, 0.f, 0.f, 0.f};
+      ElemIO<T>::ld4(pu, u);
+      ElemIO<T>::ld4(pc, cn);
+      if (ps) ElemIO<T>::ld4(ps, s1);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double cd = (double)cn[c], vd = (double)cfg_guided(u[c], cn[c], ps != nullptr, s1[c], video_scale, guidance);
+        sc += cd; scc += cd * cd; sv += vd; svv += vd * vd;
       }
-      float* lp = lat + (((long long)b * CL + c) * F + f) * HW + p;
-      const float x = *lp;
-      float x0, eps;
-      if (pred_type == 1) { x0 = sa * x - sb * v; eps = sa * v + sb * x; }
-      else if (pred_type == 0) { x0 = (x - sb * v) / sa; eps = v; }
-      else { x0 = v; eps = v; }
-      if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-      if (reclip) eps = (x - sa * x0) / sb;                        // use_clipped_model_output (scheduling_ddim.py:342-344)
-      float nx = sap * x0 + sbp * eps;
-      if (noise) nx += sigma * noise[(((long long)b * CL + c) * F + f) * HW + p];      // eta > 0 (:346-363)
-      *lp = nx;
+    } else {
+      for (int c = 0; c < CL; ++c) {
+        const float cn = ElemIO<T>::ld(pc + c);
+        const double cd = (double)cn;
+        const double vd = (double)cfg_guided(ElemIO<T>::ld(pu + c), cn, ps != nullptr, ps ? ElemIO<T>::ld(ps + c) : 0.f, video_scale, guidance);
+        sc += cd; scc += cd * cd; sv += vd; svv += vd * vd;
+      }
     }
   }
+  red[0][t] = sc; red[1][t] = scc; red[2][t] = sv; red[3][t] = svv;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) red[k][t] += red[k][t + s];
+    }
+    __syncthreads();
+  }
+  if (t < 4) parts[(long long)blockIdx.x * 4 + t] = red[t][0];
+}
+
+// One block per sample: the partials of the sample folded in index order, the factor  phi * s_text / s_cfg + (1 - phi)  formed in f64 from
+// the unbiased variances and rounded once to f32.  A constant guided prediction (s_cfg = 0) keeps the factor 1.
+__global__ void __launch_bounds__(64) cfg_rescale_factor_kernel(const double* __restrict__ parts, float* __restrict__ factor, int nparts,
+                                                                double n, float phi) {
+  __shared__ double sh[64][4];
+  const double* p = parts + (long long)blockIdx.x * nparts * 4;
+  double sc = 0.0, scc = 0.0, sv = 0.0, svv = 0.0;
+  // 64 partials at a time: every lane fetches one (the loads overlap), lane 0 adds them in index order
+  for (int k0 = 0; k0 < nparts; k0 += 64) {
+    const int k = k0 + threadIdx.x;
+    if (k < nparts) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sh[threadIdx.x][j] = p[4 * k + j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = min(64, nparts - k0);
+      for (int i = 0; i < m; ++i) { sc += sh[i][0]; scc += sh[i][1]; sv += sh[i][2]; svv += sh[i][3]; }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double var_c = fmax(scc - sc * sc / n, 0.0) / (n - 1.0), var_v = fmax(svv - sv * sv / n, 0.0) / (n - 1.0);
+  const double ph = (double)phi;
+  factor[blockIdx.x] = var_v > 0.0 ? (float)(ph * (sqrt(var_c) / sqrt(var_v)) + (1.0 - ph)) : 1.f;
 }
 
 template <typename T>
@@ -302,12 +412,18 @@ extern "C" int fyc_unet_input(const fyc_unet_input_args* a, void* stream) {
   return 0;
 }
 
-extern "C" int fyc_cfg_ddim_step(const fyc_cfg_ddim_args* a, void* stream) {
+// the argument checks of the DDIM step, shared by its two entry points
+static int cfg_ddim_check(const fyc_cfg_ddim_args* a) {
   FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_ddim_step: null pointer");
   FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_ddim_step: bad dims");
   FYC_REQUIRE(a->pred_type >= 0 && a->pred_type <= 2, "fyc_cfg_ddim_step: pred_type %d", a->pred_type);
   FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_ddim_step: pred_single needs classifier-free guidance (cfg = 1)");
   FYC_REQUIRE(a->variance_noise == nullptr || a->sigma >= 0.f, "fyc_cfg_ddim_step: sigma %g", (double)a->sigma);
+  return 0;
+}
+
+extern "C" int fyc_cfg_ddim_step(const fyc_cfg_ddim_args* a, void* stream) {
+  if (int rc = cfg_ddim_check(a)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)a->B * a->F * a->HW;
   FYC_DT(a,
@@ -315,6 +431,68 @@ extern "C" int fyc_cfg_ddim_step(const fyc_cfg_ddim_args* a, void* stream) {
          hipLaunchKernelGGL(cfg_ddim_kernel<f16_t>, dim3(grid_for(n)), dim3(256), 0, st, (const f16_t*)a->pred, a->latents, a->coef, a->B, a->F, a->HW, a->c_latent, a->ld, a->cfg, a->guidance, a->pred_type, a->clip_sample, (const f16_t*)a->pred_single, a->video_scale, a->variance_noise, a->sigma, a->clipped_model_output),
          hipLaunchKernelGGL(cfg_ddim_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)a->pred, a->latents, a->coef, a->B, a->F, a->HW, a->c_latent, a->ld, a->cfg, a->guidance, a->pred_type, a->clip_sample, (const float*)a->pred_single, a->video_scale, a->variance_noise, a->sigma, a->clipped_model_output));
   FYC_CHECK_LAUNCH("fyc_cfg_ddim_step");
+  return 0;
+}
+
+// ---- guidance rescale: moments pass, factor, step -------------------------------------------------------------------------------
+// workspace = [B * nparts][4] f64 partials, then [B] f32 factors
+struct CfgRescalePlan { int rows, nparts; int64_t part_bytes, bytes; };
+
+static bool cfg_rescale_plan(const fyc_cfg_ddim_args* s, CfgRescalePlan& pl) {
+  if (!(s->B > 0 && s->F > 0 && s->HW > 0 && s->c_latent > 0 && s->ld >= s->c_latent)) return false;
+  const int64_t rows = (int64_t)s->F * s->HW;
+  if (rows > INT32_MAX - CFG_MOMENT_ROWS || rows * s->c_latent < 2) return false;
+  const int64_t nparts = ceil_div64(rows, CFG_MOMENT_ROWS);
+  if (nparts * s->B > INT32_MAX) return false;
+  pl.rows = (int)rows;
+  pl.nparts = (int)nparts;
+  pl.part_bytes = nparts * s->B * 4 * (int64_t)sizeof(double);
+  pl.bytes = (pl.part_bytes + (int64_t)s->B * (int64_t)sizeof(float) + 255) / 256 * 256;
+  return true;
+}
+
+extern "C" int64_t fyc_cfg_ddim_rescale_workspace_bytes(const fyc_cfg_ddim_rescale_args* a) {
+  CfgRescalePlan pl;
+  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->step.cfg) return 0;
+  return cfg_rescale_plan(&a->step, pl) ? pl.bytes : 0;
+}
+
+template <typename T>
+static void cfg_rescale_launch(const fyc_cfg_ddim_rescale_args* a, const CfgRescalePlan& pl, hipStream_t st) {
+  const fyc_cfg_ddim_args* s = &a->step;
+  double* parts = (double*)a->workspace;
+  float* factor = (float*)((char*)a->workspace + pl.part_bytes);
+  const T* pred = (const T*)s->pred;
+  const T* single = (const T*)s->pred_single;
+  // one vector load per row: 4 latent channels, rows pitched in multiples of 4 elements from bases on such a boundary
+  const uintptr_t row_align = 4 * sizeof(T);
+  const bool vec = s->c_latent == 4 && s->ld % 4 == 0 && ((uintptr_t)pred % row_align) == 0 && ((uintptr_t)single % row_align) == 0;
+  const dim3 grid((unsigned)(s->B * pl.nparts));
+  if (vec) hipLaunchKernelGGL((cfg_moments_kernel<T, true>), grid, dim3(256), 0, st, pred, parts, s->B, pl.rows, s->c_latent, s->ld, pl.nparts, s->guidance, single, s->video_scale);
+  else hipLaunchKernelGGL((cfg_moments_kernel<T, false>), grid, dim3(256), 0, st, pred, parts, s->B, pl.rows, s->c_latent, s->ld, pl.nparts, s->guidance, single, s->video_scale);
+  hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(s->B), dim3(64), 0, st, (const double*)parts, factor, pl.nparts, (double)pl.rows * s->c_latent, a->guidance_rescale);
+  const long long n = (long long)s->B * pl.rows;
+  hipLaunchKernelGGL(cfg_ddim_rescaled_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, pred, s->latents, s->coef, s->B, s->F, s->HW, s->c_latent, s->ld, s->guidance, s->pred_type, s->clip_sample, single, s->video_scale, s->variance_noise, s->sigma, s->clipped_model_output, (const float*)factor);
+}
+
+extern "C" int fyc_cfg_ddim_step_rescaled(const fyc_cfg_ddim_rescale_args* a, void* stream) {
+  FYC_REQUIRE(a, "fyc_cfg_ddim_step_rescaled: null pointer");
+  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_ddim_step_rescaled: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
+  if (a->guidance_rescale == 0.f) return fyc_cfg_ddim_step(&a->step, stream);
+  const fyc_cfg_ddim_args* s = &a->step;
+  FYC_REQUIRE(s->cfg, "fyc_cfg_ddim_step_rescaled: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
+  if (int rc = cfg_ddim_check(s)) return rc;
+  FYC_REQUIRE(s->dtype == FYC_BF16 || s->dtype == FYC_F16 || s->dtype == FYC_F32, "fyc_cfg_ddim_step_rescaled: bad dtype %d", s->dtype);
+  CfgRescalePlan pl;
+  FYC_REQUIRE(cfg_rescale_plan(s, pl), "fyc_cfg_ddim_step_rescaled: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)s->F * s->HW * s->c_latent);
+  FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_ddim_step_rescaled: workspace is null or not 8-byte aligned");
+  FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_ddim_step_rescaled: workspace_bytes %lld < %lld (fyc_cfg_ddim_rescale_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
+  FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_ddim_step_rescaled: fyc_init() not called");
+  hipStream_t st = (hipStream_t)stream;
+  if (s->dtype == FYC_BF16) cfg_rescale_launch<bf16_t>(a, pl, st);
+  else if (s->dtype == FYC_F16) cfg_rescale_launch<f16_t>(a, pl, st);
+  else cfg_rescale_launch<float>(a, pl, st);
+  FYC_CHECK_LAUNCH("fyc_cfg_ddim_step_rescaled");
   return 0;
 }
 

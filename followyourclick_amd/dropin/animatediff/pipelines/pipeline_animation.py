@@ -21,7 +21,7 @@ from typing import Callable, List, Optional, Union
 import numpy as np
 import torch
 
-from followyourclick_amd.engine.sampler import DDIMSampler
+from followyourclick_amd.engine.sampler import DDIMSampler, resolve_guidance_rescale
 
 
 @dataclass
@@ -246,6 +246,9 @@ class AnimationPipeline:
         def as_list(v):
             return None if v is None else torch.as_tensor(v).reshape(-1).float().cpu().tolist()
 
+        # guidance rescale (arXiv:2305.08891 section 3.4): the keyword of later diffusers pipelines, taken from **kwargs (the parameter list is
+        # the reference's); the reference's scripts cannot pass it, for them the FYC_GUIDANCE_RESCALE environment switch (unset = 0 = off)
+        guidance_rescale = resolve_guidance_rescale(kwargs.get("guidance_rescale"))
         engine = self.unet._get_engine()
         sampler = DDIMSampler(engine, self.scheduler.engine_config)
         bar = self.progress_bar(total=num_inference_steps)
@@ -262,7 +265,8 @@ class AnimationPipeline:
                                      flow=as_list(flow_control) if use_fps_condition else None, ip_tokens=ip_tokens, callback=cb,
                                      video_scale=float(video_scale or 0.0), first_frame_condition=bool(use_first_frame_condition),
                                      eta=float(eta), generator=generator,            # stochastic DDIM (reference :672, scheduling_ddim.py:336-365)
-                                     camera=as_list(camera_movement_type) if use_camera_motion_condition else None)
+                                     camera=as_list(camera_movement_type) if use_camera_motion_condition else None,
+                                     guidance_rescale=guidance_rescale)
         if hasattr(bar, "close"):
             bar.close()
 

@@ -27,11 +27,12 @@ class DDIMScheduler:
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", trained_betas=None, clip_sample: bool = True, set_alpha_to_one: bool = True,
-                 steps_offset: int = 0, prediction_type: str = "epsilon", rescale_betas_zero_snr: bool = False, **kwargs):
+                 steps_offset: int = 0, prediction_type: str = "epsilon", rescale_betas_zero_snr: bool = False,
+                 timestep_spacing: str = "leading", **kwargs):
         self.engine_config = DDIMConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                         beta_schedule=beta_schedule, trained_betas=trained_betas, clip_sample=clip_sample,
                                         set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset, prediction_type=prediction_type,
-                                        rescale_betas_zero_snr=rescale_betas_zero_snr)
+                                        rescale_betas_zero_snr=rescale_betas_zero_snr, timestep_spacing=timestep_spacing)
         self.config = SimpleNamespace(**vars(self.engine_config))
         self.tables = DDIMTables(self.engine_config)
         self.betas, self.alphas, self.alphas_cumprod = self.tables.betas, self.tables.alphas, self.tables.alphas_cumprod
@@ -71,6 +72,7 @@ class DDIMScheduler:
              generator=None, variance_noise=None, return_dict: bool = True):
         if self.num_inference_steps is None:
             raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        self.tables.check_step(int(timestep), use_clipped_model_output)      # abar_t = 0 (first trailing step, zero SNR): no division by it
         sa, sb, sap, sbp, sigma = self.tables.step_coefficients(int(timestep), self.num_inference_steps, float(eta))
         if self.tables.pred_type == 1:
             x0, eps = sa * sample - sb * model_output, sa * model_output + sb * sample

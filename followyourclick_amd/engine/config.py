@@ -128,3 +128,7 @@ class DDIMConfig:
     steps_offset: int = 1
     prediction_type: str = "v_prediction"
     rescale_betas_zero_snr: bool = True
+    # how the inference timesteps are spread over the training ones (later diffusers; arXiv:2305.08891 section 3.3): "leading" = the
+    # reference's arange(n) * (T // n) + steps_offset, which never reaches T - 1; "trailing" starts at T - 1, the step a
+    # zero-terminal-SNR model was trained to see pure noise at; "linspace" spreads T - 1 .. 0 evenly
+    timestep_spacing: str = "leading"

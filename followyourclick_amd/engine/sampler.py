@@ -23,6 +23,26 @@ from .weights import pad_channels
 Tensor = torch.Tensor
 
 
+def check_guidance_rescale(value, what: str = "guidance_rescale") -> float:
+    """the factor phi of the guidance rescale (arXiv:2305.08891 section 3.4): 0 = off .. 1 = the conditional prediction's standard deviation"""
+    try:
+        phi = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} = {value!r} is not a number") from None
+    if not 0.0 <= phi <= 1.0:           # (NaN fails both comparisons)
+        raise ValueError(f"{what} = {value!r} must lie in [0, 1]")
+    return phi
+
+
+def resolve_guidance_rescale(value=None) -> float:
+    """the caller's keyword, else the FYC_GUIDANCE_RESCALE environment switch (unset or empty = 0 = off): for front ends whose callers cannot pass the
+    keyword (AnimationPipeline under the reference's scripts), read once per clip.  The sampler itself takes the number only."""
+    if value is not None:
+        return check_guidance_rescale(value)
+    env = os.environ.get("FYC_GUIDANCE_RESCALE", "")
+    return check_guidance_rescale(env, "FYC_GUIDANCE_RESCALE") if env.strip() else 0.0
+
+
 class DDIMSampler:
     def __init__(self, unet: UNet3DEngine, ddim: DDIMConfig):
         self.unet = unet
@@ -33,14 +53,23 @@ class DDIMSampler:
     def prepare(self, text_embeddings: Tensor, num_steps: int, batch: int, guidance_scale: float,
                 fps: Optional[Sequence[float]] = None, flow: Optional[Sequence[float]] = None,
                 ip_tokens: Optional[Tensor] = None, video_scale: float = 0.0, frames: int = 0,
-                first_frame_condition: bool = False, eta: float = 0.0, camera: Optional[Sequence[float]] = None) -> dict:
-        """text_embeddings: (cfg*batch, 77, D) with the unconditional half first (reference :397)."""
+                first_frame_condition: bool = False, eta: float = 0.0, camera: Optional[Sequence[float]] = None,
+                guidance_rescale: float = 0.0, use_clipped_model_output: bool = False) -> dict:
+        """text_embeddings: (cfg*batch, 77, D) with the unconditional half first (reference :397).
+        guidance_rescale (0 = off .. 1) is checked here and handed to every `step` by `sample`: the guided prediction of every sample is rescaled
+        towards the standard deviation of its conditional one (ops.cfg_ddim_step_rescaled); it needs classifier-free guidance.  use_clipped_model_output is only checked here, against the schedule."""
         u = self.unet
         cfg_on = guidance_scale > 1.0
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if guidance_rescale > 0 and not cfg_on:
+            raise ValueError(f"guidance_rescale = {guidance_rescale} needs classifier-free guidance (guidance_scale > 1, got {guidance_scale}): "
+                             "without it there is no guided prediction to rescale")
         beff = batch * (2 if cfg_on else 1)
         if text_embeddings.shape[0] != beff:
             raise ValueError(f"text_embeddings batch {text_embeddings.shape[0]} != {beff}")
         ts = self.tables.timesteps(num_steps)
+        for t in ts.tolist():           # a step at abar_t = 0 (trailing spacing on a zero-SNR table) that would divide by it
+            self.tables.check_step(t, use_clipped_model_output)
 
         def dup(v):
             if v is None:
@@ -75,12 +104,14 @@ class DDIMSampler:
         coef = coef_host.to(u.device)
         extra["sigma"] = coef_host[:, 4].tolist()           # eta > 0: per-step std of the added noise (0 for eta = 0)
         return dict(timesteps=ts, temb=temb.reshape(num_steps, beff, -1), coef=coef, cfg=cfg_on, beff=beff,
-                    guidance=float(guidance_scale), steps=num_steps, batch=batch, ctx_main=u.ctx_cache, **extra)
+                    guidance=float(guidance_scale), steps=num_steps, batch=batch, ctx_main=u.ctx_cache,
+                    guidance_rescale=guidance_rescale, **extra)
 
     @torch.no_grad()
     def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
-             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False) -> None:
-        """one DDIM step, latents (B,4,F,h,w) f32 updated in place.  variance_noise (latents' shape, f32): the noise of a stochastic
+             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
+             guidance_rescale: float = 0.0) -> None:
+        """one DDIM step, latents (B,4,F,h,w) f32 updated in place.  guidance_rescale = 0: ops.cfg_ddim_step as ever; above 0: ops.cfg_ddim_step_rescaled.  variance_noise (latents' shape, f32): the noise of a stochastic
         step (eta > 0, reference scheduling_ddim.py:346-363), scaled by the step's sigma from `prepare(eta=...)`."""
         u, o = self.unet, self.unet.ops
         B, CL, F, H, W = latents.shape
@@ -117,11 +148,18 @@ class DDIMSampler:
             u.ctx_cache = st["ctx_single"]
             single = u.forward(x[: B * F * H * W], st["temb_single"][i], B * F, 1, H, W)
             u.ctx_cache = st["ctx_main"]
-        o.cfg_ddim_step(pred, latents, st["coef"][i], B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1], cfg=st["cfg"],
-                        guidance=st["guidance"], pred_type=self.tables.pred_type, clip_sample=self.clip_sample,
-                        pred_single=single, video_scale=st.get("video_scale", 0.0),
-                        variance_noise=variance_noise, sigma=st["sigma"][i] if variance_noise is not None else 0.0,
-                        clipped_model_output=use_clipped_model_output)
+        kw = dict(B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1], cfg=st["cfg"],
+                  guidance=st["guidance"], pred_type=self.tables.pred_type, clip_sample=self.clip_sample,
+                  pred_single=single, video_scale=st.get("video_scale", 0.0),
+                  variance_noise=variance_noise, sigma=st["sigma"][i] if variance_noise is not None else 0.0,
+                  clipped_model_output=use_clipped_model_output)
+        phi = check_guidance_rescale(guidance_rescale)
+        if phi > 0 and not st["cfg"]:
+            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        if phi > 0:             # two more launches (moments, factor) in front of the step; an ops object without the method cannot run it
+            o.cfg_ddim_step_rescaled(pred, latents, st["coef"][i], guidance_rescale=phi, **kw)
+        else:
+            o.cfg_ddim_step(pred, latents, st["coef"][i], **kw)
 
     @torch.no_grad()
     def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float,
@@ -130,7 +168,7 @@ class DDIMSampler:
                ip_tokens: Optional[Tensor] = None, callback: Optional[Callable] = None, callback_steps: int = 1,
                use_graph: Optional[bool] = None, video_scale: float = 0.0, first_frame_condition: bool = False,
                eta: float = 0.0, generator=None, use_clipped_model_output: bool = False,
-               camera: Optional[Sequence[float]] = None) -> Tensor:
+               camera: Optional[Sequence[float]] = None, guidance_rescale: float = 0.0) -> Tensor:
         """use_graph: replay steps 1..n-1 from one captured hipGraph (None = the FYC_HIPGRAPH environment switch, default off).
         Measured on MI355X it buys nothing: at cfg2 the loop is GPU-bound (56 ms of kernels per step) and even the 2-D
         one-frame case (13.7 ms / step, ~700 small kernels) is bound by the kernels' own execution, not by launch overhead
@@ -144,8 +182,9 @@ class DDIMSampler:
             # mask for ALL frames = clamp(first_images_mask[:, :, 0:1]) (reference :632-635)
             mask = first_images_mask.to(u.device, torch.float32)[:, :, 0].reshape(B, 1, H * W).contiguous()
         st = self.prepare(text_embeddings, num_steps, B, guidance_scale, fps, flow, ip_tokens, video_scale=video_scale, frames=F,
-                          first_frame_condition=first_frame_condition, eta=eta, camera=camera)
-        ts = st["timesteps"].tolist()
+                          first_frame_condition=first_frame_condition, eta=eta, camera=camera, guidance_rescale=guidance_rescale,
+                          use_clipped_model_output=use_clipped_model_output)
+        ts, phi = st["timesteps"].tolist(), st["guidance_rescale"]
         if use_graph is None:
             use_graph = os.environ.get("FYC_HIPGRAPH", "0") == "1"
         if eta > 0:
@@ -157,13 +196,13 @@ class DDIMSampler:
                     # drawn exactly as the reference's scheduler draws it (scheduling_ddim.py:355-361): on the latents' device, in
                     # their dtype, from the caller's generator (or the device's global one)
                     noise = torch.randn(latents.shape, generator=generator, device=latents.device, dtype=latents.dtype)
-                self.step(st, i, latents, first, mask, variance_noise=noise, use_clipped_model_output=use_clipped_model_output)
+                self.step(st, i, latents, first, mask, variance_noise=noise, use_clipped_model_output=use_clipped_model_output, guidance_rescale=phi)
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, latents)
             return latents
         # Step 0 runs eagerly (it is also the warm-up: lazily set kernel attributes, allocator pools); step 1 is captured
         # reading its time-embedding row and DDIM coefficients from two fixed buffers, which are refreshed before every replay.
-        self.step(st, 0, latents, first, mask, use_clipped_model_output=use_clipped_model_output)
+        self.step(st, 0, latents, first, mask, use_clipped_model_output=use_clipped_model_output, guidance_rescale=phi)
         if callback is not None:
             callback(0, ts[0], latents)
         temb_cur, coef_cur = torch.empty_like(st["temb"][0]), torch.empty_like(st["coef"][0])
@@ -172,7 +211,7 @@ class DDIMSampler:
         side = torch.cuda.Stream(device=u.device)
         side.wait_stream(torch.cuda.current_stream(u.device))
         with torch.cuda.graph(graph, stream=side):
-            self.step(gst, 0, latents, first, mask, use_clipped_model_output=use_clipped_model_output)
+            self.step(gst, 0, latents, first, mask, use_clipped_model_output=use_clipped_model_output, guidance_rescale=phi)
         for i in range(1, num_steps):
             temb_cur.copy_(st["temb"][i])
             coef_cur.copy_(st["coef"][i])

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 from typing import List
 
+import numpy as np
 import torch
 
 from .config import DDIMConfig
@@ -52,9 +53,38 @@ class DDIMTables:
         self.pred_type = PRED_TYPES[cfg.prediction_type]
 
     def timesteps(self, num_inference_steps: int) -> torch.Tensor:
-        """set_timesteps (scheduling_ddim.py:238-252): arange(n) * (T // n), reversed, + steps_offset."""
-        ratio = self.cfg.num_train_timesteps // num_inference_steps
-        return (torch.arange(0, num_inference_steps, dtype=torch.int64) * ratio).flip(0) + self.cfg.steps_offset
+        """set_timesteps (scheduling_ddim.py:238-252): arange(n) * (T // n), reversed, + steps_offset ("leading", the reference's only
+        spacing).  "trailing" and "linspace" are those of later diffusers (arXiv:2305.08891 section 3.3), without steps_offset as there."""
+        spacing, T, n = self.cfg.timestep_spacing, self.cfg.num_train_timesteps, num_inference_steps
+        if spacing == "leading":
+            ratio = self.cfg.num_train_timesteps // num_inference_steps
+            return (torch.arange(0, num_inference_steps, dtype=torch.int64) * ratio).flip(0) + self.cfg.steps_offset
+        if spacing == "trailing":
+            ts = np.round(np.arange(T, 0, -T / n)) - 1
+        elif spacing == "linspace":
+            ts = np.round(np.linspace(0, T - 1, n))[::-1]
+        else:
+            raise ValueError(f"timestep_spacing given as {spacing!r} must be one of 'leading', 'trailing' or 'linspace'")
+        ts = ts.astype(np.int64)
+        # the float step of the trailing arange yields n + 1 entries ending in -1 for some n (61, 103, 121, ... with T = 1000): refused,
+        # not truncated - a schedule one entry short or long is another schedule
+        if len(ts) != n or (ts < 0).any():
+            raise ValueError(f"timestep_spacing {spacing!r} gives no valid schedule for num_inference_steps n = {n} with {T} training "
+                             f"timesteps ({len(ts)} entries, smallest {int(ts.min()) if len(ts) else None}): choose another n")
+        return torch.from_numpy(ts.copy())
+
+    def check_step(self, t: int, use_clipped_model_output: bool = False) -> None:
+        """A step at alphas_cumprod[t] = 0 (the first trailing step of a zero-terminal-SNR table) is x0 = sa x - sb v, eps = sa v + sb x
+        for v_prediction and x0 = v for sample: no division.  Epsilon prediction divides by sqrt(abar_t) = 0, and use_clipped_model_output
+        re-derives the direction as (x - sqrt(abar_t) x0) / sqrt(1 - abar_t), which no longer sees the clipped x0 at abar_t = 0 and divides
+        by zero at abar_t = 1: both are refused at such a timestep."""
+        a_t = float(self.alphas_cumprod[t])
+        if a_t == 0.0 and self.pred_type == PRED_TYPES["epsilon"]:
+            raise ValueError(f"timestep {t}: alphas_cumprod is 0 there (zero terminal SNR) and epsilon prediction divides by its square "
+                             "root; such a step needs prediction_type 'v_prediction' or 'sample'")
+        if use_clipped_model_output and (a_t == 0.0 or 1.0 - a_t == 0.0):
+            raise ValueError(f"timestep {t}: use_clipped_model_output cannot re-derive the noise direction where alphas_cumprod is "
+                             f"{a_t:g} ((x - sqrt(abar) x0) / sqrt(1 - abar))")
 
     def step_coefficients(self, t: int, num_inference_steps: int, eta: float = 0.0) -> List[float]:
         """{sqrt(abar_t), sqrt(1 - abar_t), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma} with sigma = eta * sqrt(variance_t)

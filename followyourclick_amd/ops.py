@@ -86,6 +86,7 @@ class HipOps:
         self._zero = None
         self._ws = None              # scratch for split-K GEMMs: one buffer, grown on demand (all work is on one stream)
         self._ws_need = {}           # (shape, flags) -> split-K scratch bytes (fyc_gemm_workspace_bytes), see gemm()
+        self._rescale_ws = None      # moments partials + factors of cfg_ddim_step_rescaled (its own buffer: a growing split-K scratch must not move it)
         self._q_cache = {}           # host-side layout queries (row parts, split bytes, statistics layout) per shape
         self._inited_dev = None
         self.f32_products = default_f32_products()      # "exact" | "split": the product rule of gemm(), attention() and temporal_attention() on f32 tensors (set_f32_products, resolve_f32_products)
@@ -537,6 +538,13 @@ class HipOps:
                       pred_single: Optional[Tensor] = None, video_scale: float = 0.0, variance_noise: Optional[Tensor] = None,
                       sigma: float = 0.0, clipped_model_output: bool = False) -> None:
         a = L.CfgDdimArgs()
+        self._fill_cfg_ddim(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_type, clip_sample, pred_single, video_scale,
+                            variance_noise, sigma, clipped_model_output)
+        self._call("fyc_cfg_ddim_step", a)
+
+    @staticmethod
+    def _fill_cfg_ddim(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_type, clip_sample, pred_single, video_scale,
+                       variance_noise, sigma, clipped_model_output) -> None:
         if variance_noise is not None and variance_noise.numel() != latents.numel():
             raise ValueError("cfg_ddim_step: variance_noise must have the latents' shape")
         a.variance_noise, a.sigma, a.clipped_model_output = _f32(variance_noise, "variance_noise"), float(sigma), int(clipped_model_output)
@@ -546,7 +554,28 @@ class HipOps:
         a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
         a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance = B, F, HW, c_latent, ld, int(cfg), guidance
         a.pred_type, a.clip_sample, a.dtype = pred_type, int(clip_sample), _dt(pred)
-        self._call("fyc_cfg_ddim_step", a)
+
+    def cfg_ddim_step_rescaled(self, pred: Tensor, latents: Tensor, coef: Tensor, *, guidance_rescale: float, B: int, F: int, HW: int,
+                               c_latent: int, ld: int, cfg: bool, guidance: float, pred_type: int, clip_sample: bool,
+                               pred_single: Optional[Tensor] = None, video_scale: float = 0.0, variance_noise: Optional[Tensor] = None,
+                               sigma: float = 0.0, clipped_model_output: bool = False) -> None:
+        """cfg_ddim_step with the guided prediction of every sample rescaled towards the standard deviation of its conditional prediction
+        (include/fyc.h, fyc_cfg_ddim_step_rescaled; guidance_rescale = 0 is cfg_ddim_step).  The moments workspace is this object's: sized by the
+        library's query per shape, one buffer kept (a fixed address under a captured graph) and grown on demand."""
+        self.ensure_init(pred.device)
+        r = L.CfgDdimRescaleArgs()
+        self._fill_cfg_ddim(r.step, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_type, clip_sample, pred_single,
+                            video_scale, variance_noise, sigma, clipped_model_output)
+        r.guidance_rescale = float(guidance_rescale)
+        key = ("cfg_rescale", B, F, HW, c_latent, ld, r.guidance_rescale > 0, bool(cfg))
+        need = self._ws_need.get(key)
+        if need is None:
+            need = self._ws_need[key] = int(self.lib.fyc_cfg_ddim_rescale_workspace_bytes(C.byref(r)))
+        if need > 0:
+            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
+                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+            r.workspace, r.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._call("fyc_cfg_ddim_step_rescaled", r)
 
     def nchw_to_nhwc(self, z: Tensor, x: Tensor, *, N: int, C_: int, HW: int, c_pad: int, scale: float) -> None:
         self.ensure_init(z.device)

@@ -29,7 +29,7 @@ extern "C" {
 /* ABI version = major * 100 + minor.  A host compiled against this header MUST compare fyc_version() with FYC_VERSION before its first
  * call and refuse a library whose MAJOR differs: argument structs grow at the end between majors (round 3 appended `wstream` to
  * fyc_temporal_block_args and widened the tuning table to 16 keys without bumping the number: a round-2 host would have passed a short
- * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off; 307 = the same rule for the fused spatial attention: f32_products APPENDED to fyc_attention's arguments - zero = off (every 16-bit launch is unchanged); FYC_F32 tensors are taken with FYC_PRODUCTS_SPLIT_BF16 only; 308 = causal mask and head dims up to 512 for the fused spatial attention, no struct changed: one new entry point, fyc_attention_masked, whose fyc_attn_mask_args is a fyc_attn_args followed by `causal` (zero = fyc_attention, call for call); fyc_attention itself takes head dims 160 < d <= 512 in multiples of 32 in every dtype it takes, and with d <= 160 every launch is unchanged. */
+ * struct whose missing tail the library reads as a pointer).  History: 100 = rounds 1-3 (see above), 200 = round 4, 201 = FYC_F16, 300 = round 5: fields were APPENDED to two argument structs - variance_noise / sigma / clipped_model_output behind the DDIM step's arguments, mode behind the UNet input's - a struct change, hence a new major: a 2xx host passes shorter structs whose missing tail this library would read; 301 = round 6, no struct change: fyc_gemm accepts chan_parts for problems it runs split-K (fyc_gemm_workspace_bytes() > 0; the finish kernel writes them in 128-row tiles, fyc_gemm_stat_layout answers for it), tile config 11, tuning keys 10-13; 302 = fyc_repeat; fields APPENDED to three argument structs - q_batch_mod behind the attention's arguments, parts1 .. parts_cs_rows behind fyc_gn_apply_cs's, gn_parts .. gn_slots behind fyc_panel_linear's - all zero = off; 303 = RoPE in the motion module: rope_cos / rope_sin APPENDED to the temporal attention's arguments - both NULL = off - which now takes frames <= 64; 304 = FYC_GEMM_CONV_T3 (the 3-tap convolution along the frame axis of TemporalConvBlock): t3_frames / t3_rows APPENDED to fyc_gemm's arguments - both zero = off; 305 = split-bf16 products for f32 operands: f32_products APPENDED to fyc_gemm's arguments - zero = off (FYC_PRODUCTS_EXACT); 306 = the same rule for the temporal attention: f32_products APPENDED to fyc_temporal_attention's arguments - zero = off; 307 = the same rule for the fused spatial attention: f32_products APPENDED to fyc_attention's arguments - zero = off (every 16-bit launch is unchanged); FYC_F32 tensors are taken with FYC_PRODUCTS_SPLIT_BF16 only; 308 = causal mask and head dims up to 512 for the fused spatial attention, no struct changed: one new entry point, fyc_attention_masked, whose fyc_attn_mask_args is a fyc_attn_args followed by `causal` (zero = fyc_attention, call for call); fyc_attention itself takes head dims 160 < d <= 512 in multiples of 32 in every dtype it takes, and with d <= 160 every launch is unchanged; 308, added entry points = guidance rescale for the fused guidance + DDIM step, no struct changed and no number bumped: fyc_cfg_ddim_step_rescaled and its query fyc_cfg_ddim_rescale_workspace_bytes, whose fyc_cfg_ddim_rescale_args is a fyc_cfg_ddim_args followed by guidance_rescale / workspace / workspace_bytes (guidance_rescale = 0 = fyc_cfg_ddim_step, call for call). */
 #define FYC_VERSION 308
 
 /* FYC_F16 (minor version 1): IEEE half storage with f32 accumulation - every op that takes FYC_BF16 takes it, same layouts, same
@@ -380,6 +380,26 @@ typedef struct {
   const float* variance_noise; float sigma; int32_t clipped_model_output;
 } fyc_cfg_ddim_args;
 int fyc_cfg_ddim_step(const fyc_cfg_ddim_args* a, void* stream);
+
+/* (308, added entry points) The same step with guidance rescale (arXiv:2305.08891 section 3.4; diffusers' rescale_noise_cfg, applied where
+ * diffusers applies it: on the guided prediction, before the prediction-type conversion).  Per batch sample b, over that sample's
+ * c_latent * F * HW values (pad channels of the ld-strided rows are never counted):
+ *   v        = the guided prediction exactly as fyc_cfg_ddim_step forms it (u + g (c - u), or the three-term form with pred_single)
+ *   s_text_b = std(c over sample b), s_cfg_b = std(v over sample b)          (unbiased, n - 1: torch.std's default)
+ *   v'       = v * (guidance_rescale * s_text_b / s_cfg_b + (1 - guidance_rescale))
+ * and fyc_cfg_ddim_step's conversion, clip_sample, clipped_model_output, update and eta noise run unchanged on v'.  Two passes over pred: a
+ * moments pass (each block owns a fixed run of rows of one sample and writes {sum c, sum c^2, sum v, sum v^2} in f64 to the workspace), a
+ * one-block-per-sample fold of those partials in index order that forms the factor in f64 and rounds it once to f32, then the step kernel
+ * with  v *= factor[b]  behind the guidance line.  No atomics: the same call gives the same bits.  A sample whose guided prediction is
+ * constant (s_cfg_b = 0) keeps the factor 1.
+ * guidance_rescale == 0 is fyc_cfg_ddim_step(&step, stream) call for call (workspace may be NULL).  A value in (0, 1] needs step.cfg == 1,
+ * at least two values per sample, fyc_init() and an 8-byte aligned device workspace of fyc_cfg_ddim_rescale_workspace_bytes() bytes
+ * (contents undefined before and after the call).  A value outside [0, 1] or NaN, cfg == 0 with a positive value, and a NULL, misaligned
+ * or short workspace are refused before anything is launched.  The query launches nothing and returns 0 for guidance_rescale == 0 or
+ * arguments the step would refuse. */
+typedef struct { fyc_cfg_ddim_args step; float guidance_rescale; void* workspace; int64_t workspace_bytes; } fyc_cfg_ddim_rescale_args;
+int64_t fyc_cfg_ddim_rescale_workspace_bytes(const fyc_cfg_ddim_rescale_args* a);
+int fyc_cfg_ddim_step_rescaled(const fyc_cfg_ddim_rescale_args* a, void* stream);
 
 /* VAE ends: z (N,4,h,w) f32 * scale -> channels-last [N][hw][c_pad];
  * image channels-last [N][HW][ld] -> (N,3,H,W) f32 = clamp(x/2+0.5, 0, 1) (pipeline_animation.py:402,410) */
