@@ -67,13 +67,12 @@ template <> struct AttnMma<f16_t> {
   }
 };
 
-#ifndef FYC_ATTN_BUILTIN_ISSUE
 // The (up to) four exec-masked DMAs of a full K / V^T tile as ONE statement: the lane masks are computed once per kernel (SGPR pairs), a DMA
 // whose mask is empty in this wave is branched over (so that the counted vmcnt waits stay exact), M0 and EXEC leave as they came.  The
 // compiler's form - v_cmp + s_and_saveexec + s_cbranch + 64-bit address add + s_mov m0 + s_nop + DMA + s_or exec per DMA - is ~50 instructions
 // per tile, ~35 of them SALU, in a loop that is bound by instruction issue (profiles/r05_attention_pmc.txt); this is 24.  Measured
 // (profiles/r05_attention_instruction_diet_ab.txt, d = 40, N = 4096): 665 -> 693 TFLOP/s without the s_setprio pairs and the sNaN-quieting
-// maxima, -> 708-717 with this statement.  -DFYC_ATTN_BUILTIN_ISSUE rebuilds the compiler's form.
+// maxima, -> 708-717 with this statement.
 __device__ __forceinline__ void dma4_masked(unsigned long long m0_, unsigned long long m1_, unsigned long long m2_, unsigned long long m3_,
                                             unsigned o0, unsigned o1, unsigned o2, unsigned o3,
                                             const char* b0, const char* b1, const char* b2, const char* b3,
@@ -91,16 +90,10 @@ __device__ __forceinline__ void dma4_masked(unsigned long long m0_, unsigned lon
                  [ba] "s"(b0), [bb] "s"(b1), [bc] "s"(b2), [bd] "s"(b3), [la] "s"(l0), [lb] "s"(l1), [lc] "s"(l2), [ld] "s"(l3)
                : "memory");
 }
-#endif
 
 // Round 5: the loop is bound by instruction ISSUE (profiles/r05_attention_pmc.txt: 150 instructions per 21 MFMAs, three waves per SIMD whose
 // issue-active time adds up to the kernel's duration), so instructions that only re-order work between the waves of a SIMD are pure cost:
-// the s_setprio pairs around the MFMA groups (8 per 64-key tile) are compiled in only with -DFYC_ATTN_SETPRIO.
-#ifdef FYC_ATTN_SETPRIO
-#define FYC_ATTN_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define FYC_ATTN_PRIO(x) do { } while (0)
-#endif
+// the s_setprio pairs that used to stand around the MFMA groups (8 per 64-key tile) are gone (profiles/r05_attention_instruction_diet_ab.txt).
 
 // max over the 4 lane quads that share a query column: xor 16 inside each 32-lane half (ds_swizzle bit mode, no LDS
 // traffic), then across the halves (v_permlane32_swap)
@@ -180,7 +173,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
     my_loads += __builtin_amdgcn_ballot_w64(v_off[it] != NODATA) != 0 ? 1 : 0;
   }
   my_loads = __builtin_amdgcn_readfirstlane(my_loads);
-#ifndef FYC_ATTN_BUILTIN_ISSUE
   unsigned long long dmask[4] = {0ull, 0ull, 0ull, 0ull};      // data lanes of the (K_IT + V_IT <= 4) DMAs of a full tile, this wave
   if (K_IT + V_IT <= 4) {
 #pragma unroll
@@ -189,7 +181,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
     for (int it = 0; it < V_IT; ++it) dmask[K_IT + it] = __builtin_amdgcn_ballot_w64(v_off[it] != NODATA);
   }
   const unsigned lds_ring = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-#endif
   char* const offs_lds = smem + NS * STAGE + tid * 16;
   if (OFFS_IN_LDS) {
     u32x4 o4 = {NODATA, NODATA, NODATA, NODATA};
@@ -219,7 +210,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
     char* sV = sK + K_BYTES;
     const char* kb = reinterpret_cast<const char*>(K) + (long long)tile * (KB * 2) * p.d;
     const char* vb = reinterpret_cast<const char*>(VT) + (long long)tile * (KB * 2);
-#ifndef FYC_ATTN_BUILTIN_ISSUE
     if constexpr (OFFS_IN_LDS) {
       const u32x4 o4 = *reinterpret_cast<const u32x4*>(offs_lds);
       const unsigned lk = lds_ring + stage * STAGE + wave * 1024, lv = lk + K_BYTES;
@@ -228,7 +218,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
       dma4_masked(dmask[0], dmask[1], dmask[2], dmask[3], o4[0], o4[1], o4[2], o4[3], base(0), base(1), base(2), base(3), ldst(0), ldst(1), ldst(2), ldst(3));
       return;
     }
-#endif
     unsigned ko[K_IT], vo[V_IT];
     if (OFFS_IN_LDS) {
       const u32x4 o4 = *reinterpret_cast<const u32x4*>(offs_lds);
@@ -386,7 +375,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
           kt4[t] = *reinterpret_cast<const s16x4*>(kr[t] + (KXOR ? (chunk ^ (krow & 7)) : chunk) * 16 + (g & 1) * 8);
         }
       }
-      FYC_ATTN_PRIO(1);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -409,7 +397,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) s[t][qt] = AttnMma<T>::k32(kf[ks], qf[qt][ks], s[t][qt]);
       }
-      FYC_ATTN_PRIO(0);
     };
     auto softmax_pv = [&](int kb, f32x4 (&s)[2][QT], f32x4 (&sn)[2][QT], bool has_next) {
       // ---- online softmax; lane holds keys kb*32 + 8g + 4t + r of query r16.  MSUB: s already is score - m_run.
@@ -493,7 +480,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
         pf[qt] = __builtin_bit_cast(Frag, pk);
       }
       // ---- O^T += V^T P^T  (row d of V^T is all ones: O^T[d] accumulates the row sums)
-      FYC_ATTN_PRIO(1);
 #pragma unroll
       for (int dv = 0; dv < DVT; ++dv) {
         const int vrow = dv * 16 + r16;
@@ -502,7 +488,6 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) o[qt][dv] = AttnMma<T>::k32(vf, pf[qt], o[qt][dv]);
       }
-      FYC_ATTN_PRIO(0);
     };
     const int nb = STEADY ? 2 : ((tile * KB + 32 < p.n_k) ? 2 : 1);      // 32-key blocks of this tile that hold keys (uniform)
     f32x4 s0[2][QT], s1[2][QT];
@@ -519,9 +504,7 @@ __global__ void __launch_bounds__(256, (DP16 == 3 && DVT == 3 && QT == 3) ? 3 : 
   };
   const int n_steady = nfull > 2 ? nfull - 2 : 0;          // tiles t with t + 2 < nfull
   int tile = 0;
-#ifndef FYC_ATTN_ONE_LOOP
   for (; tile < n_steady; ++tile) tile_body(tile, std::true_type());
-#endif
   for (; tile < ntiles; ++tile) tile_body(tile, std::false_type());
 
   // ---- epilogue: lane holds O[query r16][dv*16 + 4g + r]; l = O^T[d] sits in quad (d%16)/4, register 0 of the last block

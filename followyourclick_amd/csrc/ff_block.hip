@@ -80,16 +80,11 @@ struct FFP {
 };
 
 // LDS-DMA, MFMA, fragment read and lane-half sum: row_panel.h, with the rules they follow
-using rp::dma16x4; using rp::dma16v; using rp::dma_landed_barrier; using rp::mfma; using rp::frag;
+using rp::dma16x4; using rp::dma16v; using rp::dma_landed_barrier; using rp::mfma; using rp::frag; using rp::halves_sum;
 __device__ __forceinline__ void half_landed_barrier() {      // all but this wave's newest half (4 GPW loads) have landed, then the workgroup meets
   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * GPW) : "memory");
   __syncthreads();
 }
-#ifdef FF_BPERMUTE                                              // the racing form of row_panel.h::halves_sum (profiles/r03_ff_block_race.txt)
-__device__ __forceinline__ float halves_sum(float v) { return v + __shfl_xor(v, 32); }
-#else
-using rp::halves_sum;
-#endif
 
 #ifdef FF_TIMING                                                // phase timestamps of wave 0 of every workgroup (tools/ff_probe.py prints them)
 __device__ unsigned long long g_ff_time[1024 * 16];
@@ -119,9 +114,6 @@ __global__ void __launch_bounds__(NT) ff_block_kernel(const FFP p) {
   // n-th group of four pieces of this wave of half h (n < GPW): group wave + NW n; every wave issues exactly 4 GPW loads per
   // half, so "everything but the newest half has landed" is the constant s_waitcnt vmcnt(4 GPW)
   auto dma_group = [&](int h, int n) {
-#ifdef FF_NO_DMA
-    if (h >= 2) return;                                       // ablation build (tools/ff_probe.py): no weight stream, wrong results
-#endif
     const int grp = wave + NW * n;
     dma16x4(p.ws + (long long)h * HALF_BYTES + grp * (4 * PIECE), lane16, lds0 + (h & (NSLOT - 1)) * HALF_BYTES + grp * (4 * PIECE));
   };

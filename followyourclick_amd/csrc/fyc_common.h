@@ -39,13 +39,13 @@ enum FycTuningKey {
   FYC_TUNE_NO_STAGGER = 5,         // 1: no wave-role stagger in the 8-wave GEMM tiles
   FYC_TUNE_NO_WIDE_EPILOGUE = 6,   // 1: no LDS-staged wide epilogues
   FYC_TUNE_NO_WIDE_HEADS = 7,      // 1: no wide head-split epilogue
-  FYC_TUNE_PP_NO_SETPRIO = 8,      // FYC_GEMM_VARIANTS builds: no s_setprio in the ping-pong loop
-  FYC_TUNE_GEMM_LOOP = 9,          // FYC_GEMM_VARIANTS builds: 2 = ping-pong loop, 3 = overlapped-epilogue kernel
+  FYC_TUNE_RESERVED_8 = 8,         // reserved, ignored (the round-4 main-loop experiments, retired)
+  FYC_TUNE_RESERVED_9 = 9,         // reserved, ignored (the same)
   FYC_TUNE_SPLITK_MIN_KT = 10,     // v > 0: split-K keeps v K tiles per slice, from K >= 128 v and N >= 128
   FYC_TUNE_PHASE_DELAY = 11,       // v > 0: every other GEMM block of an XCD starts v x 1024 cycles late
   FYC_TUNE_NO_PRESTAGE = 12,       // 1: the GEMM epilogues load their per-row / per-column inputs themselves
   FYC_TUNE_GENERIC_PASS1 = 13,     // 1: the generic pass 1 of the packed LINEAR epilogue
-  FYC_TUNE_MI32 = 14,              // FYC_GEMM_MI32 builds: 1 = the 32x32x16 matrix instruction in the 256-row tiles
+  FYC_TUNE_RESERVED_14 = 14,       // reserved, ignored (the 32x32x16 main loop, retired)
   FYC_TUNE_HEADS_PACKED = 15,      // 1 / 2: the pack-first head-split epilogue on / off for every problem
   FYC_TUNE_KEYS = 16
 };

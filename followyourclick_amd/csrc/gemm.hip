@@ -1,8 +1,5 @@
 // Host entry of the GEMM family: argument validation, plan (gemm_plan.h), dispatch.
 // Kernel template: gemm_kernel.h; instantiations: gemm_{bf16,f16}_{plain,conv,act,t3}.hip, gemm_f32.hip, gemm_f32_t3.hip, gemm_f32x3.hip, gemm_f32x3_t3.hip.
-// The round-4 main-loop experiments that measured slower on every shape (ping-pong wave groups, tile configs 21 / 22 / 23; epilogue
-// under the next tile's K loop, config 31) live in tools/exp/gemm_variants/ and are only part of a library built with
-// FYC_GEMM_VARIANTS=1 (python -m followyourclick_amd._build; tests: tools/exp/gemm_variants/test_gemm_variants_gpu.py).
 #include "gemm_plan.h"
 
 using namespace fycg;
@@ -111,10 +108,6 @@ __global__ void __launch_bounds__(256) splitk_finish_stats_kernel(const float* _
 
 // the kernel entry of a plan's family; `products`: fyc_gemm_args::f32_products - the plan is the same for both rules, only the instantiation differs
 int run(const GemmPlan& pl, const GemmP& p, int products, int batch, hipStream_t st) {
-#ifdef FYC_GEMM_VARIANTS
-  if (pl.loop == GEMM_LOOP_OV) return run_ov(p, pl.cfg, st);
-  if (pl.loop == GEMM_LOOP_PP) return pl.family == GEMM_FAM_PLAIN ? run_pp_plain(p, pl.cfg, st) : run_pp_conv(p, pl.cfg, st);
-#endif
   if (pl.dtype == FYC_F32) {
     const int cfg = pl.cfg | (products == FYC_PRODUCTS_SPLIT_BF16 ? CFG_F32X3 : 0);
     return pl.family == GEMM_FAM_T3 ? run_f32_t3(p, batch, cfg, st) : run_f32(p, batch, cfg, st);

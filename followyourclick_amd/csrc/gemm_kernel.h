@@ -163,62 +163,6 @@ template <> struct Mma<f32x3_t> {
   }
 };
 
-// ---- 32x32x16 main loop (round 6) ----------------------------------------------------------------------------------------------------------
-// v_mfma_f32_32x32x16_{bf16,f16} is a 32-cycle instruction: half as many matrix instructions per K tile as the 16x16x32 form, and every one
-// covers twice as many issue cycles of the partner wave's DMA / LDS instructions (profiles/r03_mfma_fill_microbench.txt: a wave interleaving
-// LDS reads gets 26 cycles per 16 cycles of matrix work with it against 41 with the 16-cycle form).  Used as D^T = W x^T like the 16x16 form:
-// a lane of the 32x32 block holds output row m = lane % 32 and columns n = 8 q + 4 (lane / 32) + e for register 4 q + e.
-// The epilogues are written for the 16x16 layout (lane = 16 g + r: row r, columns 4 g + e of a 16x16 block); acc32_to_acc16 re-sorts a block in
-// registers with gfx950's v_permlane32_swap / v_permlane16_swap: (lane bit 5, lane bit 4, register bit q0) of the 32x32 layout are
-// (h, row bit 4, column bit 3); the 16x16 layout wants (column bit 3, h, -) in the lane and row bit 4 in the register index - a 3-cycle
-// of one register bit and two lane bits = the two swaps.  16 VALU instructions per 32x32 block, no LDS.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <typename T> struct Mma32;
-template <> struct Mma32<bf16_t> {
-  __device__ static __forceinline__ f32x16 mma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma32<f16_t> {
-  __device__ static __forceinline__ f32x16 mma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma32<float> {     // (never instantiated with MI = 32: the f32 parity mode keeps v_mfma_f32_16x16x4_f32)
-  __device__ static __forceinline__ f32x16 mma(f32x4, f32x4, f32x16 c) { return c; }
-};
-// X = {X.lo, Y.lo}, Y = {X.hi, Y.hi} (halves of 32 lanes) / X = {X.r0, Y.r0, X.r2, Y.r2}, Y = {X.r1, Y.r1, X.r3, Y.r3} (rows of 16 lanes)
-__device__ __forceinline__ void swap32(float& x, float& y) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  x = __uint_as_float(r[0]); y = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void swap16(float& x, float& y) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  x = __uint_as_float(r[0]); y = __uint_as_float(r[1]);
-}
-// one 32x32 block -> its four 16x16 blocks o[im][jn] (rows 16 im.., columns 16 jn..)
-__device__ __forceinline__ void acc32_to_acc16(const f32x16& c, f32x4& o00, f32x4& o01, f32x4& o10, f32x4& o11) {
-#pragma unroll
-  for (int q1 = 0; q1 < 2; ++q1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float x = c[8 * q1 + e], y = c[8 * q1 + 4 + e];      // q0 = 0 / 1
-      swap32(x, y);                                          // lane bit 5 <-> q0: registers now indexed by h
-      swap16(x, y);                                          // lane bit 4 <-> h:  registers now indexed by row bit 4
-      if (q1 == 0) { o00[e] = x; o10[e] = y; } else { o01[e] = x; o11[e] = y; }
-    }
-  }
-}
-// the inverse (residual tile loaded in the 16x16 layout -> 32x32 accumulators)
-__device__ __forceinline__ void acc16_to_acc32(f32x16& c, const f32x4& o00, const f32x4& o01, const f32x4& o10, const f32x4& o11) {
-#pragma unroll
-  for (int q1 = 0; q1 < 2; ++q1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float x = q1 == 0 ? o00[e] : o01[e], y = q1 == 0 ? o10[e] : o11[e];
-      swap16(x, y);
-      swap32(x, y);
-      c[8 * q1 + e] = x; c[8 * q1 + 4 + e] = y;
-    }
-  }
-}
-
 __device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
@@ -241,10 +185,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 
 // swizzle key of an LDS row: 128-B rows (8 chunks) use row&7; 64-B rows (4 chunks) use a 4-entry table over (row>>2)&3 -
 // both make the ds_read_b128 of 16 consecutive rows x one chunk conflict-free under the real 16-lane service groups
-template <int RB, int MI = 16> __device__ __forceinline__ int swz_key(int row) {
-  // 32x32x16 fragments: a 16-lane service group of ds_read_b128 holds 16 DIFFERENT rows (8 even, 8 odd) x ONE chunk - (row >> 1) & 7 gives the
-  // 8 rows of a parity 8 different chunk slots in every group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31}); row & 7 would pair rows 0 | 24, 12 | 20, ...
-  if (MI == 32) return (row >> 1) & 7;
+template <int RB> __device__ __forceinline__ int swz_key(int row) {
   if (RB == 128) return row & 7;
   return (0x78 >> (((row >> 2) & 3) * 2)) & 3;   // {0, 2, 3, 1}
 }
@@ -391,13 +332,6 @@ __device__ __forceinline__ void epilogue_linear_packed(const GemmP& p, f32x4 (&a
                                                        long long bz, char* stg_stage, int wave, int lane, const char* pre, int& ecnt) {
   static_assert(sizeof(T) == 2, "16-bit outputs only (bf16 / f16)");
   constexpr int WTM = BM / WGM / 16, WTN = BN / WGN / 16;
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 3      // TIMING BUILDS (wrong results), tools/gpu_r6.sh epi_ablation: 3 = no epilogue at all
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) asm volatile("" :: "v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]));
-  return;
-#endif
   constexpr bool LN = (MODE == FYC_GEMM_PLAIN);
   constexpr int PITCH = WTN * 32 + 16;               // bytes per staged row: the wave's WTN * 16 bf16 columns + 16 (keeps the 16-byte reads aligned)
   constexpr int CPR = WTN * 2;                       // 16-byte chunks per staged row
@@ -534,13 +468,6 @@ __device__ __forceinline__ void epilogue_linear_packed(const GemmP& p, f32x4 (&a
     __builtin_amdgcn_sched_barrier(0);
   }
   }
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 2      // 2 = pass 1 only (final values packed in registers, nothing staged or stored)
-#pragma unroll
-  for (int i = 0; i < WTM; ++i)
-#pragma unroll
-    for (int j = 0; j < WTN; ++j) asm volatile("" :: "v"(pk[i][j][0]), "v"(pk[i][j][1]));
-  return;
-#endif
   FYC_STAMP_E(p, wave, lane, ecnt);
   // ---- pass 2: 16 rows x (WTN * 16) columns per step through the wave's staging slice ---------------------------------------------
   const int lrow = lane / CPR, lch = lane - lrow * CPR;
@@ -589,42 +516,27 @@ __device__ __forceinline__ void epilogue_linear_packed(const GemmP& p, f32x4 (&a
 #pragma unroll
     for (int j = 0; j < WTN; ++j) *reinterpret_cast<u32x2*>(stg + r16 * PITCH + j * 32 + g * 8) = pk[i][j];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // round 6: ALL reads of the block first, by every lane (rows clamped into the staged block), ONE wait, then the predicated stores -
-    // inside the `if (live)` each of the NQ reads was followed by its own lgkmcnt(0): 24 exposed LDS round trips per 256x320 tile and wave
-    // (in groups of at most QG reads: all six of the 256x320 tile at once cost its kernels 60 more bytes of scratch and the convolutions 1.5 %)
-    // (QG = 1: read, wait, store - the round-5 order.  Batching the reads of a block - all NQ, or groups of 3 - measured 5-7 % faster on the
-    // short-K linears in the cold-operand probe and 0.1 ms per DDIM step SLOWER in the pipeline, where the convolutions' epilogues lost more than
-    // the linears' gained: profiles/r06_gemm_epilogue_ab.txt.  -DFYC_P2_QG=n rebuilds the batched form.)
-#ifdef FYC_P2_QG
-    constexpr int QG = FYC_P2_QG;
-#else
-    constexpr int QG = 1;
-#endif
+    // round 6: the read of a store step by every lane (rows clamped into the staged block), outside the `if (live)`, then its wait and the
+    // predicated store.  Batching the reads of a block - all NQ, or groups of 3 - measured 5-7 % faster on the short-K linears in the
+    // cold-operand probe and 0.1 ms per DDIM step SLOWER in the pipeline, where the convolutions' epilogues lost more than the linears'
+    // gained (all six reads of the 256x320 tile at once: 60 more bytes of scratch): profiles/r06_gemm_epilogue_ab.txt
+    // (the shape of this loop body - the read in a scope of its own, `v4` copied inside the branch - is the one that leaves hipcc's instruction
+    // streams as they were measured: tools/device_asm_diff.py)
 #pragma unroll
-    for (int q0 = 0; q0 < NQ; q0 += QG) {
-    u32x4 v4q[QG];
-#pragma unroll
-    for (int qq = 0; qq < QG; ++qq) {
-      const int q = q0 + qq;
-      const int rowc = (q * RPP + lrow) < 15 ? (q * RPP + lrow) : 15;
-      if (q < NQ) v4q[qq] = *reinterpret_cast<const u32x4*>(stg + rowc * PITCH + lch * 16);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int qq = 0; qq < QG; ++qq) {
-      const int q = q0 + qq;
-      if (q >= NQ) continue;
+    for (int q = 0; q < NQ; ++q) {
+      u32x4 v4q;
+      {
+        const int rowc = (q * RPP + lrow) < 15 ? (q * RPP + lrow) : 15;
+        v4q = *reinterpret_cast<const u32x4*>(stg + rowc * PITCH + lch * 16);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const int row = q * RPP + lrow;
       const int m = tile_m * BM + (wm * WTM + i) * 16 + row;
       float rsum = 0.f, rsq = 0.f;
       const bool live = lact && row < 16 && m < p.M && n_lane < p.N;
       if (live) {
-        const u32x4 v4 = v4q[qq];
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 1      // 1 = everything but the global stores
-        asm volatile("" :: "v"(v4[0]), "v"(v4[1]), "v"(v4[2]), "v"(v4[3]));
-#else
+        const u32x4 v4 = v4q;
         *reinterpret_cast<u32x4*>(O + (long long)m * p.ldo + n_lane) = v4;   // (nt stores: same GEMM time, consumers +10 %: profiles/r04_epilogue_nontemporal_ab.txt)
-#endif
         if (do_cs || do_rp) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -641,7 +553,6 @@ __device__ __forceinline__ void epilogue_linear_packed(const GemmP& p, f32x4 (&a
         float* dst = racc + ((wm * WTM + i) * 16 + row) * 2;
         lds_add(dst, rsum); lds_add(dst + 1, rsq);
       }
-    }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
@@ -899,12 +810,8 @@ __device__ __forceinline__ void load_residual_acc(const GemmP& p, f32x4 (&acc)[B
   // fetched in PAIRS with 16 bytes per lane (lane g of a row: columns 32 jp + 8 g .. + 7, i.e. 16 rows x 64 contiguous bytes per instruction, half as
   // many instructions) and re-sorted in registers to the accumulator layout: (lane bit 5, lane bit 4, dword pair) = (block of the pair, half of the
   // block, quarter of the half) must become (half, quarter, block) - v_permlane16_swap then v_permlane32_swap on the dword pairs (0, 2) and (1, 3).
-  // Same values, same conversion: bitwise the results of the 8-byte form (-DFYC_RES_LOAD8 rebuilds it).
-#ifdef FYC_RES_LOAD8
-  constexpr int NP = 0;
-#else
+  // Same values, same conversion: bitwise the results of the 8-byte form (A/B: profiles/r06_gemm_residual_load_ab.txt).
   constexpr int NP = WTN / 2;                          // column-block pairs; an odd last block keeps the 8-byte form
-#endif
   u32x4 raw16[WTM][NP > 0 ? NP : 1];
   u32x2 raw[WTM][WTN - 2 * NP > 0 ? WTN - 2 * NP : 1];
 #pragma unroll
@@ -959,13 +866,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
   const T* R = reinterpret_cast<const T*>(p.residual);
   if constexpr (WIDE && EPI == FYC_EPI_HEADS && sizeof(T) == 2) {
     if (p.fast1 && p.heads_pk) {
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 3      // timing build: no epilogue (the accumulators stay alive)
-#pragma unroll
-      for (int i = 0; i < WTM; ++i)
-#pragma unroll
-        for (int j = 0; j < WTN; ++j) asm volatile("" :: "v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]));
-      return;
-#endif
       epilogue_heads_packed<T, BM, BN, WGM, WGN, STG_BYTES, MODE>(p, acc, tile_m, tile_n, stg_stage, wave, lane, pre);
       return;
     }
@@ -979,13 +879,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
     constexpr int JG = (WTN + 1) / 2;
     constexpr int PITCH = JG * 64 + 16;
     static_assert(WGM * WGN * 16 * PITCH + 2 * BN * 4 <= STG_BYTES, "staging + column constants must fit in one ring stage");
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 3      // timing build: no epilogue (the accumulators stay alive)
-#pragma unroll
-    for (int i = 0; i < WTM; ++i)
-#pragma unroll
-      for (int j = 0; j < WTN; ++j) asm volatile("" :: "v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]));
-    return;
-#endif
     __builtin_amdgcn_s_barrier();
     char* stg = stg_stage + wave * (16 * PITCH);
     float* colc = reinterpret_cast<float*>(stg_stage + WGM * WGN * 16 * PITCH);
@@ -1061,13 +954,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
   }
   if constexpr (WIDE && EPI == FYC_EPI_GEGLU && sizeof(T) == 2) {
     if (p.fast1) {
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 3      // timing build: no epilogue (the accumulators stay alive)
-#pragma unroll
-      for (int i = 0; i < WTM; ++i)
-#pragma unroll
-        for (int j = 0; j < WTN; ++j) asm volatile("" :: "v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]));
-      return;
-#endif
       epilogue_geglu_packed<T, BM, BN, WGM, WGN, STG_BYTES, MODE>(p, acc, tile_m, tile_n, bz, stg_stage, wave, lane, pre);
       return;
     }
@@ -1083,13 +969,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
     constexpr int JG = (OT + 1) / 2;                   // output tiles per pass
     constexpr int PITCH = JG * 64 + 16;                // bytes per staged row (f32), +16 keeps ds_write_b128 conflict-free
     static_assert(WGM * WGN * 16 * PITCH + 2 * BN * 4 <= STG_BYTES, "staging + column constants must fit in one ring stage");
-#if defined(FYC_ABL_EPI) && FYC_ABL_EPI == 3      // timing build: no epilogue (the accumulators stay alive)
-#pragma unroll
-    for (int i = 0; i < WTM; ++i)
-#pragma unroll
-      for (int j = 0; j < WTN; ++j) asm volatile("" :: "v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]));
-    return;
-#endif
     __builtin_amdgcn_s_barrier();                      // every wave is done reading the stage we reuse
     char* stg = stg_stage + wave * (16 * PITCH);
     const int n_w0 = tile_n * BN + wn * WTN * 16;      // first GEMM column of this wave
@@ -1364,8 +1243,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
   }  // !WIDE
 }
 
+template <int S> using KStep = std::integral_constant<int, S>;
 // P: the product rule, T's own except for f32x3_t on float storage
-template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, int MI = 16, typename P = T>
+template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, typename P = T>
 __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) {
   typedef Mma<P> Tr;
   typedef typename Tr::Frag Frag;
@@ -1378,10 +1258,8 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   constexpr int LOADS = A_IT + B_IT;       // DMA instructions per thread per K tile
   constexpr int WTM = BM / WGM / 16, WTN = BN / WGN / 16;
   static_assert(EPI != FYC_EPI_GEGLU || WTN % 2 == 0, "GEGLU pairs value / gate column blocks inside a wave");
-  constexpr bool M32 = (MI == 32);       // 32x32x16 matrix instruction in the K loop (16-bit operands, 128-byte K tiles, even block counts)
-  static_assert(MI == 16 || (MI == 32 && sizeof(T) == 2 && RB == 128 && WTM % 2 == 0 && WTN % 2 == 0), "32x32x16 main loop: 16-bit operands, wave tile of whole 32x32 blocks");
   constexpr bool SPLIT3 = std::is_same<P, f32x3_t>::value;      // split-bf16 products of f32 operands (Mma<f32x3_t>)
-  static_assert(std::is_same<P, T>::value || (SPLIT3 && std::is_same<T, float>::value && RB == 128 && MI == 16 && WGM * WGN == 4),
+  static_assert(std::is_same<P, T>::value || (SPLIT3 && std::is_same<T, float>::value && RB == 128 && WGM * WGN == 4),
                 "f32x3: float storage, one 32-float K tile per matrix instruction, the 4-wave tiles of the f32 mode");
   constexpr int A_BYTES = BM * RB, STAGE = (BM + BN) * RB;
   constexpr bool STAGGER = (WGM * WGN == 8) && KSTEPS >= 2 && NS == 2;
@@ -1416,7 +1294,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   // K offset is the same for every `it` and for both operands.  Addresses are rebuilt from (tile, it) at issue time (a few
   // VALU ops per 1 KiB DMA); only the conv gather keeps per-row state (pixel base and packed top-left tap position).
   const int lrow = tid / CPR;
-  const int koff = ((tid % CPR) ^ swz_key<RB, MI>(lrow)) * CH;
+  const int koff = ((tid % CPR) ^ swz_key<RB>(lrow)) * CH;
   constexpr int ROWS_IT = NT / CPR;
   static_assert(ROWS_IT % 16 == 0, "row stride per DMA instruction must keep the swizzle key");
   int i_tm = 0, i_tn = 0;                 // tile coordinates of the tile being issued (wave-uniform)
@@ -1522,7 +1400,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   };
 
   f32x4 acc[WTM][WTN];
-  f32x16 acc32[M32 ? WTM / 2 : 1][M32 ? WTN / 2 : 1];      // (M32: the K loop accumulates here; acc is filled from it behind the loop)
   FYC_STAMP_DECL;
   int fyc_trace_e = 0;      // (timing builds: stamps inside the packed epilogue)
 
@@ -1537,20 +1414,10 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   // trip exposed in front of every block row but the first, 8 per K tile and wave on the 256x320 tile (profiles/r06_gemm_row_prefetch_ab.txt).  Now the
   // row fragments run PF block rows ahead in a small register ring (PF x WTN x 16 matrix cycles >= ~250), pinned by scheduling fences: the wait in
   // front of block row i is lgkmcnt(PF) and only the first read batch of a k-step is exposed.
-#ifdef FYC_NO_FRAG_ROW
-  constexpr bool FRAG_ROW = false;
-#else
-  constexpr bool FRAG_ROW = sizeof(T) == 2 && !FRAG_ALL && !M32;
-#endif
+  constexpr bool FRAG_ROW = sizeof(T) == 2 && !FRAG_ALL;
   constexpr int PF = (WTN >= 8) ? 2 : (WTN >= 4 ? 4 : 6);      // block rows of read-ahead
-  // FYC_LATE_POS (A/B, round 6): where the late half of the waves issues its DMAs - 0 (default): between the two k-steps; r > 0: inside the
-  // SECOND k-step, behind block row r - 1 (FRAG_ROW tiles only; the callback `mid` of compute())
-#ifndef FYC_LATE_POS
-#define FYC_LATE_POS 0
-#endif
-  constexpr int LATE_ROW = (FRAG_ROW && FYC_LATE_POS > 0 && FYC_LATE_POS < WTM) ? FYC_LATE_POS : 0;
-  auto no_mid = []() {};
-  auto compute = [&](int stage, int s0, int s1, auto&& mid) {     // MFMA k-steps [s0, s1) of one staged K tile
+  auto compute = [&](int stage, auto first, auto end) {     // MFMA k-steps [first, end) of one staged K tile
+    constexpr int s0 = decltype(first)::value, s1 = decltype(end)::value;
     const char* sA = smem + stage * STAGE + (wm * WTM * 16 + r16) * RB;
     const char* sB = smem + stage * STAGE + A_BYTES + (wn * WTN * 16 + r16) * RB;
 #pragma unroll
@@ -1571,7 +1438,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
 #pragma unroll
           for (int j = 0; j < WTN; ++j) acc[i][j] = Tr::mma(bfr[j], ar[i % RING], acc[i][j]);
           __builtin_amdgcn_sched_barrier(0);
-          if (LATE_ROW > 0 && s == KSTEPS - 1 && i == LATE_ROW - 1) { mid(); __builtin_amdgcn_sched_barrier(0); }
         }
         continue;
       }
@@ -1590,12 +1456,8 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   };
   // XSTEP (round 6): the small tiles (FRAG_ALL) have room for the fragments of BOTH k-steps of a K tile: the second step's reads are issued in
   // front of the first step's matrix instructions, so one LDS round trip per K tile is exposed instead of two.
-  // (A/B, profiles/r06_gemm_row_prefetch_ab.txt: -DFYC_NO_XSTEP / -DFYC_NO_FRAG_ROW rebuild the round-5 orders)
-#ifdef FYC_NO_XSTEP
-  constexpr bool XSTEP = false;
-#else
-  constexpr bool XSTEP = FRAG_ALL && KSTEPS == 2 && !M32 && (WTM * WTN + 2 * (WTM + WTN)) * 4 <= 190;
-#endif
+  // (A/B of FRAG_ROW and XSTEP against the round-5 orders: profiles/r06_gemm_row_prefetch_ab.txt)
+  constexpr bool XSTEP = FRAG_ALL && KSTEPS == 2 && (WTM * WTN + 2 * (WTM + WTN)) * 4 <= 190;
   auto compute_xstep = [&](int stage, auto&& between) {
     const char* sA = smem + stage * STAGE + (wm * WTM * 16 + r16) * RB;
     const char* sB = smem + stage * STAGE + A_BYTES + (wn * WTN * 16 + r16) * RB;
@@ -1646,41 +1508,10 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
         for (int j = 0; j < WTN; ++j) acc[i][j] = Tr::mma(bs[j], as[i], acc[i][j]);
     }
   };
-  // 32x32x16 form: k32-step s = two k16-steps; lane (h = lane / 32, r32 = lane % 32) reads row r32 of a 32-row block, chunk 2 s' + h
-  const int r32 = lane & 31, h32 = lane >> 5;
-  const int sw32 = swz_key<RB, 32>(r32);
-  auto compute32 = [&](int stage, int s0, int s1) {
-    constexpr int BI = M32 ? WTM / 2 : 1, BJ = M32 ? WTN / 2 : 1;
-    const char* sA = smem + stage * STAGE + (wm * WTM * 16 + r32) * RB;
-    const char* sB = smem + stage * STAGE + A_BYTES + (wn * WTN * 16 + r32) * RB;
-#pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) {            // one k32 step = the fragments of its two k16 steps read together, then 2 x BI x BJ instructions
-      if (s < s0 || s >= s1) continue;
-      const int coff0 = ((4 * s + h32) ^ sw32) * 16, coff1 = ((4 * s + 2 + h32) ^ sw32) * 16;
-      Frag af[2][BI], bf[2][BJ];
-#pragma unroll
-      for (int i = 0; i < BI; ++i) { af[0][i] = *reinterpret_cast<const Frag*>(sA + i * 32 * RB + coff0); af[1][i] = *reinterpret_cast<const Frag*>(sA + i * 32 * RB + coff1); }
-#pragma unroll
-      for (int j = 0; j < BJ; ++j) { bf[0][j] = *reinterpret_cast<const Frag*>(sB + j * 32 * RB + coff0); bf[1][j] = *reinterpret_cast<const Frag*>(sB + j * 32 * RB + coff1); }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int i = 0; i < BI; ++i)
-#pragma unroll
-          for (int j = 0; j < BJ; ++j) acc32[i][j] = Mma32<T>::mma(bf[u][j], af[u][i], acc32[i][j]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
   auto issue = [&](int kt, int stage) {
     char* sA = smem + stage * STAGE;
     char* sB = sA + A_BYTES;
     const int k0 = kt * BK;
-#ifdef FYC_ABLATE_CONV_A
-    // TIMING BUILD (wrong results): the A gather of a 3x3 convolution is issued for `FYC_ABLATE_CONV_A` of the 9 taps of a slab only -
-    // the upper bound of what a halo tile of the input in LDS (each pixel fetched once per slab, read by all nine taps) could save
-    if (MODE == FYC_GEMM_PLAIN || tap < FYC_ABLATE_CONV_A)
-#endif
 #pragma unroll
     for (int it = 0; it < A_IT; ++it) glds16(src_a(it, k0), sA + (it * NT + wave * 64) * 16);
 #pragma unroll
@@ -1755,14 +1586,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
     for (int i = 0; i < WTM; ++i)
 #pragma unroll
       for (int j = 0; j < WTN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if constexpr (M32) {
-#pragma unroll
-      for (int i = 0; i < WTM / 2; ++i)
-#pragma unroll
-        for (int j = 0; j < WTN / 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc32[i][j][e] = 0.f;
-    }
     if constexpr (PRE_BUILT) {
       // the epilogue's inputs of THIS tile, by DMA, in front of its K loop (not inside it: 200 more instructions in the loop body cost the
       // convolutions 2-4 %): behind a barrier - nobody reads the previous tile's inputs any more -, retired by the vmcnt(0) + barrier of the
@@ -1779,12 +1602,6 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
         int rm, rn;
         tile_coords(p, remap(tile / S), rm, rn);
         load_residual_acc<T, BM, BN, WGM, WGN>(p, acc, rm, rn, wave, lane);
-        if constexpr (M32) {
-#pragma unroll
-          for (int i = 0; i < WTM / 2; ++i)
-#pragma unroll
-            for (int j = 0; j < WTN / 2; ++j) acc16_to_acc32(acc32[i][j], acc[2 * i][2 * j], acc[2 * i][2 * j + 1], acc[2 * i + 1][2 * j], acc[2 * i + 1][2 * j + 1]);
-        }
       }
     }
     FYC_STAMP(p, wave, lane);
@@ -1810,17 +1627,11 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
       } else if constexpr (XSTEP) {
         compute_xstep(st_c, [&]() { if (late && i_tile < nwork) issue_next(); });
       } else {
-        if constexpr (M32) compute32(st_c, 0, 1); else compute(st_c, 0, 1, no_mid);
-        if (LATE_ROW == 0 && late && i_tile < nwork) issue_next();
-        if constexpr (M32) compute32(st_c, 1, KSTEPS); else compute(st_c, 1, KSTEPS, [&]() { if (late && i_tile < nwork) issue_next(); });
+        compute(st_c, KStep<0>{}, KStep<1>{});
+        if (late && i_tile < nwork) issue_next();
+        compute(st_c, KStep<1>{}, KStep<KSTEPS>{});
       }
       st_c = (st_c + 1 == NS) ? 0 : st_c + 1;
-    }
-    if constexpr (M32) {      // 32x32 blocks -> the 16x16 layout every epilogue (and the split-K partial store) is written for
-#pragma unroll
-      for (int i = 0; i < WTM / 2; ++i)
-#pragma unroll
-        for (int j = 0; j < WTN / 2; ++j) acc32_to_acc16(acc32[i][j], acc[2 * i][2 * j], acc[2 * i][2 * j + 1], acc[2 * i + 1][2 * j], acc[2 * i + 1][2 * j + 1]);
     }
     FYC_STAMP(p, wave, lane);
     const int t = remap(tile / S);
@@ -1854,12 +1665,12 @@ inline int rowbias_slots(int bm, int rpb) {
   return n <= RB_SLOTS ? n : 0;
 }
 
-template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, int MI = 16, typename P = T>
+template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, typename P = T>
 int launch(const GemmP& p, int batch, hipStream_t st) {
   constexpr bool PRE_BUILT = WIDE && NS == 2;
   constexpr int smem = NS * (BM + BN) * RB + (PRE_BUILT ? pre_bytes<BM, BN>() : 0);
   static_assert(smem <= 160 * 1024, "LDS budget");
-  auto kern = fyc_gemm_kernel<T, BM, BN, WGM, WGN, MODE, EPI, NS, RB, WIDE, MI, P>;
+  auto kern = fyc_gemm_kernel<T, BM, BN, WGM, WGN, MODE, EPI, NS, RB, WIDE, P>;
   int dev = 0;
   (void)hipGetDevice(&dev);
   // per-device one-time setup (attribute + CU count), guarded: one process may drive several GPUs from several threads
@@ -1930,8 +1741,8 @@ template <typename T, int MODE, int EPI, bool WIDE, typename P = T>
 int dispatch_cfg(int cfg, int ns, const GemmP& p, int batch, hipStream_t st) {
   if constexpr (!WIDE) {
     if (cfg != 1 && cfg != 2) cfg = (p.N % 128 == 0 || p.N > 512) ? 1 : 2;
-    if (cfg == 1) return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 128, false, 16, P>(p, batch, st);
-    return launch<T, 128, 64, 2, 2, MODE, EPI, 2, 128, false, 16, P>(p, batch, st);
+    if (cfg == 1) return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 128, false, P>(p, batch, st);
+    return launch<T, 128, 64, 2, 2, MODE, EPI, 2, 128, false, P>(p, batch, st);
   } else {
     switch (cfg) {
       case 1: if (ns == 3) return launch<T, 128, 128, 2, 2, MODE, EPI, 3, 128, true>(p, batch, st);
@@ -1954,15 +1765,9 @@ int dispatch_cfg(int cfg, int ns, const GemmP& p, int batch, hipStream_t st) {
       // round 6: 128x160 over 2x2 waves (64x80 per wave, the wave tile of config 6) with 72 KB of ring: TWO independent workgroups per CU,
       // so one's epilogue / first fill runs under the other's K loop - for the short-K problems whose 128x320 tiles spend as long in the
       // epilogue as in the K loop (profiles/r06_gemm_two_workgroups_ab.txt)
-      // round 6: the 32x32x16 matrix instruction in the K loop (same tiles and wave grids as 5 / 7 / 3).  Parity-green, 8-12 % SLOWER than the
-      // 16x16x32 loop on every shape (profiles/r06_gemm_mi32_ab.txt): only in builds with FYC_BUILD_EXTRA=-DFYC_GEMM_MI32 (tests: FYC_TEST_MI32=1)
-#ifdef FYC_GEMM_MI32
-      case 12: return launch<T, 256, 320, 4, 2, MODE, EPI, 2, 128, true, 32>(p, batch, st);
-      case 13: return launch<T, 256, 256, 2, 4, MODE, EPI, 2, 128, true, 32>(p, batch, st);
-      case 14: return launch<T, 256, 128, 4, 2, MODE, EPI, 2, 128, true, 32>(p, batch, st);
-#endif
       case 11: if constexpr (EPI == FYC_EPI_GEGLU) FYC_FAIL(-2, "fyc_gemm: tile config 11 gives a wave an odd number of column blocks: not built for GEGLU");
                else return launch<T, 128, 160, 2, 2, MODE, EPI, 2, 128, true>(p, batch, st);
+      // (12 / 13 / 14 were the 32x32x16 main-loop twins of 5 / 7 / 3, 8-12 % slower on every shape, profiles/r06_gemm_mi32_ab.txt: retired, never built)
     }
     FYC_FAIL(-2, "fyc_gemm: tile config %d not built", cfg);
   }

@@ -8,21 +8,15 @@
 // arguments are then checked against that plan, and a call that cannot run it (a folded LayerNorm on a problem that splits, operands
 // that rule out the 16-byte epilogue, ...) is REFUSED with the conflict named: never another tile, never a layout nobody announced.
 #pragma once
-#ifdef FYC_GEMM_VARIANTS
-#include "../../tools/exp/gemm_variants/gemm_pp_kernel.h"
-#include "../../tools/exp/gemm_variants/gemm_ov_kernel.h"
-#else
 #include "gemm_kernel.h"
-#endif
 
 namespace fycg {
 
 enum { GEMM_FAM_PLAIN, GEMM_FAM_CONV, GEMM_FAM_ACT, GEMM_FAM_T3 };   // one translation unit per (dtype, family): gemm_kernel.h::run_*
-enum { GEMM_LOOP_ONE_PHASE, GEMM_LOOP_PP, GEMM_LOOP_OV };            // main loop: the product's, or a FYC_GEMM_VARIANTS experiment
 enum { GEMM_STATS_CHAN = 1, GEMM_STATS_ROW = 2 };
 
 struct GemmPlan {
-  int dtype, family, loop;
+  int dtype, family;
   int cfg, bm, bn, ns;     // tile config (gemm_kernel.h::dispatch_cfg; of the split launch when splitk > 1), its rows x columns, ring depth
   int splitk;              // K slices per output tile; 1 = no split, > 1: a splitk_finish kernel adds the slices after the main launch
   int wide, colc;          // GemmP::wide / colc
@@ -33,7 +27,8 @@ struct GemmPlan {
 
 inline bool gemm_is16(int dtype) { return dtype == FYC_BF16 || dtype == FYC_F16; }   // the 16-bit storage formats share every tile / epilogue decision
 
-// row-tile height / column-tile width of a tile config (gemm_kernel.h::dispatch_cfg)
+// row-tile height / column-tile width of a tile config (gemm_kernel.h::dispatch_cfg).  12 / 13 / 14 (the 32x32x16 twins of 5 / 7 / 3) and 21 / 22 / 23 /
+// 31 (main-loop experiments on the tiles of 5 / 6 / 7 / 6) are RETIRED ids, never built: their rows stay so that the layout queries answer as they always did
 inline int gemm_tile_bm(int cfg) { return (cfg == 3 || cfg == 4 || cfg == 5 || cfg == 7 || (cfg >= 12 && cfg <= 14) || cfg == 21 || cfg == 23) ? 256 : 128; }
 inline int gemm_tile_bn(int cfg) {
   switch (cfg) { case 2: case 4: return 64; case 5: case 6: case 8: case 12: case 21: case 22: case 31: return 320; case 7: case 13: case 23: return 256; case 11: return 160; default: return 128; }
@@ -102,19 +97,8 @@ inline bool plan_gemm(const fyc_gemm_args* a, int stats, bool query, GemmPlan& p
   // GEGLU pairs 16-column value / gate blocks inside a wave: config 6 gives a wave 5 column blocks (128x320 over 2x4 waves) and
   // used to leave the output unwritten (found by tools/gemm_diag.py at M = 4096 / 8192, N = 2560 - shapes the UNet never issued)
   const auto geglu_tile = [&](int c) { return a->epilogue != FYC_EPI_GEGLU ? c : (c == 6 || c == 11) ? 5 : c == 22 ? 21 : c; };
-  // The FYC_GEMM_VARIANTS main loops take over the automatic choice (FYC_TUNE_GEMM_LOOP = 2: ping-pong wave groups, gemm_pp_kernel.h, for the
-  // 8-wave tiles; 3: the overlapped-epilogue kernel, gemm_ov_kernel.h, tile config 31 = 128x320, for every LINEAR problem that would get a
-  // 256x320 / 128x320 tile); a problem that does not qualify falls back to the one-phase twin below
-  const auto variant_tile = [&](int c) {
-#ifdef FYC_GEMM_VARIANTS
-    const bool forced = a->tile > 0 || tune[FYC_TUNE_GEMM_TILE] > 0;
-    if (!forced && tune[FYC_TUNE_GEMM_LOOP] == 2) return c == 5 ? 21 : c == 6 ? 22 : c == 7 ? 23 : c;
-    if (!forced && tune[FYC_TUNE_GEMM_LOOP] == 3 && (c == 5 || c == 6) && linear) return 31;
-#endif
-    return c;
-  };
   if (h16) {
-    cfg = variant_tile(geglu_tile(cfg));
+    cfg = geglu_tile(cfg);
     if (!((cfg == 1 && ns == 3) || (cfg == 2 && (ns == 3 || ns == 4) && a->mode == FYC_GEMM_PLAIN))) ns = 2;   // deeper rings: config 1 (3) and, for linears, config 2 (3, 4)
   }
   // The packed 16-bit LINEAR epilogue stages every per-column input through LDS.  The 64-byte K-tile configs (8 / 10) have a ring stage too
@@ -133,7 +117,6 @@ inline bool plan_gemm(const fyc_gemm_args* a, int stats, bool query, GemmPlan& p
   // the CUs idle (64 tiles): each output tile is cut into K slices (raw f32 partials to the workspace, added by a finish kernel that also
   // applies the LINEAR epilogue and, for chan_parts, writes the statistics in ITS 128-row tiles).
   int splitk = 1;
-  [[maybe_unused]] bool split_shape = false;                                    // the problem would split, given the workspace and the 16-byte epilogue
   const int split_cfg = (a->N % 320 == 0) ? 6 : 1;             // 128x320 or 128x128 tiles
   {
     // FYC_TUNE_SPLITK_MIN_KT = v > 0 (A/B): at least v K tiles per slice instead of 10, K >= 128 v instead of 2048 - the K = 1280 linears
@@ -157,37 +140,18 @@ inline bool plan_gemm(const fyc_gemm_args* a, int stats, bool query, GemmPlan& p
     PLAN_REFUSE_IF(splitk > 1 && chan && unsplittable,
                    "fyc_gemm: chan_parts next to ln_stats / row_parts on a split-K shape (M=%d N=%d K=%d): the chan_parts layout fyc_gemm_stat_layout announces is the split-K finish kernel's, and a split problem can neither fold a LayerNorm nor sum its rows", a->M, a->N, a->K);
     if (!chan && unsplittable) splitk = 1;
-    split_shape = splitk > 1;
     const int64_t want = (int64_t)splitk * a->M * a->N * 4;
     const bool ws_ok = query || (a->workspace != nullptr && a->workspace_bytes >= want && ((uintptr_t)a->workspace % 16) == 0);
     if (splitk > 1 && !(wide && ws_ok)) {
       PLAN_REFUSE_IF(chan, "fyc_gemm: chan_parts of a split-K problem (fyc_gemm_workspace_bytes() > 0) are laid out for its finish kernel: pass the workspace (and 16-byte aligned operands)");
       if (!chan) splitk = 1;
     }
-    if (splitk > 1) { cfg = variant_tile(split_cfg); ns = 2; pl.ws_bytes = (chan && unsplittable) ? 0 : want; }      // (a call that will be refused wants nothing)
+    if (splitk > 1) { cfg = split_cfg; ns = 2; pl.ws_bytes = (chan && unsplittable) ? 0 : want; }      // (a call that will be refused wants nothing)
   }
-  // ---- main loop: the experiments are built for bf16 PLAIN / 3x3 problems with the 16-byte epilogues, whole 64-element K tiles (at least
-  // two) and no batch; everything else, and every build without them, runs the one-phase twin (same tile, same wave grid) ----------
-  {
-    const int twin = cfg == 21 ? 5 : cfg == 22 ? 6 : cfg == 23 ? 7 : cfg == 31 ? 6 : cfg;
-#ifdef FYC_GEMM_VARIANTS
-    const int bm = gemm_tile_bm(cfg);
-    const bool pp_ok = a->dtype == FYC_BF16 && wide && a->batch <= 1 && a->act == FYC_ACT_NONE && a->K % 64 == 0 && a->K >= 128 && a->mode != FYC_GEMM_CONV_T3;
-    const bool ov_ok = pp_ok && linear && a->K >= 5 * 64 && a->M % 2 == 0 && a->ln_nparts == 0 && a->row_parts == nullptr && !split_shape &&
-                       !(a->ln_stats != nullptr && a->residual != nullptr) && (a->chan_parts == nullptr || a->cs_rows % bm == 0) &&
-                       (a->rowbias == nullptr || rpb % bm == 0 || rowbias_slots(bm, rpb) > 0);
-    if (!(pp_cfg(cfg) ? pp_ok : ov_cfg(cfg) ? ov_ok : true)) cfg = twin;
-    pl.loop = pp_cfg(cfg) ? GEMM_LOOP_PP : ov_cfg(cfg) ? GEMM_LOOP_OV : GEMM_LOOP_ONE_PHASE;
-#else
-    cfg = twin;
-#endif
-  }
-  cfg = geglu_tile(cfg);      // (a fallback above may land on the one tile GEGLU is not built for)
-  // 32x32x16 matrix instruction in the K loop of the tiles that have such a twin (FYC_TUNE_MI32: A/B switch, FYC_GEMM_MI32 builds)
-#ifdef FYC_GEMM_MI32
-  if (wide && tune[FYC_TUNE_MI32] == 1 && pl.loop == GEMM_LOOP_ONE_PHASE && (pl.family == GEMM_FAM_PLAIN || pl.family == GEMM_FAM_CONV))
-    cfg = cfg == 5 ? 12 : cfg == 7 ? 13 : cfg == 3 ? 14 : cfg;
-#endif
+  // tile configs 21 / 22 / 23 / 31 named the round-4 main-loop experiments (retired: profiles/r04_gemm_pingpong_and_prefetch_sweep.txt): a request for one runs its
+  // one-phase twin (same tile, same wave grid), as it did in every build without them
+  cfg = cfg == 21 ? 5 : cfg == 22 ? 6 : cfg == 23 ? 7 : cfg == 31 ? 6 : cfg;
+  cfg = geglu_tile(cfg);      // (the twin may be the one tile GEGLU is not built for)
 
   pl.cfg = cfg; pl.ns = ns; pl.splitk = splitk; pl.wide = wide ? 1 : 0; pl.colc = colc ? 1 : 0;
   pl.bm = gemm_tile_bm(cfg); pl.bn = gemm_tile_bn(cfg);

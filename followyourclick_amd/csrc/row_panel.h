@@ -63,7 +63,7 @@ template <typename Frag> __device__ __forceinline__ Frag frag(const char* sl, in
 // and hipcc (which cannot see the asm DMAs above) waits for it with a COUNTED lgkmcnt between the fragment reads of the stages it
 // sinks this code into - with LDS-DMA writes in flight the result was consumed early in ~12 % of the row blocks of ff_block.hip
 // (row statistics off by ~1e-3: tools/ff_stress.py found the kernel's output changing from launch to launch;
-// profiles/r03_ff_block_race.txt; -DFF_BPERMUTE rebuilds that form there).  No LDS-queue instruction other than fragment reads
+// profiles/r03_ff_block_race.txt).  No LDS-queue instruction other than fragment reads
 // and staging writes may sit between asm-issued DMAs.
 __device__ __forceinline__ float halves_sum(float v) { return swap32_sum(v); }             // over the two lane halves of a wave, every lane gets it (fyc_common.h: the two results of the swap must stay opaque to hipcc)
 __device__ __forceinline__ float rows_sum(float v) { return swap32_sum(swap16_sum(v)); }   // over the four 16-lane rows of a wave (fyc_common.h: opaque swap results, as for the maxima)

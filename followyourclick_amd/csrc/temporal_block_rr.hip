@@ -56,12 +56,7 @@ struct TRP {
 };
 
 // LDS-DMA, MFMA, fragment read and the row reductions: row_panel.h, with the rules they follow
-using rp::dma16; using rp::dma16v; using rp::dma_landed_barrier; using rp::frag; using rp::rows_sum; using rp::rows_max;
-#ifdef TB_NO_MFMA                                              // ablation build: DMA + LDS reads + barriers only, wrong results
-template <typename Frag> __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 c) { c[0] += __builtin_bit_cast(f32x4, a)[0] + __builtin_bit_cast(f32x4, b)[0]; return c; }
-#else
-using rp::mfma;
-#endif
+using rp::dma16; using rp::dma16v; using rp::dma_landed_barrier; using rp::mfma; using rp::frag; using rp::rows_sum; using rp::rows_max;
 template <typename T> __device__ __forceinline__ typename Pair16<T>::Vec8 op8(const f32x4& a, const f32x4& b) {          // two 4-row results -> one 8-slot operand
   return __builtin_bit_cast(typename Pair16<T>::Vec8, (u32x4){Pair16<T>::pack(a[0], a[1]), Pair16<T>::pack(a[2], a[3]), Pair16<T>::pack(b[0], b[1]), Pair16<T>::pack(b[2], b[3])});
 }
@@ -150,9 +145,6 @@ __global__ void __launch_bounds__(NT) tblock_rr_kernel(const TRP p) {
 
   // n-th piece of this wave of stage tnext (np pieces; the last round wraps around and fetches the first pieces again: no branch)
   auto dma_piece = [&](int tnext, int n, int np) {
-#ifdef TB_NO_DMA
-    return;                                                   // ablation build (tools/tblock_probe.py): compute only, wrong results
-#endif
     int q = wave + 4 * n;
     q = q >= np ? q - np : q;
     dma16(p.ws + (long long)tnext * STAGE_BYTES + q * PIECE, lane16, lds0 + (tnext & 1) * STAGE_BYTES + q * PIECE);

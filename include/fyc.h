@@ -47,16 +47,14 @@ int fyc_device_caps(int64_t* caps);
 /* tuning knobs for A/B measurements (0 = automatic): key 0 = 1 disables split-K, key 1 = GEMM tile config (1: 128x128/4 waves, 2: 128x64/4,
  * 3: 256x128/8, 4: 256x64/4, 5: 256x320/8, 6: 128x320/8, 7: 256x256/8, 8/10: 128x320 / 128x128 with 64-byte K tiles, 11: 128x160/4 waves, two workgroups per CU), key 2 = GEMM LDS ring depth (2..4), key 3 = attention kernel variant,
  * key 4 = column-strip width of the GEMM tile order (-1: row-major), key 5 = 1 disables the wave-role stagger of the 8-wave GEMM tiles, key 6 = 1 disables the LDS-staged wide epilogues, key 7 = 1 only the wide head-split one,
- * keys 8 / 9 only act in a library built with FYC_GEMM_VARIANTS=1 (tools/exp/gemm_variants/: the round-4 main-loop experiments, measured slower,
- * not part of the product library): key 8 = 1: no s_setprio around the MFMA phases of the ping-pong loop; key 9 = 2: the ping-pong loop (tile
- * configs 21 / 22 / 23) wherever it is built, 3: the overlapped-epilogue kernel (config 31).  In the product library key 9 is ignored and a
- * request for one of those tile configs runs its one-phase twin (5 / 6 / 7 / 6): the one-phase loop always;
+ * keys 8 / 9: reserved, ignored (experiments retired: the round-4 ping-pong / overlapped-epilogue main loops, tile configs 21 / 22 / 23 / 31; results in
+ * profiles/r04_gemm_pingpong_and_prefetch_sweep.txt).  A request for one of those tile configs runs its one-phase twin (5 / 6 / 7 / 6): the one-phase loop always;
  * key 10 = v > 0: split-K for M <= 4096 keeps at least v K tiles per slice and starts at K >= 128 v and N >= 128 (default, key 10 = 0: 10 K tiles per slice, K >= 2048, N >= 256);
  * key 11 = v > 0: every other GEMM block of an XCD starts v x 1024 cycles late (phase shift between the CUs' epilogues, A/B);
  * key 12 = 1: the GEMM epilogues load their per-row / per-column inputs themselves instead of finding them pre-staged in LDS (A/B);
  * key 13 = 1: the generic pass 1 of the packed LINEAR epilogue instead of its specialised copies (A/B);
- * key 14 = 1: the 32x32x16 matrix instruction in the K loop of the 256-row tiles (tile configs 12 / 13 / 14 = twins of 5 / 7 / 3) - only in a
- * library built with -DFYC_GEMM_MI32 (measured 8-12 % slower, not part of the product library); key 15 = 1 / 2: the pack-first head-split
+ * key 14: reserved, ignored (experiment retired: the 32x32x16 matrix instruction in the K loop, tile configs 12 / 13 / 14, which are not built; results in
+ * profiles/r06_gemm_mi32_ab.txt); key 15 = 1 / 2: the pack-first head-split
  * epilogue on / off for every problem (default: M <= 8192 only) */
 int fyc_set_tuning(int key, int value);
 

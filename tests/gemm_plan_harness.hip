@@ -27,12 +27,7 @@
 #include <string>
 #include <vector>
 
-#ifdef FYC_GEMM_VARIANTS
-#include "../tools/exp/gemm_variants/gemm_pp_kernel.h"
-#include "../tools/exp/gemm_variants/gemm_ov_kernel.h"
-#else
 #include "../followyourclick_amd/csrc/gemm_kernel.h"
-#endif
 
 using fycg::GemmP;
 
@@ -56,11 +51,6 @@ int run_f16_act(const GemmP& p, int batch, int cfg, hipStream_t) { return record
 int run_bf16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t) { return record("bf16_t3", p, batch, cfg, ns); }
 int run_f16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t) { return record("f16_t3", p, batch, cfg, ns); }
 int run_f32_t3(const GemmP& p, int batch, int cfg, hipStream_t) { return record("f32_t3", p, batch, cfg, -1); }
-#ifdef FYC_GEMM_VARIANTS
-int run_pp_plain(const GemmP& p, int cfg, hipStream_t) { return record("pp_plain", p, 1, cfg, -1); }
-int run_pp_conv(const GemmP& p, int cfg, hipStream_t) { return record("pp_conv", p, 1, cfg, -1); }
-int run_ov(const GemmP& p, int cfg, hipStream_t) { return record("ov", p, 1, cfg, -1); }
-#endif
 }  // namespace fycg
 
 namespace {

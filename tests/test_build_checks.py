@@ -140,7 +140,7 @@ def test_attention_issue_statement_restores_m0_and_exec(tmp_path):
             checked += 1
         canon = re.findall(r"v_max_f32_e32 (v\d+), (v\d+), (v\d+)", body)
         assert not [c for c in canon if c[1] == c[2]], f"{name}: sNaN-quieting v_max_f32 x, x, x is back (is -fno-honor-nans still on the attention sources?)"
-        assert "s_setprio" not in body, f"{name}: s_setprio in an issue-bound loop (-DFYC_ATTN_SETPRIO builds it)"
+        assert "s_setprio" not in body, f"{name}: s_setprio in an issue-bound loop (measured: profiles/r05_attention_instruction_diet_ab.txt)"
     assert checked >= len(kernels), (checked, len(kernels))      # at least one such statement per kernel (prologue + loop)
 
 

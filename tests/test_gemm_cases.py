@@ -13,8 +13,7 @@ from test_kernels_gpu import CONV_TILES, F16_TILES, PLAIN_TILES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "followyourclick_amd", "csrc")
-MI32_TWINS = (12, 13, 14)        # only built with FYC_GEMM_MI32: they follow FYC_TEST_MI32 on the GPU, not here
-CASES = [c for c in G.CASES if c.tile not in MI32_TWINS]
+CASES = G.CASES
 
 
 @pytest.fixture(scope="module")
@@ -68,10 +67,10 @@ def test_every_tile_of_the_sweeps_is_executed_wide(recorded, mode, tiles, extra)
     """across the wide, unsplit cases of a mode the executed (tile config, ring depth) are exactly the sweep's list (tile 0 being the automatic
     choice) and the f16 subset's (F16_TILES has (1, 2) and (2, 2), which CONV_TILES leaves out), plus in PLAIN mode the two deeper rings of the 128x64 linears"""
     executed = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in CASES if c.mode == mode and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
-    want = {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles + F16_TILES if t not in MI32_TWINS} | set(extra)
+    want = {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles + F16_TILES} | set(extra)
     assert executed == want, (sorted(executed - want), sorted(want - executed))
     bf16 = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in CASES if c.mode == mode and c.dt == "bf16" and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
-    assert {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles if t not in MI32_TWINS} <= bf16
+    assert {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles} <= bf16
     for t in (8, 10):      # and the 64-byte K-tile configs by cases that ASKED for them
         assert any(c.tile == t and recorded[c.name]["cfg"] == t and recorded[c.name]["wide"] == 1 for c in CASES if c.mode == mode), t
 

@@ -3,7 +3,6 @@
 same bf16 values on both sides, so the only differences are accumulation order and the final
 round-to-bf16)."""
 import math
-import os
 
 import pytest
 import torch
@@ -14,8 +13,7 @@ pytestmark = pytest.mark.gpu
 
 DT = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}
 RTOL = {"bf16": 4e-3, "f32": 2e-5, "f16": 5e-4}      # f16 (FYC_F16): same operand values on both sides, one rounding to 11 bits at the end
-MI32 = os.environ.get("FYC_TEST_MI32") == "1"      # a library built with FYC_BUILD_EXTRA=-DFYC_GEMM_MI32 (32x32x16 main loop, tile configs 12 / 13 / 14: A/B only)
-F16_TILES = [(0, 0), (1, 2), (2, 2), (3, 2), (5, 2), (6, 2)] + ([(12, 2), (13, 2)] if MI32 else [])      # the f16 instantiations share the tile templates: a subset keeps the suite short
+F16_TILES = [(0, 0), (1, 2), (2, 2), (3, 2), (5, 2), (6, 2)]      # the f16 instantiations share the tile templates: a subset keeps the suite short
 
 
 @pytest.fixture(scope="module")
@@ -48,9 +46,8 @@ def close(hip_t, emu_t, tag, rtol):
 
 
 # ---------------------------------------------------------------------------------------------
-# (12 / 13 / 14: the 32x32x16-instruction twins of 5 / 7 / 3, round 6)
-PLAIN_TILES = [(0, 0), (1, 2), (1, 3), (2, 2), (3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (10, 2), (11, 2)] + ([(12, 2), (13, 2), (14, 2)] if MI32 else [])
-CONV_TILES = [(0, 0), (1, 3), (3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (10, 2), (11, 2)] + ([(12, 2), (13, 2), (14, 2)] if MI32 else [])
+PLAIN_TILES = [(0, 0), (1, 2), (1, 3), (2, 2), (3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (10, 2), (11, 2)]
+CONV_TILES = [(0, 0), (1, 3), (3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (10, 2), (11, 2)]
 
 
 def _dt_tiles(tiles):
@@ -135,7 +132,7 @@ def test_gemm_geglu(hip, emu, dt):
     close(o_h, o_e, f"geglu {dt}", RTOL[dt])
 
 
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 7, 8, 10] + ([12, 13, 14] if MI32 else []))
+@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 7, 8, 10])
 @pytest.mark.parametrize("M", [300, 4096, 8192])
 def test_gemm_geglu_every_tile(hip, emu, M, tile):
     """GEGLU + folded LayerNorm at the SD-1.5 width (N = 2560, K = 320) with every tile configuration and with the library's own
@@ -165,6 +162,41 @@ def test_gemm_geglu_rejects_odd_wave_tiles(hip):
     assert torch.isfinite(o.float()).all()
 
 
+def _retired_tile_operands():
+    M, N, K = 300, 320, 320
+    T = torch.bfloat16
+    ops = dict(a=rnd((M, K), T, 1).cuda(), w=rnd((N, K), T, 2, 1 / math.sqrt(K)).cuda(), bias=rnd((N,), torch.float32, 3).cuda(), res=rnd((M, N), T, 4).cuda())
+    return ops, dict(M=M, N=N, K=K, lda=K, ldw=K, ldo=N, ldr=N)
+
+
+def _retired_tile_run(hip, ops, kw, tile):
+    o = torch.full((kw["M"], kw["N"]), float("nan"), dtype=torch.bfloat16, device="cuda")
+    hip.gemm(ops["a"], ops["w"], o, bias=ops["bias"], residual=ops["res"], tile=tile, **kw)
+    torch.cuda.synchronize()
+    return o
+
+
+@pytest.mark.parametrize("tile", [12, 13, 14])
+def test_gemm_retired_mi32_tiles_are_refused(hip, tile):
+    """tile configs 12 / 13 / 14 (the retired 32x32x16 main loop) are not built: the call is refused with the number named, before any launch"""
+    from followyourclick_amd._lib import FycError
+    ops, kw = _retired_tile_operands()
+    o = torch.full((kw["M"], kw["N"]), float("nan"), dtype=torch.bfloat16, device="cuda")
+    with pytest.raises(FycError, match=rf"tile config {tile}\b"):
+        hip.gemm(ops["a"], ops["w"], o, bias=ops["bias"], residual=ops["res"], tile=tile, **kw)
+    torch.cuda.synchronize()
+    assert torch.isnan(o.float()).all(), f"tile {tile}: the refused call wrote output"
+
+
+@pytest.mark.parametrize("tile,twin", [(21, 5), (22, 6), (23, 7), (31, 6)])
+def test_gemm_retired_loop_tiles_run_their_twins(hip, tile, twin):
+    """tile configs 21 / 22 / 23 / 31 (the retired round-4 main loops) run the one-phase tile of the same shape: bitwise the twin's output"""
+    ops, kw = _retired_tile_operands()
+    got, want = _retired_tile_run(hip, ops, kw, tile), _retired_tile_run(hip, ops, kw, twin)
+    assert torch.isfinite(want.float()).all()
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16)), f"tile {tile} vs {twin}: {(got != want).sum().item()} elements differ"
+
+
 @pytest.mark.parametrize("dt", ["bf16", "f32", "f16"])
 @pytest.mark.parametrize("tokens,heads,d", [(64, 8, 8), (77, 8, 40), (20, 2, 160)])
 def test_gemm_heads(hip, emu, dt, tokens, heads, d):
@@ -185,7 +217,7 @@ def test_gemm_heads(hip, emu, dt, tokens, heads, d):
         close(oh[i], oe[i], f"heads {dt} seg {n}", RTOL[dt])
 
 
-@pytest.mark.parametrize("tile", [1, 5, 6, 11] + ([12, 13] if MI32 else []))
+@pytest.mark.parametrize("tile", [1, 5, 6, 11])
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 def test_gemm_heads_every_wide_tile(hip, emu, dt, tile):
     """the wide head-split epilogue (q / k as 16-byte runs along the head dim, V^T along the token axis) at the SD-1.5 level-0 width
@@ -986,10 +1018,10 @@ def test_ddim_three_way_guidance(hip, emu, dt):
 
 
 # ---- statistics fused into the producing epilogue (fyc_gemm chan_stats / row_parts, fyc_gn_apply_cs) --------------------------
-STAT_TILES = [0, 1, 2, 3, 4, 5, 6, 7, 11] + ([12, 13, 14] if MI32 else [])
+STAT_TILES = [0, 1, 2, 3, 4, 5, 6, 7, 11]
 
 
-@pytest.mark.parametrize("dt,tile", [("bf16", t) for t in STAT_TILES] + [("f32", 0)] + [("f16", t) for t in (0, 5, 6) + ((12,) if MI32 else ())])
+@pytest.mark.parametrize("dt,tile", [("bf16", t) for t in STAT_TILES] + [("f32", 0)] + [("f16", t) for t in (0, 5, 6)])
 @pytest.mark.parametrize("M,N,K,cs_rows,res", [(512, 320, 320, 64, True), (768, 640, 128, 128, True), (1152, 128, 64, 192, False),
                                                (4096, 320, 64, 4096, True), (1280, 328, 72, 640, False), (1040, 64, 64, 80, False),
                                                (1152, 320, 64, 144, True), (2304, 640, 128, 576, True)])     # 12x12 / 24x24 frames (768^2): samples straddle wave rows

@@ -6,7 +6,9 @@ Identical instruction streams are the proof a refactor of a kernel file owes: be
 timing run is needed.  The comparison is on text lines and knows no instruction.  Left out before comparing: comment lines, `.file`, `.ident`, and
 the lines that name __hip_cuid_* (a hash per translation unit).  A template kernel whose parameter struct was renamed or moved to another
 namespace keeps its name and template arguments and differs in the mangled parameter list behind them (..E v <parameters>): lines that differ
-in nothing else are counted apart and reported with both manglings, they do not fail the run."""
+in nothing else are counted apart and reported with both manglings, they do not fail the run.  A template that lost or gained a parameter
+renames every instantiation: for the same comparison every mangled symbol (_Z...) is replaced by its index of first appearance in its file, the
+lines that differ in such spellings only are counted with the others, and the two sides must define equally many kernels."""
 import concurrent.futures as cf
 import os
 import re
@@ -21,6 +23,14 @@ from followyourclick_amd import _build  # noqa: E402
 CSRC_REL = os.path.relpath(_build.CSRC, ROOT)
 DROPPED = re.compile(r"^\s*(;|//|\.file\b|\.ident\b)|__hip_cuid_")
 PARAMS = re.compile(r"\b(_Z\w*Ev)(\w*)")      # greedy: the last `Ev` of a symbol closes the template arguments and names the void return type
+SYMBOL = re.compile(r"(?<!\w)(?:\.L)?_Z\w+")      # (.L_Z...: the resource-usage symbols of a function that was not inlined)
+KERNEL = re.compile(r"^\s*\.amdhsa_kernel\s+(\S+)")
+
+
+def by_index(lines):
+    """the lines with every mangled symbol replaced by its index of first appearance"""
+    seen = {}
+    return [SYMBOL.sub(lambda m: f"<symbol {seen.setdefault(m.group(0), len(seen))}>", x) for x in lines]
 
 
 def device_asm(csrc, src, out):
@@ -48,13 +58,18 @@ def differing(old, new, tmp, tag):
 
 
 def compare(src, old, new, tmp):
-    """-> (lines of the new assembly, differing lines, lines that differ in kernel parameter types only, the manglings seen)"""
+    """-> (lines of the new assembly, differing lines, lines that differ in the spelling of symbols only, what was respelt)"""
     n = differing(old, new, tmp, src)
     if n == 0:
         return len(new), 0, 0, ""
-    rest = differing([PARAMS.sub(r"\1<parameters>", x) for x in old], [PARAMS.sub(r"\1<parameters>", x) for x in new], tmp, src + ".noparams")
+    params = n - differing([PARAMS.sub(r"\1<parameters>", x) for x in old], [PARAMS.sub(r"\1<parameters>", x) for x in new], tmp, src + ".noparams")
+    rest = differing(by_index(old), by_index(new), tmp, src + ".nosymbols")
+    kernels = [len({m.group(1) for x in side for m in [KERNEL.match(x)] if m}) for side in (old, new)]
+    if kernels[0] != kernels[1]:
+        rest = max(rest, 1)
     types = [" | ".join(sorted({m.group(2) for x in side for m in PARAMS.finditer(x)})) for side in (old, new)]
-    return len(new), rest, n - rest, f"{types[0]} -> {types[1]}" if n > rest else ""
+    what = (f"{params} in kernel parameter types: {types[0]} -> {types[1]}; " if params else "") + f"kernel symbols {kernels[0]} -> {kernels[1]}"
+    return len(new), rest, n - rest, what
 
 
 def main(argv):
@@ -78,7 +93,7 @@ def main(argv):
                 bad += 1
                 continue
             lines, diff, params, types = compare(s, old, new, tmp)
-            print(f"{s:28s} {lines:7d} lines  {diff:7d} differing" + (f"  ({params} more in kernel parameter types only: {types})" if params else ""))
+            print(f"{s:28s} {lines:7d} lines  {diff:7d} differing" + (f"  ({params} more in symbol spelling only; {types})" if params else ""))
             bad += diff != 0
     return 1 if bad else 0
 
