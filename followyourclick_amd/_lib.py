@@ -117,6 +117,14 @@ class CfgDdimRescaleArgs(C.Structure):      # (308, added entry points) fyc_cfg_
     _fields_ = [("step", CfgDdimArgs), ("guidance_rescale", f32), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+class CfgSolverArgs(C.Structure):      # (308, added entry points) fyc_cfg_solver_step: guidance + one DPM-Solver multistep update
+    _fields_ = [("pred", vp), ("latents", vp), ("coef", vp),
+                ("B", i32), ("F", i32), ("HW", i32), ("c_latent", i32), ("ld", i32), ("cfg", i32), ("guidance", f32),
+                ("dtype", i32), ("pred_single", vp), ("video_scale", f32),
+                ("hist_out", vp), ("hist_1", vp), ("hist_2", vp), ("order", i32),
+                ("guidance_rescale", f32), ("workspace", vp), ("workspace_bytes", i64)]
+
+
 class NchwInArgs(C.Structure):
     _fields_ = [("z", vp), ("x", vp), ("N", i32), ("C", i32), ("HW", i32), ("c_pad", i32), ("scale", f32), ("dtype", i32)]
 
@@ -166,7 +174,7 @@ OPS = {
     "fyc_gn_stats": GnStatsArgs, "fyc_gn_apply": GnApplyArgs, "fyc_layernorm": LayerNormArgs,
     "fyc_softmax_rows": SoftmaxArgs, "fyc_concat_channels": ConcatArgs, "fyc_silu_f32": SiluArgs,
     "fyc_cast_from_f32": CastArgs, "fyc_cast_to_f32": CastArgs, "fyc_unet_input": UnetInputArgs,
-    "fyc_cfg_ddim_step": CfgDdimArgs, "fyc_cfg_ddim_step_rescaled": CfgDdimRescaleArgs, "fyc_nchw_to_nhwc": NchwInArgs, "fyc_nhwc_to_nchw": NhwcOutArgs,
+    "fyc_cfg_ddim_step": CfgDdimArgs, "fyc_cfg_ddim_step_rescaled": CfgDdimRescaleArgs, "fyc_cfg_solver_step": CfgSolverArgs, "fyc_nchw_to_nhwc": NchwInArgs, "fyc_nhwc_to_nchw": NhwcOutArgs,
     "fyc_embed_tokens": EmbedArgs, "fyc_patchify": PatchifyArgs, "fyc_row_stats": RowStatsArgs,
     "fyc_gn_apply_cs": GnApplyCsArgs, "fyc_chan_stats_reduce": ChanStatsReduceArgs,
     "fyc_pack_conv3x3": PackConv3x3Args, "fyc_pack_geglu": PackGegluArgs, "fyc_temporal_block": TemporalBlockArgs,
@@ -174,7 +182,7 @@ OPS = {
 }
 MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set_tuning", "fyc_gemm_row_parts", "fyc_gemm_stat_layout", "fyc_gemm_workspace_bytes", "fyc_gn_stats_workspace", "fyc_temporal_block_supported", "fyc_temporal_block_wstream_bytes",
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes",
-        "fyc_cfg_ddim_rescale_workspace_bytes"]
+        "fyc_cfg_ddim_rescale_workspace_bytes", "fyc_cfg_solver_workspace_bytes"]
 
 _lib = None
 FYC_VERSION = 308        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
@@ -232,6 +240,9 @@ def load() -> C.CDLL:
     if not ab_build or hasattr(lib, "fyc_cfg_ddim_rescale_workspace_bytes"):
         lib.fyc_cfg_ddim_rescale_workspace_bytes.argtypes = [C.POINTER(CfgDdimRescaleArgs)]
         lib.fyc_cfg_ddim_rescale_workspace_bytes.restype = i64
+    if not ab_build or hasattr(lib, "fyc_cfg_solver_workspace_bytes"):
+        lib.fyc_cfg_solver_workspace_bytes.argtypes = [C.POINTER(CfgSolverArgs)]
+        lib.fyc_cfg_solver_workspace_bytes.restype = i64
     for name, st in OPS.items():
         if ab_build and not hasattr(lib, name):
             continue

@@ -151,6 +151,43 @@ __global__ void __launch_bounds__(256) cfg_ddim_rescaled_kernel(const T* __restr
                           sigma, reclip, factor);
 }
 
+// Guidance + one step of the DPM-Solver multistep family (fyc_cfg_solver_step).  Every update of the family is linear in the latents x,
+// the guided prediction v and the stored converted outputs: coef = {a_x, a_v, c_x, c_0, c_1, c_2} gives m0 = a_x x + a_v v and
+// x' = c_x x + c_0 m0 + c_1 m1 + c_2 m2.  ORDER is a template parameter so that a history buffer the order does not use is never
+// loaded: 0 * NaN is NaN, and the first step's history is whatever the allocator left.
+template <typename T, int ORDER, bool RESCALE>
+__global__ void __launch_bounds__(256) cfg_solver_kernel(const T* __restrict__ pred, float* __restrict__ lat,
+                                                         const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
+                                                         int cfg, float guidance, const T* __restrict__ single, float video_scale,
+                                                         float* __restrict__ hist_out, const float* __restrict__ hist_1,
+                                                         const float* __restrict__ hist_2, const float* __restrict__ factor) {
+  const float ax = coef[0], av = coef[1], cx = coef[2], c0 = coef[3], c1 = coef[4], c2 = coef[5];
+  const long long total = (long long)B * F * HW;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const long long bf = i / HW;
+    const int f = (int)(bf % F), b = (int)(bf / F);
+    const T* pu = pred + i * ld;                                   // uncond (or the only) half
+    const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
+    for (int c = 0; c < CL; ++c) {
+      float v = ElemIO<T>::ld(pu + c);
+      if (cfg) {
+        const float u = v, cnd = ElemIO<T>::ld(pc + c);
+        v = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
+        if (RESCALE) v *= factor[b];
+      }
+      const long long j = (((long long)b * CL + c) * F + f) * HW + p;
+      const float x = lat[j];
+      const float m0 = ax * x + av * v;
+      float nx = cx * x + c0 * m0;
+      if (ORDER >= 2) nx += c1 * hist_1[j];
+      if (ORDER >= 3) nx += c2 * hist_2[j];
+      lat[j] = nx;
+      hist_out[j] = m0;
+    }
+  }
+}
+
 // Moments pass of the guidance rescale.  Block (b, part) owns rows [part * CFG_MOMENT_ROWS, +CFG_MOMENT_ROWS) of the F * HW pixel-rows
 // of sample b - a run fixed by the shape; thread t takes rows t, t + 256, ... of the run.  c and v are the f32 values the step kernel
 // forms; {sum c, sum c^2, sum v, sum v^2} are accumulated in f64 (the squares of f32 values are exact there), reduced over the block by a
@@ -457,11 +494,11 @@ extern "C" int64_t fyc_cfg_ddim_rescale_workspace_bytes(const fyc_cfg_ddim_resca
   return cfg_rescale_plan(&a->step, pl) ? pl.bytes : 0;
 }
 
+// the moments and factor launches, shared by the DDIM and the solver step -> the device factors [B] inside the workspace
 template <typename T>
-static void cfg_rescale_launch(const fyc_cfg_ddim_rescale_args* a, const CfgRescalePlan& pl, hipStream_t st) {
-  const fyc_cfg_ddim_args* s = &a->step;
-  double* parts = (double*)a->workspace;
-  float* factor = (float*)((char*)a->workspace + pl.part_bytes);
+static const float* cfg_rescale_factors(const fyc_cfg_ddim_args* s, void* workspace, float phi, const CfgRescalePlan& pl, hipStream_t st) {
+  double* parts = (double*)workspace;
+  float* factor = (float*)((char*)workspace + pl.part_bytes);
   const T* pred = (const T*)s->pred;
   const T* single = (const T*)s->pred_single;
   // one vector load per row: 4 latent channels, rows pitched in multiples of 4 elements from bases on such a boundary
@@ -470,7 +507,16 @@ static void cfg_rescale_launch(const fyc_cfg_ddim_rescale_args* a, const CfgResc
   const dim3 grid((unsigned)(s->B * pl.nparts));
   if (vec) hipLaunchKernelGGL((cfg_moments_kernel<T, true>), grid, dim3(256), 0, st, pred, parts, s->B, pl.rows, s->c_latent, s->ld, pl.nparts, s->guidance, single, s->video_scale);
   else hipLaunchKernelGGL((cfg_moments_kernel<T, false>), grid, dim3(256), 0, st, pred, parts, s->B, pl.rows, s->c_latent, s->ld, pl.nparts, s->guidance, single, s->video_scale);
-  hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(s->B), dim3(64), 0, st, (const double*)parts, factor, pl.nparts, (double)pl.rows * s->c_latent, a->guidance_rescale);
+  hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(s->B), dim3(64), 0, st, (const double*)parts, factor, pl.nparts, (double)pl.rows * s->c_latent, phi);
+  return factor;
+}
+
+template <typename T>
+static void cfg_rescale_launch(const fyc_cfg_ddim_rescale_args* a, const CfgRescalePlan& pl, hipStream_t st) {
+  const fyc_cfg_ddim_args* s = &a->step;
+  const float* factor = cfg_rescale_factors<T>(s, a->workspace, a->guidance_rescale, pl, st);
+  const T* pred = (const T*)s->pred;
+  const T* single = (const T*)s->pred_single;
   const long long n = (long long)s->B * pl.rows;
   hipLaunchKernelGGL(cfg_ddim_rescaled_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, pred, s->latents, s->coef, s->B, s->F, s->HW, s->c_latent, s->ld, s->guidance, s->pred_type, s->clip_sample, single, s->video_scale, s->variance_noise, s->sigma, s->clipped_model_output, (const float*)factor);
 }
@@ -493,6 +539,79 @@ extern "C" int fyc_cfg_ddim_step_rescaled(const fyc_cfg_ddim_rescale_args* a, vo
   else if (s->dtype == FYC_F16) cfg_rescale_launch<f16_t>(a, pl, st);
   else cfg_rescale_launch<float>(a, pl, st);
   FYC_CHECK_LAUNCH("fyc_cfg_ddim_step_rescaled");
+  return 0;
+}
+
+// ---- DPM-Solver multistep: guidance (+ rescale) + conversion + update -----------------------------------------------------------
+// the guidance fields of the solver's arguments as the DDIM step's struct: what the rescale plan and its moments launch read
+static fyc_cfg_ddim_args cfg_solver_guidance(const fyc_cfg_solver_args* a) {
+  fyc_cfg_ddim_args s = {};
+  s.pred = a->pred; s.latents = a->latents; s.coef = a->coef;
+  s.B = a->B; s.F = a->F; s.HW = a->HW; s.c_latent = a->c_latent; s.ld = a->ld; s.cfg = a->cfg; s.guidance = a->guidance;
+  s.dtype = a->dtype; s.pred_single = a->pred_single; s.video_scale = a->video_scale;
+  return s;
+}
+
+extern "C" int64_t fyc_cfg_solver_workspace_bytes(const fyc_cfg_solver_args* a) {
+  CfgRescalePlan pl;
+  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->cfg) return 0;
+  const fyc_cfg_ddim_args s = cfg_solver_guidance(a);
+  return cfg_rescale_plan(&s, pl) ? pl.bytes : 0;
+}
+
+template <typename T, bool RESCALE>
+static void cfg_solver_launch(const fyc_cfg_solver_args* a, const float* factor, hipStream_t st) {
+  const long long n = (long long)a->B * a->F * a->HW;
+  const dim3 grid(grid_for(n));
+  const T* pred = (const T*)a->pred;
+  const T* single = (const T*)a->pred_single;
+#define FYC_SOLVER_LAUNCH(ORDER)                                                                                                      \
+  hipLaunchKernelGGL((cfg_solver_kernel<T, ORDER, RESCALE>), grid, dim3(256), 0, st, pred, a->latents, a->coef, a->B, a->F, a->HW,    \
+                     a->c_latent, a->ld, a->cfg, a->guidance, single, a->video_scale, a->hist_out, a->hist_1, a->hist_2, factor)
+  if (a->order == 1) FYC_SOLVER_LAUNCH(1);
+  else if (a->order == 2) FYC_SOLVER_LAUNCH(2);
+  else FYC_SOLVER_LAUNCH(3);
+#undef FYC_SOLVER_LAUNCH
+}
+
+template <typename T>
+static void cfg_solver_dispatch(const fyc_cfg_solver_args* a, const CfgRescalePlan* pl, hipStream_t st) {
+  if (pl == nullptr) return cfg_solver_launch<T, false>(a, nullptr, st);
+  const fyc_cfg_ddim_args s = cfg_solver_guidance(a);
+  cfg_solver_launch<T, true>(a, cfg_rescale_factors<T>(&s, a->workspace, a->guidance_rescale, *pl, st), st);
+}
+
+extern "C" int fyc_cfg_solver_step(const fyc_cfg_solver_args* a, void* stream) {
+  FYC_REQUIRE(a && a->pred && a->latents && a->coef && a->hist_out, "fyc_cfg_solver_step: null pointer");
+  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_solver_step: bad dims");
+  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_cfg_solver_step: bad dtype %d", a->dtype);
+  FYC_REQUIRE(a->order >= 1 && a->order <= 3, "fyc_cfg_solver_step: order %d (1 .. 3)", a->order);
+  FYC_REQUIRE(a->order < 2 || a->hist_1 != nullptr, "fyc_cfg_solver_step: order %d needs hist_1", a->order);
+  FYC_REQUIRE(a->order < 3 || a->hist_2 != nullptr, "fyc_cfg_solver_step: order 3 needs hist_2");
+  // hist_out is written while other threads still read the latents and the histories: any overlap of the [n] f32 ranges is refused,
+  // not only equal bases
+  const int64_t n = (int64_t)a->B * a->c_latent * a->F * a->HW;
+  auto overlaps = [n](const float* p, const float* q) { return q != nullptr && p < q + n && q < p + n; };
+  FYC_REQUIRE(!overlaps(a->hist_out, a->latents), "fyc_cfg_solver_step: hist_out aliases latents");
+  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_1), "fyc_cfg_solver_step: hist_out aliases hist_1");
+  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_2), "fyc_cfg_solver_step: hist_out aliases hist_2");
+  FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_solver_step: pred_single needs classifier-free guidance (cfg = 1)");
+  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_solver_step: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
+  hipStream_t st = (hipStream_t)stream;
+  CfgRescalePlan pl;
+  const bool rescale = a->guidance_rescale > 0.f;
+  if (rescale) {
+    FYC_REQUIRE(a->cfg, "fyc_cfg_solver_step: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
+    const fyc_cfg_ddim_args s = cfg_solver_guidance(a);
+    FYC_REQUIRE(cfg_rescale_plan(&s, pl), "fyc_cfg_solver_step: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)a->F * a->HW * a->c_latent);
+    FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_solver_step: workspace is null or not 8-byte aligned");
+    FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_solver_step: workspace_bytes %lld < %lld (fyc_cfg_solver_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
+    FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_solver_step: fyc_init() not called");
+  }
+  if (a->dtype == FYC_BF16) cfg_solver_dispatch<bf16_t>(a, rescale ? &pl : nullptr, st);
+  else if (a->dtype == FYC_F16) cfg_solver_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
+  else cfg_solver_dispatch<float>(a, rescale ? &pl : nullptr, st);
+  FYC_CHECK_LAUNCH("fyc_cfg_solver_step");
   return 0;
 }
 

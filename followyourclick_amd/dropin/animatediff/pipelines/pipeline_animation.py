@@ -21,7 +21,7 @@ from typing import Callable, List, Optional, Union
 import numpy as np
 import torch
 
-from followyourclick_amd.engine.sampler import DDIMSampler, resolve_guidance_rescale
+from followyourclick_amd.engine.sampler import make_sampler, resolve_guidance_rescale
 
 
 @dataclass
@@ -250,7 +250,7 @@ class AnimationPipeline:
         # the reference's); the reference's scripts cannot pass it, for them the FYC_GUIDANCE_RESCALE environment switch (unset = 0 = off)
         guidance_rescale = resolve_guidance_rescale(kwargs.get("guidance_rescale"))
         engine = self.unet._get_engine()
-        sampler = DDIMSampler(engine, self.scheduler.engine_config)
+        sampler = make_sampler(engine, self.scheduler.engine_config)      # by the scheduler's engine_config type: DDIM or the multistep solver
         bar = self.progress_bar(total=num_inference_steps)
 
         def cb(i, t, lat):

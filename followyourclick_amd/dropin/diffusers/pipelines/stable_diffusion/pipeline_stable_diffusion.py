@@ -15,7 +15,7 @@ from typing import Callable, List, Optional, Union
 import numpy as np
 import torch
 
-from followyourclick_amd.engine.sampler import DDIMSampler
+from followyourclick_amd.engine.sampler import make_sampler
 
 
 @dataclass
@@ -166,7 +166,7 @@ class StableDiffusionPipeline:
         if eta != 0.0:
             raise NotImplementedError("StableDiffusionPipeline on the MI355X engine: eta > 0 (stochastic DDIM) is not implemented")
         if not hasattr(self.scheduler, "engine_config"):
-            raise TypeError("scheduler must be the drop-in diffusers.DDIMScheduler (the update runs as a fused HIP kernel)")
+            raise TypeError("scheduler must be the drop-in diffusers.DDIMScheduler or DPMSolverMultistepScheduler (the update runs as a fused HIP kernel)")
         batch_size = 1 if isinstance(prompt, str) else len(prompt)
         device = self._execution_device
         cfg_on = guidance_scale > 1.0
@@ -174,7 +174,7 @@ class StableDiffusionPipeline:
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.in_channels, height, width, text_embeddings.dtype,
                                        device, generator, latents)
-        sampler = DDIMSampler(self.unet._get_engine(), self.scheduler.engine_config)
+        sampler = make_sampler(self.unet._get_engine(), self.scheduler.engine_config)
         bar = self.progress_bar(total=num_inference_steps)
 
         def cb(i, t, lat):

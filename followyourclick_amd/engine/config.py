@@ -132,3 +132,22 @@ class DDIMConfig:
     # reference's arange(n) * (T // n) + steps_offset, which never reaches T - 1; "trailing" starts at T - 1, the step a
     # zero-terminal-SNR model was trained to see pure noise at; "linspace" spreads T - 1 .. 0 evenly
     timestep_spacing: str = "leading"
+
+
+@dataclass
+class SolverConfig:
+    """DPMSolverMultistepScheduler.__init__ kwargs (reference diffusers/schedulers/scheduling_dpmsolver_multistep.py:124-141) with the reference's
+    defaults, plus rescale_betas_zero_snr (an engine extension: the reference's class has no such kwarg, the shipped checkpoints need it).
+    thresholding (a per-sample quantile) and beta_schedule "squaredcos_cap_v2" are not implemented."""
+    num_train_timesteps: int = 1000
+    beta_start: float = 0.0001
+    beta_end: float = 0.02
+    beta_schedule: str = "linear"
+    trained_betas: object = None
+    solver_order: int = 2
+    prediction_type: str = "epsilon"
+    thresholding: bool = False
+    algorithm_type: str = "dpmsolver++"
+    solver_type: str = "midpoint"
+    lower_order_final: bool = True
+    rescale_betas_zero_snr: bool = False

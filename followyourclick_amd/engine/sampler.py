@@ -6,7 +6,8 @@ with classifier-free guidance, and - for a UNet built without the concat conditi
 StableDiffusionPipeline.__call__ (reference diffusers/pipelines/stable_diffusion/pipeline_stable_diffusion.py:522-541).  Per step: build the 9-channel channels-last input (one kernel instead
 of 3 zeros_like + 2 cat), UNet forward on the CFG pair, guidance + DDIM update (one kernel, no host
 sync).  Everything that is constant over the loop (text/IP K/V, all time embeddings, DDIM
-coefficients) is prepared once per clip.
+coefficients) is prepared once per clip.  SolverSampler is the same loop for a DPM-Solver multistep scheduler
+(the reference's loop is scheduler-agnostic): it shares the input build and the forward and differs in the schedule and the update kernel.
 """
 from __future__ import annotations
 
@@ -15,8 +16,8 @@ from typing import Callable, Optional, Sequence
 
 import torch
 
-from .config import DDIMConfig
-from .scheduler import DDIMTables
+from .config import DDIMConfig, SolverConfig
+from .scheduler import DDIMTables, SolverTables
 from .unet3d import UNet3DEngine
 from .weights import pad_channels
 
@@ -49,6 +50,14 @@ class DDIMSampler:
         self.tables = DDIMTables(ddim)
         self.clip_sample = bool(ddim.clip_sample)
 
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
+        """-> (timesteps, the host coefficient table [n][.] f32, further per-clip entries of the state `prepare` returns)"""
+        ts = self.tables.timesteps(num_steps)
+        for t in ts.tolist():           # a step at abar_t = 0 (trailing spacing on a zero-SNR table) that would divide by it
+            self.tables.check_step(t, use_clipped_model_output)
+        coef_host = self.tables.coefficient_table(num_steps, eta)
+        return ts, coef_host, dict(sigma=coef_host[:, 4].tolist())           # eta > 0: per-step std of the added noise (0 for eta = 0)
+
     @torch.no_grad()
     def prepare(self, text_embeddings: Tensor, num_steps: int, batch: int, guidance_scale: float,
                 fps: Optional[Sequence[float]] = None, flow: Optional[Sequence[float]] = None,
@@ -67,9 +76,7 @@ class DDIMSampler:
         beff = batch * (2 if cfg_on else 1)
         if text_embeddings.shape[0] != beff:
             raise ValueError(f"text_embeddings batch {text_embeddings.shape[0]} != {beff}")
-        ts = self.tables.timesteps(num_steps)
-        for t in ts.tolist():           # a step at abar_t = 0 (trailing spacing on a zero-SNR table) that would divide by it
-            self.tables.check_step(t, use_clipped_model_output)
+        ts, coef_host, sched = self.schedule(num_steps, eta, use_clipped_model_output)
 
         def dup(v):
             if v is None:
@@ -100,19 +107,16 @@ class DDIMSampler:
             extra["temb_first"] = temb0
         u.prepare_context(text_embeddings, ip_tokens)
         emb, temb = u.prepare_time_embeddings(ts.tolist(), dup(fps), dup(flow), beff, camera=dup(camera))
-        coef_host = self.tables.coefficient_table(num_steps, eta)
         coef = coef_host.to(u.device)
-        extra["sigma"] = coef_host[:, 4].tolist()           # eta > 0: per-step std of the added noise (0 for eta = 0)
+        extra.update(sched)
         return dict(timesteps=ts, temb=temb.reshape(num_steps, beff, -1), coef=coef, cfg=cfg_on, beff=beff,
                     guidance=float(guidance_scale), steps=num_steps, batch=batch, ctx_main=u.ctx_cache,
                     guidance_rescale=guidance_rescale, **extra)
 
     @torch.no_grad()
-    def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
-             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
-             guidance_rescale: float = 0.0) -> None:
-        """one DDIM step, latents (B,4,F,h,w) f32 updated in place.  guidance_rescale = 0: ops.cfg_ddim_step as ever; above 0: ops.cfg_ddim_step_rescaled.  variance_noise (latents' shape, f32): the noise of a stochastic
-        step (eta > 0, reference scheduling_ddim.py:346-363), scaled by the step's sigma from `prepare(eta=...)`."""
+    def predict(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor]):
+        """the part of a step every scheduler shares: pin frame 0 (first_frame_condition), build the UNet input, run the forward(s)
+        -> (pred [cfg B F HW][ld], the per-frame unconditional prediction or None)"""
         u, o = self.unet, self.unet.ops
         B, CL, F, H, W = latents.shape
         cp = pad_channels(u.cfg.conv_in_channels)
@@ -148,6 +152,17 @@ class DDIMSampler:
             u.ctx_cache = st["ctx_single"]
             single = u.forward(x[: B * F * H * W], st["temb_single"][i], B * F, 1, H, W)
             u.ctx_cache = st["ctx_main"]
+        return pred, single
+
+    @torch.no_grad()
+    def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
+             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
+             guidance_rescale: float = 0.0) -> None:
+        """one DDIM step, latents (B,4,F,h,w) f32 updated in place.  guidance_rescale = 0: ops.cfg_ddim_step as ever; above 0: ops.cfg_ddim_step_rescaled.  variance_noise (latents' shape, f32): the noise of a stochastic
+        step (eta > 0, reference scheduling_ddim.py:346-363), scaled by the step's sigma from `prepare(eta=...)`."""
+        o = self.unet.ops
+        B, CL, F, H, W = latents.shape
+        pred, single = self.predict(st, i, latents, first_image_latents, mask)
         kw = dict(B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1], cfg=st["cfg"],
                   guidance=st["guidance"], pred_type=self.tables.pred_type, clip_sample=self.clip_sample,
                   pred_single=single, video_scale=st.get("video_scale", 0.0),
@@ -219,3 +234,56 @@ class DDIMSampler:
             if callback is not None and i % callback_steps == 0:
                 callback(i, ts[i], latents)
         return latents
+
+
+class SolverSampler(DDIMSampler):
+    """The same loop with a DPM-Solver multistep scheduler (engine/scheduler.py::SolverTables; the reference's loop is scheduler-agnostic,
+    pipeline_animation.py:712, :767).  Input build and UNet forward are DDIMSampler.predict; `prepare` differs in the schedule (linspace
+    timesteps, the per-step order, the table of collapsed coefficients) and the update is ops.cfg_solver_step.  The sampler owns three
+    latent-shaped f32 history buffers (the converted outputs of this step and of the two before) and rotates their roles per step; because
+    those pointers change per step nothing is replayed from a captured graph.  eta, generator and use_clipped_model_output are accepted and
+    unused, as the reference's prepare_extra_step_kwargs drops them for a scheduler whose step() does not take them; there is no clip_sample."""
+
+    def __init__(self, unet: UNet3DEngine, solver: SolverConfig):
+        self.unet = unet
+        self.tables = SolverTables(solver)
+        self.clip_sample = False
+
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
+        ts = self.tables.timesteps(num_steps)
+        coef_host = self.tables.coefficient_table(num_steps)          # (checks every step: a zero-SNR first step the family cannot take)
+        return ts, coef_host, dict(orders=self.tables.plan(num_steps), hist=[])
+
+    @torch.no_grad()
+    def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
+             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
+             guidance_rescale: float = 0.0) -> None:
+        """one solver step, latents (B,4,F,h,w) f32 updated in place; the steps of a clip are taken in order from i = 0 (the history is the state)"""
+        B, CL, F, H, W = latents.shape
+        phi = check_guidance_rescale(guidance_rescale)
+        if phi > 0 and not st["cfg"]:
+            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        hist = st["hist"]
+        if len(hist) != 3 or hist[0].shape != latents.shape or hist[0].device != latents.device:
+            hist[:] = [torch.empty_like(latents) for _ in range(3)]
+        pred, single = self.predict(st, i, latents, first_image_latents, mask)
+        order = st["orders"][i]
+        self.unet.ops.cfg_solver_step(pred, latents, st["coef"][i], hist_out=hist[i % 3], hist_1=hist[(i - 1) % 3] if order >= 2 else None,
+                                      hist_2=hist[(i - 2) % 3] if order == 3 else None, order=order, B=B, F=F, HW=H * W, c_latent=CL,
+                                      ld=pred.shape[1], cfg=st["cfg"], guidance=st["guidance"], pred_single=single,
+                                      video_scale=st.get("video_scale", 0.0), guidance_rescale=phi)
+
+    @torch.no_grad()
+    def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float, *args, use_graph: Optional[bool] = None,
+               eta: float = 0.0, generator=None, use_clipped_model_output: bool = False, **kwargs) -> Tensor:
+        return super().sample(latents, text_embeddings, num_steps, guidance_scale, *args, use_graph=False, eta=0.0, generator=None,
+                              use_clipped_model_output=False, **kwargs)
+
+
+def make_sampler(unet: UNet3DEngine, scheduler_config) -> DDIMSampler:
+    """the sampler of a scheduler's engine_config: SolverConfig -> SolverSampler, DDIMConfig -> DDIMSampler"""
+    if isinstance(scheduler_config, SolverConfig):
+        return SolverSampler(unet, scheduler_config)
+    if isinstance(scheduler_config, DDIMConfig):
+        return DDIMSampler(unet, scheduler_config)
+    raise TypeError(f"no sampler for a scheduler config of type {type(scheduler_config).__name__} (DDIMConfig or SolverConfig)")

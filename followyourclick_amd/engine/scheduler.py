@@ -14,7 +14,7 @@ from typing import List
 import numpy as np
 import torch
 
-from .config import DDIMConfig
+from .config import DDIMConfig, SolverConfig
 
 PRED_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 
@@ -99,3 +99,153 @@ class DDIMTables:
     def coefficient_table(self, num_inference_steps: int, eta: float = 0.0) -> torch.Tensor:
         ts = self.timesteps(num_inference_steps).tolist()
         return torch.tensor([self.step_coefficients(t, num_inference_steps, eta) for t in ts], dtype=torch.float32)
+
+
+class SolverTables:
+    """DPM-Solver multistep on the host (reference diffusers/schedulers/scheduling_dpmsolver_multistep.py; arXiv:2206.00927, arXiv:2211.01095).
+
+    alpha_t, sigma_t and lambda_t are the reference's f32 op sequence (:165-170), bit-identical tables.  Every update of the family is linear in
+    the current latents x, the (guided) prediction v and the stored converted outputs m1, m2, so a step collapses to six numbers:
+
+        m0 = a_x x + a_v v                          (convert_model_output, :234-280)
+        x' = c_x x + c_0 m0 + c_1 m1 + c_2 m2       (:304-426 with D1, D2 expanded)
+
+    The scalars the reference forms (h, r0, r1, exp(-+h) - 1, the heun and third-order factors) are formed in f32 tensor arithmetic in its order
+    - its (exp(-h) - 1) / h + 1 cancels in f32, and a step computed from f64 scalars would sit two hundred ulps from it -, then collapsed in f64
+    and rounded once each to f32; the update itself is the fused guidance + solver kernel (fyc_cfg_solver_step)."""
+
+    def __init__(self, cfg: SolverConfig):
+        self.cfg = cfg
+        n = cfg.num_train_timesteps
+        if cfg.thresholding:
+            raise NotImplementedError("thresholding=True (dynamic thresholding, a per-sample quantile of x0) is not implemented for SolverTables")
+        if cfg.trained_betas is not None:
+            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
+        elif cfg.beta_schedule == "linear":
+            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
+        elif cfg.beta_schedule == "scaled_linear":
+            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
+        else:
+            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for SolverTables")
+        if cfg.rescale_betas_zero_snr:
+            betas = rescale_zero_terminal_snr(betas)
+        if cfg.algorithm_type not in ("dpmsolver", "dpmsolver++"):
+            raise NotImplementedError(f"{cfg.algorithm_type} is not implemented for SolverTables")
+        if cfg.solver_type not in ("midpoint", "heun"):
+            raise NotImplementedError(f"{cfg.solver_type} is not implemented for SolverTables")
+        if cfg.solver_order not in (1, 2, 3):
+            raise ValueError(f"solver_order given as {cfg.solver_order} must be 1, 2 or 3")
+        if cfg.prediction_type not in PRED_TYPES:
+            raise ValueError(f"prediction_type given as {cfg.prediction_type} must be one of `epsilon`, `sample`, or `v_prediction`")
+        self.betas = betas
+        self.alphas = 1.0 - betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.pred_type = PRED_TYPES[cfg.prediction_type]
+        self.plus = cfg.algorithm_type == "dpmsolver++"
+
+    def timesteps(self, num_inference_steps: int) -> torch.Tensor:
+        """set_timesteps (:199-204): linspace(0, T - 1, n + 1).round()[::-1][:-1].  An n that rounds two entries to the same timestep is refused:
+        the reference's step() finds its place by `timesteps == t`, and a zero-length step has h = 0"""
+        T, n = self.cfg.num_train_timesteps, int(num_inference_steps)
+        if n < 1:
+            raise ValueError(f"num_inference_steps = {num_inference_steps} must be at least 1")
+        ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        if len(np.unique(ts)) != n:
+            raise ValueError(f"num_inference_steps n = {n} gives duplicate timesteps with {T} training timesteps: choose n < {T}")
+        return torch.from_numpy(ts)
+
+    def next_order(self, step_index: int, num_steps: int, lower_order_nums: int) -> int:
+        """the order step() takes at a step (:463-489) after `lower_order_nums` earlier steps (counted up to solver_order)"""
+        short = self.cfg.lower_order_final and num_steps < 15
+        if self.cfg.solver_order == 1 or lower_order_nums < 1 or (short and step_index == num_steps - 1):
+            return 1
+        if self.cfg.solver_order == 2 or lower_order_nums < 2 or (short and step_index == num_steps - 2):
+            return 2
+        return 3
+
+    def plan(self, num_inference_steps: int) -> List[int]:
+        """per step, the order actually used: the warm-up from first order and the lower-order final steps of a schedule shorter than 15"""
+        orders, low = [], 0
+        for i in range(num_inference_steps):
+            orders.append(self.next_order(i, num_inference_steps, low))
+            low = min(low + 1, self.cfg.solver_order)
+        return orders
+
+    def check_step(self, t: int) -> None:
+        """At alphas_cumprod[t] = 0 (the first step of a zero-terminal-SNR table) lambda_t is -inf.  dpmsolver++ with v_prediction or sample stays
+        finite there, as in the reference: the first step degenerates to sigma_prev x + alpha_prev x0 and the next step's 1 / r0 is 0.  Epsilon
+        prediction divides by alpha_t = 0 and dpmsolver multiplies by exp(h) = inf: both are refused at such a timestep."""
+        if float(self.alphas_cumprod[t]) != 0.0:
+            return
+        if not self.plus:
+            raise ValueError(f"timestep {t}: alphas_cumprod is 0 there (zero terminal SNR, lambda = -inf) and algorithm_type 'dpmsolver' "
+                             "integrates exp(h) = inf over it; such a step needs algorithm_type 'dpmsolver++'")
+        if self.pred_type == PRED_TYPES["epsilon"]:
+            raise ValueError(f"timestep {t}: alphas_cumprod is 0 there (zero terminal SNR) and epsilon prediction divides by its square "
+                             "root; such a step needs prediction_type 'v_prediction' or 'sample'")
+
+    def convert_coefficients(self, t: int) -> List[float]:
+        """(a_x, a_v) of m0 = a_x x + a_v v (:234-280): x0 for dpmsolver++, eps for dpmsolver, from the f32 table entries, in f64"""
+        a, s = float(self.alpha_t[t]), float(self.sigma_t[t])
+        pred = self.cfg.prediction_type
+        if self.plus:
+            if pred == "epsilon":           # x0 = (x - sigma_t v) / alpha_t; alpha_t = 0 is refused by check_step
+                return [1.0 / a, -s / a] if a != 0.0 else [float("nan"), float("nan")]
+            return [a, -s] if pred == "v_prediction" else [0.0, 1.0]            # x0 = alpha_t x - sigma_t v;  x0 = v
+        if pred == "sample":                # eps = (x - alpha_t v) / sigma_t
+            return [1.0 / s, -a / s] if s != 0.0 else [float("nan"), float("nan")]
+        return [s, a] if pred == "v_prediction" else [0.0, 1.0]                 # eps = alpha_t v + sigma_t x;  eps = v
+
+    def step_scalars(self, ts: List[int], i: int, order: int) -> dict:
+        """the scalars of step i of the schedule `ts` at an order, each formed as the reference forms it (f32 tensor arithmetic, its order of
+        operations) -> python floats holding those f32 values: cx (the factor of the sample), k0, k1, k2 (the signed factors of D0, D1, D2),
+        inv_r0 = 1 / r0, inv_r1 = 1 / r1, w = r0 / (r0 + r1), u = 1 / (r0 + r1).  Only what the order uses is formed: at an infinite h (the first
+        step from lambda = -inf) the higher-order factors are inf / inf."""
+        lam, al, sg = self.lambda_t, self.alpha_t, self.sigma_t
+        t, s0 = (0 if i == len(ts) - 1 else ts[i + 1]), ts[i]
+        h = lam[t] - lam[s0]
+        if self.plus:
+            cx, lead, e, hh = sg[t] / sg[s0], al[t], torch.exp(-h) - 1.0, h
+        else:
+            cx, lead, e, hh = al[t] / al[s0], sg[t], torch.exp(h) - 1.0, -h
+        out = dict(cx=cx, k0=-(lead * e))
+        if order == 2 and self.cfg.solver_type == "midpoint":
+            out["k1"] = -(0.5 * (lead * e))
+        elif order >= 2:
+            # dpmsolver++: + alpha_t ((exp(-h) - 1) / h + 1);  dpmsolver: - sigma_t ((exp(h) - 1) / h - 1)
+            out["k1"] = lead * (e / h + 1.0) if self.plus else -(lead * (e / h - 1.0))
+        if order == 3:
+            # dpmsolver++: (exp(-h) - 1 + h) / h^2 - 0.5;  dpmsolver: (exp(h) - 1 - h) / h^2 - 0.5
+            out["k2"] = -(lead * ((e + hh) / h ** 2 - 0.5))
+        if order >= 2:
+            r0 = (lam[s0] - lam[ts[i - 1]]) / h
+            out["inv_r0"] = 1.0 / r0
+        if order == 3:
+            r1 = (lam[ts[i - 1]] - lam[ts[i - 2]]) / h
+            out["inv_r1"], out["w"], out["u"] = 1.0 / r1, r0 / (r0 + r1), 1.0 / (r0 + r1)
+        return {k: float(v) for k, v in out.items()}
+
+    def step_coefficients(self, ts: List[int], i: int, order: int) -> List[float]:
+        """{a_x, a_v, c_x, c_0, c_1, c_2, 0, 0} of step i: the f32 scalars collapsed in f64.  An infinite h_0 or h_1 (a history entry taken at
+        lambda = -inf) enters only through 1 / r0, 1 / r1, w and u, which the f32 arithmetic has already turned into 0: the products below are of
+        finite numbers, never inf * 0."""
+        s = self.step_scalars(ts, i, order)
+        c0, c1, c2 = s["k0"], 0.0, 0.0
+        if order == 2:          # D1 = (1 / r0) (m0 - m1)
+            d = s["k1"] * s["inv_r0"]
+            c0, c1 = c0 + d, -d
+        elif order == 3:        # D1_0 = (m0 - m1) / r0, D1_1 = (m1 - m2) / r1, D1 = D1_0 + w (D1_0 - D1_1), D2 = u (D1_0 - D1_1)
+            g0 = (s["k1"] * (1.0 + s["w"]) + s["k2"] * s["u"]) * s["inv_r0"]        # the factor of m0 - m1
+            g1 = -(s["k1"] * s["w"] + s["k2"] * s["u"]) * s["inv_r1"]               # the factor of m1 - m2
+            c0, c1, c2 = c0 + g0, g1 - g0, -g1
+        return [*self.convert_coefficients(ts[i]), s["cx"], c0, c1, c2, 0.0, 0.0]
+
+    def coefficient_table(self, num_inference_steps: int) -> torch.Tensor:
+        """[n][8] f32, each entry rounded once, for the orders of plan(n)"""
+        ts = self.timesteps(num_inference_steps).tolist()
+        for t in ts:
+            self.check_step(t)
+        return torch.tensor([self.step_coefficients(ts, i, o) for i, o in enumerate(self.plan(num_inference_steps))], dtype=torch.float64).float()

@@ -577,6 +577,37 @@ class HipOps:
             r.workspace, r.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
         self._call("fyc_cfg_ddim_step_rescaled", r)
 
+    def cfg_solver_step(self, pred: Tensor, latents: Tensor, coef: Tensor, *, hist_out: Tensor, hist_1: Optional[Tensor] = None,
+                        hist_2: Optional[Tensor] = None, order: int, B: int, F: int, HW: int, c_latent: int, ld: int, cfg: bool,
+                        guidance: float, pred_single: Optional[Tensor] = None, video_scale: float = 0.0,
+                        guidance_rescale: float = 0.0) -> None:
+        """guidance + one DPM-Solver multistep update (include/fyc.h, fyc_cfg_solver_step): coef f32[8] = {a_x, a_v, c_x, c_0, c_1, c_2, -, -};
+        latents are updated in place, hist_out receives this step's converted output, hist_1 / hist_2 hold those of the two steps before
+        (read only at order >= 2 / 3).  The moments workspace of the guidance rescale is the one cfg_ddim_step_rescaled keeps."""
+        self.ensure_init(pred.device)
+        if coef.numel() < 8:
+            raise ValueError(f"cfg_solver_step: coef holds {coef.numel()} values, the kernel's table row has 8")
+        for name, h in (("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2)):
+            if h is not None and h.numel() != latents.numel():
+                raise ValueError(f"cfg_solver_step: {name} must have the latents' shape")
+        if pred_single is not None and pred_single.dtype != pred.dtype:
+            raise TypeError("cfg_solver_step: pred_single dtype differs from pred")
+        a = L.CfgSolverArgs()
+        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
+        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
+        a.pred_single, a.video_scale = _p(pred_single), video_scale
+        a.hist_out, a.hist_1, a.hist_2, a.order = _f32(hist_out, "hist_out"), _f32(hist_1, "hist_1"), _f32(hist_2, "hist_2"), int(order)
+        a.guidance_rescale = float(guidance_rescale)
+        key = ("cfg_solver", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg))
+        need = self._ws_need.get(key)
+        if need is None:
+            need = self._ws_need[key] = int(self.lib.fyc_cfg_solver_workspace_bytes(C.byref(a)))
+        if need > 0:
+            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
+                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+            a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._call("fyc_cfg_solver_step", a)
+
     def nchw_to_nhwc(self, z: Tensor, x: Tensor, *, N: int, C_: int, HW: int, c_pad: int, scale: float) -> None:
         self.ensure_init(z.device)
         a = L.NchwInArgs()

@@ -399,6 +399,33 @@ typedef struct { fyc_cfg_ddim_args step; float guidance_rescale; void* workspace
 int64_t fyc_cfg_ddim_rescale_workspace_bytes(const fyc_cfg_ddim_rescale_args* a);
 int fyc_cfg_ddim_step_rescaled(const fyc_cfg_ddim_rescale_args* a, void* stream);
 
+/* (308, added entry points) Classifier-free guidance + one step of the DPM-Solver multistep family in one pass (arXiv:2206.00927,
+ * arXiv:2211.01095; scheduling_dpmsolver_multistep.py:234-280 convert_model_output, :304-426 the first / second / third order updates of
+ * dpmsolver++ and dpmsolver, midpoint and heun).  Every update of the family is linear in the latents x, the guided prediction v and the
+ * converted outputs of the previous steps, so the host collapses a step to six numbers, coef (device f32[8], the last two are padding) =
+ * {a_x, a_v, c_x, c_0, c_1, c_2}:
+ *   v  = the guided prediction exactly as fyc_cfg_ddim_step forms it; with guidance_rescale > 0 times the per-sample factor of
+ *        fyc_cfg_ddim_step_rescaled (the same moments and factor launches run in front: no atomics, the same call gives the same bits)
+ *   m0 = a_x x + a_v v                                       (x0 for dpmsolver++, eps for dpmsolver; any prediction type)
+ *   x' = c_x x + c_0 m0 + c_1 hist_1 + c_2 hist_2            (summed left to right)
+ * latents (B,c_latent,F,h,w) f32 is updated in place to x'; hist_out (same shape, f32) receives m0; hist_1 / hist_2 are the m0 of the
+ * previous step and of the one before.  hist_1 is read only when order >= 2 and hist_2 only when order == 3: an unused history may be NULL
+ * or uninitialised (NaN included) without reaching the result.  pred, pred_single, cfg, guidance, video_scale, ld, dtype: as in
+ * fyc_cfg_ddim_args.  Refused before anything is launched: NULL pred / latents / coef / hist_out, bad dims, order outside 1..3, a NULL
+ * history the order reads, hist_out overlapping latents, hist_1 or hist_2, pred_single without cfg, and what fyc_cfg_ddim_step_rescaled
+ * refuses of guidance_rescale, cfg and the workspace (fyc_cfg_solver_workspace_bytes() bytes, 8-byte aligned; 0 = none needed). */
+typedef struct {
+  const void* pred; float* latents; const float* coef;
+  int32_t B, F, HW, c_latent, ld, cfg; float guidance;
+  int32_t dtype;
+  const void* pred_single; float video_scale;
+  float* hist_out; const float* hist_1; const float* hist_2;
+  int32_t order;
+  float guidance_rescale; void* workspace; int64_t workspace_bytes;
+} fyc_cfg_solver_args;
+int64_t fyc_cfg_solver_workspace_bytes(const fyc_cfg_solver_args* a);
+int fyc_cfg_solver_step(const fyc_cfg_solver_args* a, void* stream);
+
 /* VAE ends: z (N,4,h,w) f32 * scale -> channels-last [N][hw][c_pad];
  * image channels-last [N][HW][ld] -> (N,3,H,W) f32 = clamp(x/2+0.5, 0, 1) (pipeline_animation.py:402,410) */
 typedef struct { const float* z; void* x; int32_t N, C, HW, c_pad; float scale; int32_t dtype; } fyc_nchw_in_args;
