@@ -45,6 +45,10 @@ class AttnMaskArgs(C.Structure):      # (ABI 308) fyc_attention_masked: the atte
     _fields_ = [("attn", AttnArgs), ("causal", i32)]
 
 
+class ConvUpPhasesArgs(C.Structure):      # (308, added entry points) fyc_conv_up_phases: the GEMM's arguments as they are, the group rows behind them
+    _fields_ = [("gemm", GemmArgs), ("group_rows", i32)]
+
+
 class TAttnArgs(C.Structure):
     _fields_ = [("qkv", vp), ("o", vp), ("clips", i32), ("frames", i32), ("pixels", i32), ("heads", i32), ("d", i32),
                 ("scale", f32), ("dtype", i32), ("rope_cos", vp), ("rope_sin", vp), ("f32_products", i32)]
@@ -179,10 +183,11 @@ OPS = {
     "fyc_gn_apply_cs": GnApplyCsArgs, "fyc_chan_stats_reduce": ChanStatsReduceArgs,
     "fyc_pack_conv3x3": PackConv3x3Args, "fyc_pack_geglu": PackGegluArgs, "fyc_temporal_block": TemporalBlockArgs,
     "fyc_ff_block": FFBlockArgs, "fyc_panel_linear": PanelLinearArgs, "fyc_repeat": RepeatArgs,
+    "fyc_conv_up_phases": ConvUpPhasesArgs,
 }
 MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set_tuning", "fyc_gemm_row_parts", "fyc_gemm_stat_layout", "fyc_gemm_workspace_bytes", "fyc_gn_stats_workspace", "fyc_temporal_block_supported", "fyc_temporal_block_wstream_bytes",
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes",
-        "fyc_cfg_ddim_rescale_workspace_bytes", "fyc_cfg_solver_workspace_bytes"]
+        "fyc_cfg_ddim_rescale_workspace_bytes", "fyc_cfg_solver_workspace_bytes", "fyc_conv_up_phases_stat_layout", "fyc_conv_up_phases_supported"]
 
 _lib = None
 FYC_VERSION = 308        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
@@ -243,6 +248,11 @@ def load() -> C.CDLL:
     if not ab_build or hasattr(lib, "fyc_cfg_solver_workspace_bytes"):
         lib.fyc_cfg_solver_workspace_bytes.argtypes = [C.POINTER(CfgSolverArgs)]
         lib.fyc_cfg_solver_workspace_bytes.restype = i64
+    if not ab_build or hasattr(lib, "fyc_conv_up_phases_supported"):
+        lib.fyc_conv_up_phases_supported.argtypes = [i32] * 7
+        lib.fyc_conv_up_phases_supported.restype = C.c_int
+        lib.fyc_conv_up_phases_stat_layout.argtypes = [C.POINTER(ConvUpPhasesArgs), C.POINTER(i32), C.POINTER(i32)]
+        lib.fyc_conv_up_phases_stat_layout.restype = C.c_int
     for name, st in OPS.items():
         if ab_build and not hasattr(lib, name):
             continue

@@ -34,6 +34,16 @@ namespace fycg {
 
 constexpr int FYC_MAX_DEVICES = 64;
 
+// Internal kernel mode beside the public FYC_GEMM_* values (never a value of fyc_gemm_args::mode; host: conv_up_phases.hip): nearest-2x upsampling + 3x3
+// convolution as four 2x2 convolutions of the LOW-resolution input, one per output phase (py, px) = parity of the output pixel.  On the upsampled image every
+// input pixel appears 2x2 times, so the three filter rows an output pixel (2y + py, 2x + px) touches collapse onto two input rows (py = 0: row y - 1 with
+// W[ky=0], row y with W[1] + W[2]; py = 1: row y with W[0] + W[1], row y + 1 with W[2]), columns alike: K = 4 * Cin with weights pre-summed at pack time
+// instead of 9 * Cin.  Rows of the problem are VIRTUAL, ordered [group][phase = 2 py + px][row in group]; a group is up_rows consecutive input pixels (whole
+// frames: one statistics sample of the consuming GroupNorm), up_rows % BM == 0, so a row tile has one phase and lies in one group.  The A gather is the CONV3X3
+// one with 4 taps whose top-left is (y - 1 + py, x - 1 + px) on the Hin x Win image (zero padding maps onto itself); the weights are [4 phases][N][ldw], and the
+// epilogue stores virtual row m at the output pixel's row ((frame * 2 Hin + 2 y + py) * 2 Win + 2 x + px).
+constexpr int GEMM_MODE_UP_PHASES = 16;
+
 struct GemmP {
   const char* a; const char* a2; const char* w; const float* bias; const float* rowbias; const char* residual; char* out;
   char* seg_out[3]; int seg_transposed[3]; int seg_ld[3];
@@ -68,6 +78,7 @@ struct GemmP {
   unsigned long long* trace;   // timing builds (-DFYC_TRACE, tools/gemm_phase_probe.py): per-block s_memtime stamps; nullptr otherwise
 };
 // (t3_frames / t3_rows sit in the two alignment holes the struct had: its size and every kernel-argument offset of the older modes stay put)
+// (GEMM_MODE_UP_PHASES adds no field either: t3_rows holds its rows per group, up_sw the reciprocal 1 / Win of its output row map)
 static_assert(sizeof(GemmP) == 392, "GemmP grew: the kernel-argument offsets of every instantiation move");
 
 // timing builds: waves 0 and 4 of a block append the shader clock to their list ([block][2][128] u64, zeroed by the host; the
@@ -475,6 +486,16 @@ __device__ __forceinline__ void epilogue_linear_packed(const GemmP& p, f32x4 (&a
   const int n_lane = n_w0 + lch * 8;                 // this lane's 8 output columns
   const int first_sample = do_cs ? (tile_m * BM) / p.cs_rows : 0;
   const bool one_slot = p.cs_slots == 1;
+  // UP_PHASES: virtual row m0 + d of this tile is input pixel q = q0 + d (frame-major over Hin x Win) in phase (py, px) and is stored at output row
+  //   (frame * 2 Hin + 2 y + py) * 2 Win + 2 x + px  =  4 q - 2 x + 2 py Win + px,   x = q mod Win = (q0 mod Win + d) mod Win
+  // - one division per tile; per row a 3-instruction fdiv_small (q0 mod Win + d < Win + BM <= 2^16, host: Win <= 4096)
+  int up_xb = 0, up_o0 = 0;
+  if constexpr (MODE == GEMM_MODE_UP_PHASES) {
+    const int m0 = tile_m * BM, vs = m0 / p.t3_rows, phase = vs & 3;      // vs = 4 * group + phase
+    const int q0 = (vs >> 2) * p.t3_rows + (m0 - vs * p.t3_rows);
+    up_xb = q0 % p.Win;
+    up_o0 = 4 * q0 + 2 * (phase >> 1) * p.Win + (phase & 1);              // (stored row = up_o0 + 4 d - 2 x; 4 q < M < 2^31)
+  }
   float cs8[8], cq8[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) cs8[e] = cq8[e] = 0.f;
@@ -534,9 +555,14 @@ __device__ __forceinline__ void epilogue_linear_packed(const GemmP& p, f32x4 (&a
       const int m = tile_m * BM + (wm * WTM + i) * 16 + row;
       float rsum = 0.f, rsq = 0.f;
       const bool live = lact && row < 16 && m < p.M && n_lane < p.N;
+      int mo = m;                                          // the row of `out` virtual row m is stored at
+      if constexpr (MODE == GEMM_MODE_UP_PHASES) {
+        const int d = (wm * WTM + i) * 16 + row, xd = up_xb + d;
+        mo = up_o0 + 4 * d - 2 * (xd - fdiv_small(xd, p.up_sw) * p.Win);
+      }
       if (live) {
         const u32x4 v4 = v4q;
-        *reinterpret_cast<u32x4*>(O + (long long)m * p.ldo + n_lane) = v4;   // (nt stores: same GEMM time, consumers +10 %: profiles/r04_epilogue_nontemporal_ab.txt)
+        *reinterpret_cast<u32x4*>(O + (long long)mo * p.ldo + n_lane) = v4;   // (nt stores: same GEMM time, consumers +10 %: profiles/r04_epilogue_nontemporal_ab.txt)
         if (do_cs || do_rp) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -859,6 +885,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[BM / 
                                               long long bz, char* stg_stage, int wave, int lane, const char* pre, int& ecnt) {
   constexpr int WTM = BM / WGM / 16, WTN = BN / WGN / 16;
   constexpr bool LN = (MODE == FYC_GEMM_PLAIN);   // the folded LayerNorm only exists for plain GEMMs: keep it out of the conv kernels
+  // the output row map of UP_PHASES lives in ONE store site, epilogue_linear_packed's: no other epilogue is built for the mode
+  static_assert(MODE != GEMM_MODE_UP_PHASES || (WIDE && EPI == FYC_EPI_LINEAR && sizeof(T) == 2), "UP_PHASES: the packed 16-bit LINEAR epilogue only");
   const int wm = wave / WGN, wn = wave % WGN;
   const int g = lane >> 4, r16 = lane & 15;
   // ---- epilogue: lane holds out[m][n0 .. n0+3] per (i, j) ---------------------------------
@@ -1305,12 +1333,13 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   // conv: per row, pixel position of the top-left tap (pos0 = frame base + iy0*Win + ix0, may point outside the image) and a
   // 9-bit mask of the taps that fall inside the image (0 for rows beyond M) - built once per tile (KT = 45..360 K tiles follow);
   // per K tile a gather address is pos0 + tap offset (scalar) -> one 64-bit multiply-add
-  constexpr bool C3 = (MODE == FYC_GEMM_CONV3X3);
+  constexpr bool UPP = (MODE == GEMM_MODE_UP_PHASES);      // the CONV3X3 gather with 4 taps (2x2) and a 4-bit mask; phase and group are tile-uniform
+  constexpr bool C3 = (MODE == FYC_GEMM_CONV3X3) || UPP;
   // frame-axis conv (CONV_T3): output row m reads rows m - HW, m, m + HW of the same clip - the tap shift is a whole number of rows and the same
   // for every row, so the base is the PLAIN one (a_base) and the only per-row state is a 3-bit presence mask (0 for rows beyond M), packed for
   // all A_IT rows of the thread into one register
   constexpr bool T3 = (MODE == FYC_GEMM_CONV_T3);
-  constexpr int TAPS = T3 ? 3 : 9;
+  constexpr int TAPS = T3 ? 3 : UPP ? 4 : 9;
   static_assert(!T3 || A_IT * 3 <= 32, "CONV_T3: the presence masks of a thread's rows share one register");
   int a_pos[C3 ? A_IT : 1], a_msk[C3 ? A_IT : 1];
   unsigned t_msk = 0, t_step = 0;     // CONV_T3: packed masks; element offset of one frame (HW * Cin)
@@ -1341,6 +1370,26 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
         const int f = (m / p.t3_rows) % p.t3_frames;
         const unsigned msk = (f > 0 ? 1u : 0u) | 2u | (f + 1 < p.t3_frames ? 4u : 0u);
         if (m < p.M) t_msk |= msk << (3 * it);
+      }
+    } else if constexpr (UPP) {
+      // virtual rows [group][phase][row in group]: this tile's virtual sample vs = 4 * group + phase; its rows are the input pixels q0 + (row in tile)
+      const int m0 = i_tm * BM, vs = m0 / p.t3_rows, phase = vs & 3;
+      const int q0 = (vs >> 2) * p.t3_rows + (m0 - vs * p.t3_rows);
+      b_base += (unsigned)phase * (unsigned)p.N * (unsigned)p.ldw;      // weights [4 phases][N][ldw]
+      const int hw = p.Hin * p.Win;
+#pragma unroll
+      for (int it = 0; it < A_IT; ++it) {
+        const int q = q0 + lrow + it * ROWS_IT;
+        const int fr = q / hw, rem = q - fr * hw, y = rem / p.Win, x = rem - y * p.Win;
+        const int iy0 = y - 1 + (phase >> 1), ix0 = x - 1 + (phase & 1);      // top-left of the 2x2 taps
+        a_pos[it] = fr * hw + iy0 * p.Win + ix0;
+        int msk = 0;
+#pragma unroll
+        for (int tp = 0; tp < 4; ++tp) {
+          const int iy = iy0 + (tp >> 1), ix = ix0 + (tp & 1);
+          if ((unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win) msk |= 1 << tp;
+        }
+        a_msk[it] = (m0 + lrow + it * ROWS_IT < p.M) ? msk : 0;
       }
     } else {
 #pragma unroll
@@ -1378,7 +1427,7 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
       const unsigned e = a_base + (unsigned)(it * ROWS_IT) * (unsigned)p.Cin + (unsigned)(tap - 1) * t_step + (unsigned)c0;
       return ((t_msk >> (3 * it + tap)) & 1u) ? A + (size_t)e : zero;
     } else if (C3) {
-      const int ky = tap / 3, kx = tap - 3 * ky;                      // wave-uniform
+      const int ky = UPP ? tap >> 1 : tap / 3, kx = UPP ? tap & 1 : tap - 3 * ky;      // wave-uniform
       const int pos = a_pos[it] + ky * p.Win + kx;
       return ((a_msk[it] >> tap) & 1) ? A + (size_t)((unsigned)pos * (unsigned)p.Cin + (c0 + koff)) : zero;
     } else {  // nearest-upsampled input of virtual size (Hout, Wout): F.interpolate(mode="nearest") folded into the gather
@@ -1799,5 +1848,8 @@ int run_f16_act(const GemmP& p, int batch, int cfg, hipStream_t st);
 int run_bf16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_f16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
 int run_f32_t3(const GemmP& p, int batch, int cfg, hipStream_t st);
+// nearest-2x upsample + 3x3 as four 2x2 phase convolutions (GEMM_MODE_UP_PHASES; entry: conv_up_phases.hip): conv_up_phases_{bf16,f16}.hip
+int run_bf16_up_phases(const GemmP& p, int cfg, int ns, hipStream_t st);
+int run_f16_up_phases(const GemmP& p, int cfg, int ns, hipStream_t st);
 
 }  // namespace fycg

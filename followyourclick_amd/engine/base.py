@@ -162,14 +162,44 @@ class EngineBase:
                              eps=eps, silu=silu, **kw)
         return y
 
+    def _up_phases_group(self, w: Tensor, w_ph: Optional[Tensor], frames: int, Hin: int, Win: int, Ho: int, Wo: int, out_rows: int) -> int:
+        """input rows per group G of the four-phase form of an upsampling convolution (fyc_conv_up_phases: K = 4 Cin instead of 9 Cin), or 0 where
+        today's FYC_GEMM_CONV3X3_UP2 launch runs: no phase weights, a size that is not exactly 2x (`up_size` of an odd level), f32, an ops
+        object without the op (the CPU emulator and the recording backend of the tests, an A/B library), FYC_UP_PHASES=0, or a group the kernel's
+        row tiles do not divide (per-frame norms at 8x8).  `out_rows`: output rows per sample of the consuming GroupNorm - a clip's or a frame's;
+        a group is that sample's input rows, so that the epilogue's partial sums fold to it."""
+        supported = getattr(self.ops, "conv_up_phases_supported", None)
+        if (w_ph is None or supported is None or os.environ.get("FYC_UP_PHASES", "1") == "0" or self.dtype not in (torch.bfloat16, torch.float16)
+                or (Ho, Wo) != (2 * Hin, 2 * Win)):
+            return 0
+        G = out_rows // 4 if out_rows else Hin * Win
+        if G <= 0 or G % (Hin * Win) or (frames * Hin * Win) % G:
+            return 0
+        Cout, K = w.shape
+        return G if supported(self.dtype, Cin=K // 9, Cout=Cout, Hin=Hin, Win=Win, group_rows=G, exact2=True) else 0
+
     def conv_stats(self, x: Tensor, w: Tensor, b: Tensor, frames: int, Hin: int, Win: int, nxt=None, per_frame: bool = False,
-                   stride: int = 1, pad: int = 1, up2: bool = False, up_size=None, **kw) -> Tuple[Tensor, Optional[ChanStats]]:
+                   stride: int = 1, pad: int = 1, up2: bool = False, up_size=None, w_ph: Optional[Tensor] = None, **kw) -> Tuple[Tensor, Optional[ChanStats]]:
         """a 3x3 convolution whose output feeds a GroupNorm -> (output, its ChanStats or None).  `nxt` = (rows per statistics
-        sample of the epilogue = one frame, rows per sample of the norm); per_frame: a per-frame norm, whatever size comes out"""
+        sample of the epilogue = one frame, rows per sample of the norm); per_frame: a per-frame norm, whatever size comes out.
+        `w_ph` (up2): the phase weights beside `w` (engine/weights.py::pack_conv_up_phases) - where _up_phases_group allows, the four-phase
+        launch runs and its statistics are per (group, phase) over VIRTUAL rows: stat_rows = G, out_rows = 4 G, which fyc_chan_stats_reduce and
+        the consumers' own fold take as they are"""
         Cout, K = w.shape
         Ho, Wo = conv_out_size(Hin, Win, stride, pad, up2, up_size)
         if per_frame:
             nxt = (Ho * Wo, Ho * Wo)
+        G = self._up_phases_group(w, w_ph, frames, Hin, Win, Ho, Wo, nxt[1] if nxt is not None else 0) if up2 and not kw else 0
+        if G:
+            st = None
+            if nxt is not None and self.fuse_stats:
+                nt, tile_rows, slots = self.ops.conv_up_phases_stat_layout(self.dtype, frames=frames, Hin=Hin, Win=Win, Cin=K // 9, Cout=Cout, group_rows=G)
+                st = ChanStats(Cout, 4 * G, parts=self.new(nt * slots * Cout * 2, dtype=torch.float32), tile_rows=tile_rows, slots=slots,
+                               rows=frames * Ho * Wo, stat_rows=G)
+            out = self.new(frames * Ho * Wo, Cout)
+            self.ops.conv_up_phases(x, w_ph, out, frames=frames, Hin=Hin, Win=Win, Cin=K // 9, Cout=Cout, group_rows=G, bias=b,
+                                    chan_parts=None if st is None else st.parts)
+            return out, self._produced(st)
         st = None
         if nxt is not None:
             st = self._cs_plan(frames * Ho * Wo, nxt[0], Cout, K, L.GEMM_CONV3X3_UP2 if up2 else L.GEMM_CONV3X3, nxt[1])

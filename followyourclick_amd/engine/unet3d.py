@@ -595,7 +595,8 @@ class UNet3DEngine(EngineBase):
                 Hn, Wn = sizes[-1]
                 g2 = dict(g, H=Hn, W=Wn)
                 g2["rows"] = B * F * Hn * Wn
-                x = self._conv_act(x.t, blk.up.w, blk.up.b, frames, g["H"], g["W"], clip(g2), up2=True, up_size=(Hn, Wn))
+                # (clip(g2) also names the group of the four-phase form, EngineBase.conv_stats: the clip, or the frame with use_inflated_groupnorm)
+                x = self._conv_act(x.t, blk.up.w, blk.up.b, frames, g["H"], g["W"], clip(g2), up2=True, up_size=(Hn, Wn), w_ph=blk.up.get("w_ph"))
                 g = g2
         h, _ = self._gn(x, P.out_g, P.out_b, g["rows"], clip(g)[1], cfg.norm_eps, True)
         return self.conv(h, P.conv_out_w, P.conv_out_b, frames, g["H"], g["W"])

@@ -96,7 +96,7 @@ class VAEDecoderEngine(EngineBase):
             for r in blk.resnets:
                 x, cs = self.resnet(r, x, N, H, W, cs)
             if blk.up is not None:
-                x, cs = self.conv_cs(x, blk.up.w, blk.up.b, N, H, W, up2=True)
+                x, cs = self.conv_cs(x, blk.up.w, blk.up.b, N, H, W, up2=True, w_ph=blk.up.get("w_ph"))      # (per-frame norm: the group is the frame)
                 H, W = 2 * H, 2 * W
         c0 = cfg.block_out_channels[0]
         h = self.gn(x, cs, P.out_g, P.out_b, N * H * W, c0, H * W, True)

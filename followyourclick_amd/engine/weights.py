@@ -44,6 +44,39 @@ def pack_conv3x3(w: Tensor, dtype, device) -> Tensor:
     return p.reshape(O, 9 * Ip).to(dtype).contiguous().to(device)
 
 
+def up_phase_weights(w: Tensor) -> Tensor:
+    """OIHW 3x3 -> (4 phases, O, I, 2, 2) in the dtype of `w`: the 2x2 filters of nearest-2x upsampling + this 3x3 convolution, one per output phase
+    2 py + px.  Along y (columns alike): py = 0 reads input rows y - 1, y with W[0], W[1] + W[2]; py = 1 reads rows y, y + 1 with W[0] + W[1], W[2]."""
+    rows = ((w[:, :, 0], w[:, :, 1] + w[:, :, 2]), (w[:, :, 0] + w[:, :, 1], w[:, :, 2]))      # [py][ty] -> (O, I, 3)
+    out = []
+    for py in range(2):
+        for px in range(2):
+            taps = []
+            for ty in range(2):
+                r = rows[py][ty]
+                cols = ((r[..., 0], r[..., 1] + r[..., 2]), (r[..., 0] + r[..., 1], r[..., 2]))[px]
+                taps.append(torch.stack(cols, dim=-1))
+            out.append(torch.stack(taps, dim=-2))
+    return torch.stack(out, dim=0)
+
+
+def pack_conv_up_phases(w: Tensor, dtype, device) -> Tensor:
+    """OIHW 3x3 -> [4 phases][O][slab][tap = 2 ty + tx][c in slab] = (4, O, 4 * I_pad): the weights of fyc_conv_up_phases (K order of the
+    conv3x3 gather with four taps).  The 3x3 master weights are summed in f32 and rounded ONCE to the storage type."""
+    O, I, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    Ip, sl = pad_channels(I), conv_slab(dtype)
+    p = torch.zeros(4, O, Ip, 2, 2, dtype=torch.float32)
+    p[:, :, :I] = up_phase_weights(w.detach().float())
+    p = p.reshape(4, O, Ip // sl, sl, 2, 2).permute(0, 1, 2, 4, 5, 3)
+    return p.reshape(4, O, 4 * Ip).to(dtype).contiguous().to(device)
+
+
+def _up_phases(w: Tensor, dtype, device) -> Optional[Tensor]:
+    """the phase weights an upsampler keeps beside its 3x3 ones (`up.w_ph`): 16-bit tiers only, f32 stays on the 3x3 path"""
+    return pack_conv_up_phases(w, dtype, device) if dtype in (torch.bfloat16, torch.float16) else None
+
+
 def pack_conv_t3(w: Tensor, dtype, device) -> Tensor:
     """Conv3d (O, I, 3, 1, 1) -> [O][slab][tap][c in slab]: K order of FYC_GEMM_CONV_T3 (the 3 frame taps of a slab are adjacent K tiles)"""
     O, I, kt, kh, kw = w.shape
@@ -462,7 +495,8 @@ def pack_unet(sd: Dict[str, Tensor], cfg: UNet3DConfig, dtype, device) -> Packed
                 if cfg.use_motion_module and (2 ** (nb - 1 - i)) in cfg.motion_module_resolutions else None))
         us = None
         if i != nb - 1:
-            us = Packed(w=pack_conv3x3(sd[f"{p}.upsamplers.0.conv.weight"], dtype, device), b=f32(sd[f"{p}.upsamplers.0.conv.bias"], device))
+            us = Packed(w=pack_conv3x3(sd[f"{p}.upsamplers.0.conv.weight"], dtype, device), b=f32(sd[f"{p}.upsamplers.0.conv.bias"], device),
+                        w_ph=_up_phases(sd[f"{p}.upsamplers.0.conv.weight"], dtype, device))
         up.append(Packed(layers=layers, up=us))
     P["up"] = up
     P["out_g"], P["out_b"] = f32(sd["conv_norm_out.weight"], device), f32(sd["conv_norm_out.bias"], device)
@@ -498,7 +532,7 @@ def pack_vae_decoder(sd: Dict[str, Tensor], cfg: VAEDecoderConfig, dtype, device
         us = None
         if i != nb - 1:
             k = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-            us = Packed(w=pack_conv3x3(sd[k + ".weight"], dtype, device), b=f32(sd[k + ".bias"], device))
+            us = Packed(w=pack_conv3x3(sd[k + ".weight"], dtype, device), b=f32(sd[k + ".bias"], device), w_ph=_up_phases(sd[k + ".weight"], dtype, device))
         ups.append(Packed(resnets=rs, up=us))
     P["ups"] = ups
     P["out_g"], P["out_b"] = f32(sd["decoder.conv_norm_out.weight"], device), f32(sd["decoder.conv_norm_out.bias"], device)

@@ -219,6 +219,49 @@ class HipOps:
         a.out_rows = out_rows
         self._call("fyc_chan_stats_reduce", a)
 
+    # -- nearest-2x upsample + 3x3 convolution as four 2x2 phase convolutions (include/fyc.h, fyc_conv_up_phases) ---------------
+    def conv_up_phases_supported(self, dtype: torch.dtype, *, Cin: int, Cout: int, Hin: int, Win: int, group_rows: int, exact2: bool = True) -> bool:
+        """does fyc_conv_up_phases cover this shape?  (no launch; an A/B library of an earlier build, FYC_LIB_PATH, has no such entry: False)"""
+        if not hasattr(self.lib, "fyc_conv_up_phases_supported") or dtype not in (torch.bfloat16, torch.float16):
+            return False
+        key = ("cups", dtype, Cin, Cout, Hin, Win, group_rows, bool(exact2))
+        if key not in self._q_cache:
+            self._q_cache[key] = bool(self.lib.fyc_conv_up_phases_supported(_dtc(dtype), Cin, Cout, Hin, Win, group_rows, int(bool(exact2))))
+        return self._q_cache[key]
+
+    @staticmethod
+    def _conv_up_phases_args(dtype_code: int, frames: int, Hin: int, Win: int, Cin: int, Cout: int, ldw: int, ldo: int, group_rows: int):
+        u = L.ConvUpPhasesArgs()
+        g = u.gemm
+        g.M, g.N, g.K, g.lda, g.ldw, g.ldo = 4 * frames * Hin * Win, Cout, 4 * Cin, Cin, ldw, ldo
+        g.mode, g.epilogue, g.batch, g.out_scale, g.dtype = L.GEMM_CONV3X3_UP2, L.EPI_LINEAR, 1, 1.0, dtype_code
+        g.Hout, g.Wout, g.Hin, g.Win, g.Cin, g.conv_stride, g.conv_pad = 2 * Hin, 2 * Win, Hin, Win, Cin, 1, 1
+        u.group_rows = group_rows
+        return u
+
+    def conv_up_phases_stat_layout(self, dtype: torch.dtype, *, frames: int, Hin: int, Win: int, Cin: int, Cout: int, group_rows: int):
+        """(row tiles, rows per tile, slots = 1) of the `chan_parts` output of conv_up_phases over its virtual rows (fyc_conv_up_phases_stat_layout)"""
+        key = ("cupl", dtype, frames, Hin, Win, Cin, Cout, group_rows)
+        if key not in self._q_cache:
+            u = self._conv_up_phases_args(_dtc(dtype), frames, Hin, Win, Cin, Cout, 4 * Cin, Cout, group_rows)
+            tr, sl = L.i32(0), L.i32(0)
+            n = int(self.lib.fyc_conv_up_phases_stat_layout(C.byref(u), C.byref(tr), C.byref(sl)))
+            self._q_cache[key] = (n, int(tr.value), int(sl.value))
+        return self._q_cache[key]
+
+    def conv_up_phases(self, x: Tensor, w_ph: Tensor, out: Tensor, *, frames: int, Hin: int, Win: int, Cin: int, Cout: int, group_rows: int,
+                       bias: Optional[Tensor] = None, ldo: int = 0, chan_parts: Optional[Tensor] = None) -> None:
+        """out [frames * 2 Hin * 2 Win][ldo] = conv3x3(nearest-2x(x)) + bias from the phase weights w_ph [4][Cout][4 * Cin]
+        (engine/weights.py::pack_conv_up_phases); chan_parts: per (group of group_rows input rows, phase) partial sums"""
+        self.ensure_init(x.device)
+        if x.dtype != w_ph.dtype:
+            raise TypeError(f"conv_up_phases: activation {x.dtype} vs weight {w_ph.dtype}")
+        u = self._conv_up_phases_args(_dt(x), frames, Hin, Win, Cin, Cout, w_ph.shape[-1], ldo or Cout, group_rows)
+        g = u.gemm
+        g.a, g.w, g.bias, g.out = _p(x), _p(w_ph), _f32(bias, "bias"), _p(out)
+        g.chan_parts, g.cs_rows = _f32(chan_parts, "chan_parts"), (group_rows if chan_parts is not None else 0)
+        self._call("fyc_conv_up_phases", u)
+
     @staticmethod
     def _gemm_args(a, w, out, *, M, N, K, lda, ldw, ldo, bias, rowbias, rows_per_batch, residual, ldr, ldrb, out_scale, epilogue, mode,
                    conv, batch, stride_a, stride_w, stride_o, heads, tile, a2, k_split, lda2, act, ln_stats, ln_colsum, ln_nparts,

@@ -64,6 +64,22 @@ class TimedOps:
         key = f"{fam} M={M} N={N} K={K} b={batch} epi={kw.get('epilogue', 0)} res={int(kw.get('residual') is not None)}"
         return self._timed(fam, flops, nbytes, self.inner.gemm, a, w, out, _key=key, **kw)
 
+    def conv_up_phases_supported(self, dtype, **kw):      # host-side queries, no kernel (an inner backend without the op: not supported)
+        fn = getattr(self.inner, "conv_up_phases_supported", None)
+        return bool(fn and fn(dtype, **kw))
+
+    def conv_up_phases_stat_layout(self, dtype, **kw):
+        return self.inner.conv_up_phases_stat_layout(dtype, **kw)
+
+    def conv_up_phases(self, x, w_ph, out, **kw):
+        """filed under conv3x3 with the FLOPs it EXECUTES (K = 4 Cin, not the 9 Cin of the convolution it stands for): skipped work must not
+        raise roofline.frac"""
+        M, N, K = 4 * kw["frames"] * kw["Hin"] * kw["Win"], kw["Cout"], 4 * kw["Cin"]
+        es = _esize(x)
+        nbytes = (M // 4 * kw["Cin"] + 4 * N * K + M * N) * es
+        key = f"conv3x3 up_phases M={M} N={N} K={K} b=1 epi=0 res=0"
+        return self._timed("conv3x3", 2.0 * M * N * K, nbytes, self.inner.conv_up_phases, x, w_ph, out, _key=key, **kw)
+
     def attention(self, q, k, vt, o, **kw):
         B, H, nq, nk, d = kw["batch"], kw["heads"], kw["n_q"], kw["n_k"], kw["d"]
         flops = 4.0 * B * H * nq * nk * d

@@ -155,6 +155,29 @@ int fyc_gemm_row_parts(const fyc_gemm_args* a);
  * *slots = sample slots per tile; chan_parts holds row_tiles * slots * N * 2 floats */
 int fyc_gemm_stat_layout(const fyc_gemm_args* a, int32_t* tile_rows, int32_t* slots);
 
+/* (308, added entry points) FYC_GEMM_CONV3X3_UP2 with an output of exactly twice the input, computed as four 2x2 convolutions of the low-resolution
+ * input - one per output phase (py, px) = parity of the output pixel - with weights pre-summed from the 3x3 filter: K = 4*Cin instead of 9*Cin, the same
+ * result up to the summation order and the one rounding of the pre-summed weights.  No struct changed and no number bumped.
+ *   For output pixel (2y+py, 2x+px) the filter rows collapse onto two input rows: py = 0 reads row y-1 with W[ky=0] and row y with W[1]+W[2]; py = 1 reads
+ *   row y with W[0]+W[1] and row y+1 with W[2]; columns alike with px.  Zero padding maps onto itself (upsampled row -1 is input row -1, 2*Hin is Hin).
+ * fyc_conv_up_phases_args = { fyc_gemm_args gemm; int32_t group_rows; }: fyc_gemm_args keeps its layout.  `gemm` describes the CONV3X3_UP2 problem it
+ * replaces (mode FYC_GEMM_CONV3X3_UP2, a = [frames][Hin][Win][Cin], out [M = frames*Hout*Wout][ldo], N, bias, Hout = 2*Hin, Wout = 2*Win, dtype FYC_BF16 /
+ * FYC_F16, Cin a multiple of 64) except for the weights: w = [4 phases = 2*py+px][N][ldw], K = 4*Cin ordered (128-byte channel slab, tap = 2*ty+tx, channel
+ * in slab) where tap (ty, tx) multiplies input pixel (y-1+py+ty, x-1+px+tx); engine/weights.py::pack_conv_up_phases sums the f32 master weights and rounds
+ * once.  group_rows = G: input rows (whole frames) per statistics sample of the consuming GroupNorm - a clip's F*Hin*Win or a frame's Hin*Win - a
+ * multiple of the row tile (128; M/4 a multiple of G).  The kernel walks VIRTUAL rows [group][phase][row in group] so that a row tile has one phase and one group.
+ * chan_parts (optional, cs_rows == group_rows): [row tiles][1 slot][N][2] over the virtual rows, i.e. virtual sample 4*group+phase has G rows; folded with
+ * fyc_chan_stats_reduce using rows = M, cs_rows = G, out_rows = 4*G and the tile_rows the layout query below answers, it yields the sums of every 4*G stored
+ * output rows - the group's frames.  Refused before anything is launched: FYC_F32, residual, rowbias, a2, a folded LayerNorm, row_parts, an activation,
+ * batch > 1, a size that is not exactly 2x, Cin % 64, N % 8, Win > 4096, G not a whole number of frames or of row tiles, operands the 16-byte epilogue
+ * cannot take.  Such problems keep fyc_gemm with FYC_GEMM_CONV3X3_UP2.
+ * The layout query returns the number of row tiles (0 = not covered), *tile_rows = rows per tile, *slots = 1; the _supported query (dtype, Cin, Cout = N,
+ * Hin, Win, group_rows, exact2 = the output is exactly 2x) returns 1 where a call with aligned operands would run.  Neither launches anything. */
+typedef struct { fyc_gemm_args gemm; int32_t group_rows; } fyc_conv_up_phases_args;
+int fyc_conv_up_phases(const fyc_conv_up_phases_args* a, void* stream);
+int fyc_conv_up_phases_stat_layout(const fyc_conv_up_phases_args* a, int32_t* tile_rows, int32_t* slots);
+int fyc_conv_up_phases_supported(int32_t dtype, int32_t Cin, int32_t Cout, int32_t Hin, int32_t Win, int32_t group_rows, int32_t exact2);
+
 /* cs[o][n] = {sum, sum of squares} over the rows of output sample o (out_rows rows each, a multiple of cs_rows; 0 = cs_rows) of
  * channel n, in f64, from the row-tile partials a fyc_gemm epilogue wrote with cs_rows rows per statistics sample (chan_parts;
  * tile_rows / slots from fyc_gemm_stat_layout).  out_rows = H*W for a per-frame GroupNorm, F*H*W for a cross-frame one.
