@@ -82,6 +82,42 @@ __global__ void __launch_bounds__(256) unet_input_kernel(const float* __restrict
   }
 }
 
+// fyc_unet_input_scaled: unet_input_kernel with every stored value divided by `denom` (a sigma-space scheduler's scale_model_input,
+// sqrt(sigma^2 + 1)): a true f32 division, as the reference divides, rounded once more to the storage type.  scale_cond: the mask channel
+// and the first-frame block of mode 0 are divided as well (the reference scales the concatenated tensor); mode 1 divides the latents only.
+template <typename T>
+__global__ void __launch_bounds__(256) unet_input_scaled_kernel(const float* __restrict__ lat, const float* __restrict__ mask,
+                                                                const float* __restrict__ first, T* __restrict__ x, int B, int F,
+                                                                int HW, int CL, int c_pad, int cfg_dup, int mask_frames, int mode,
+                                                                float denom, int scale_cond) {
+  const long long total = (long long)cfg_dup * B * F * HW;
+  const float cden = scale_cond ? denom : 1.f;                // (v / 1.f is v: the unscaled channels keep their bits)
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const long long bf = i / HW;
+    const int f = (int)(bf % F);
+    const int b = (int)((bf / F) % B);  // CFG duplicates share the same latents
+    T* o = x + i * c_pad;
+    for (int c = 0; c < CL; ++c) ElemIO<T>::st(o + c, lat[(((long long)b * CL + c) * F + f) * HW + p] / denom);
+    if (mode == 1) {
+      for (int c = 0; c < CL; ++c) ElemIO<T>::st(o + CL + c, first ? first[((long long)b * CL + c) * HW + p] : 0.f);
+      for (int c = 2 * CL; c < c_pad; ++c) ElemIO<T>::st(o + c, 0.f);
+      continue;
+    }
+    float m;
+    if (mask) {
+      const int mf = mask_frames > 1 ? f : 0;
+      m = fminf(fmaxf(mask[((long long)b * mask_frames + mf) * HW + p], 0.f), 1.f);
+    } else {
+      m = (f == 0) ? 1.f : 0.f;
+    }
+    ElemIO<T>::st(o + CL, m / cden);
+    for (int c = 0; c < CL; ++c)
+      ElemIO<T>::st(o + CL + 1 + c, (f == 0 && first) ? first[((long long)b * CL + c) * HW + p] / cden : 0.f);
+    for (int c = 2 * CL + 1; c < c_pad; ++c) ElemIO<T>::st(o + c, 0.f);
+  }
+}
+
 // the guided prediction of one element from the unconditional, conditional and (optional) per-frame unconditional one: the one f32
 // expression of the step kernels and of the moments pass of the guidance rescale
 __device__ __forceinline__ float cfg_guided(float u, float cnd, bool has_single, float s1, float video_scale, float guidance) {
@@ -184,6 +220,46 @@ __global__ void __launch_bounds__(256) cfg_solver_kernel(const T* __restrict__ p
       if (ORDER >= 3) nx += c2 * hist_2[j];
       lat[j] = nx;
       hist_out[j] = m0;
+    }
+  }
+}
+
+// Guidance + one step of a sigma-space (k-diffusion) sampler: Euler, Euler ancestral, LMS (fyc_cfg_sigma_step).  coef = {a_x, a_v, c_x, c_0,
+// c_1, c_2, c_3, c_n} gives the derivative d = a_x x + a_v v and x' = c_x x + c_0 d + c_1 d1 + c_2 d2 + c_3 d3 + c_n noise, summed left to
+// right.  ORDER is a template parameter as in cfg_solver_kernel: a history the order does not use is never loaded.  hist_out and noise are
+// NULL for the variants without them (one uniform branch each): nothing is stored, nothing is loaded.
+template <typename T, int ORDER, bool RESCALE>
+__global__ void __launch_bounds__(256) cfg_sigma_kernel(const T* __restrict__ pred, float* __restrict__ lat,
+                                                        const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
+                                                        int cfg, float guidance, const T* __restrict__ single, float video_scale,
+                                                        float* __restrict__ hist_out, const float* __restrict__ hist_1,
+                                                        const float* __restrict__ hist_2, const float* __restrict__ hist_3,
+                                                        const float* __restrict__ noise, const float* __restrict__ factor) {
+  const float ax = coef[0], av = coef[1], cx = coef[2], c0 = coef[3], c1 = coef[4], c2 = coef[5], c3 = coef[6], cn = coef[7];
+  const long long total = (long long)B * F * HW;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const long long bf = i / HW;
+    const int f = (int)(bf % F), b = (int)(bf / F);
+    const T* pu = pred + i * ld;                                   // uncond (or the only) half
+    const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
+    for (int c = 0; c < CL; ++c) {
+      float v = ElemIO<T>::ld(pu + c);
+      if (cfg) {
+        const float u = v, cnd = ElemIO<T>::ld(pc + c);
+        v = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
+        if (RESCALE) v *= factor[b];
+      }
+      const long long j = (((long long)b * CL + c) * F + f) * HW + p;
+      const float x = lat[j];
+      const float d = ax * x + av * v;
+      float nx = cx * x + c0 * d;
+      if (ORDER >= 2) nx += c1 * hist_1[j];
+      if (ORDER >= 3) nx += c2 * hist_2[j];
+      if (ORDER >= 4) nx += c3 * hist_3[j];
+      if (noise) nx += cn * noise[j];
+      lat[j] = nx;
+      if (hist_out) hist_out[j] = d;
     }
   }
 }
@@ -449,6 +525,28 @@ extern "C" int fyc_unet_input(const fyc_unet_input_args* a, void* stream) {
   return 0;
 }
 
+extern "C" int fyc_unet_input_scaled(const fyc_unet_input_scaled_args* s, void* stream) {
+  FYC_REQUIRE(s, "fyc_unet_input_scaled: null pointer");
+  const fyc_unet_input_args* a = &s->base;
+  FYC_REQUIRE(a->latents && a->x, "fyc_unet_input_scaled: null pointer");
+  FYC_REQUIRE(a->mode == 0 || a->mode == 1, "fyc_unet_input_scaled: mode %d", a->mode);
+  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->c_pad >= 2 * a->c_latent + (a->mode == 1 ? 0 : 1), "fyc_unet_input_scaled: bad dims");
+  FYC_REQUIRE(a->cfg_dup == 1 || a->cfg_dup == 2, "fyc_unet_input_scaled: cfg_dup must be 1 or 2");
+  FYC_REQUIRE(a->mask == nullptr || a->mask_frames == 1 || a->mask_frames == a->F, "fyc_unet_input_scaled: mask_frames must be 1 or F");
+  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_unet_input_scaled: bad dtype %d", a->dtype);
+  FYC_REQUIRE(s->denom >= 1.f && s->denom <= 3.0e38f, "fyc_unet_input_scaled: denom %g must be finite and at least 1 (sqrt(sigma^2 + 1))", (double)s->denom);
+  FYC_REQUIRE(s->scale_cond == 0 || s->scale_cond == 1, "fyc_unet_input_scaled: scale_cond %d", s->scale_cond);
+  FYC_REQUIRE(a->mode == 0 || s->scale_cond == 0, "fyc_unet_input_scaled: scale_cond must be 0 in mode 1 (the UNet concatenates the clean first-frame latents behind the scaling)");
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = (long long)a->cfg_dup * a->B * a->F * a->HW;
+  const int mf = a->mask ? a->mask_frames : 1;
+  if (a->dtype == FYC_BF16) hipLaunchKernelGGL(unet_input_scaled_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, a->latents, a->mask, a->first, (bf16_t*)a->x, a->B, a->F, a->HW, a->c_latent, a->c_pad, a->cfg_dup, mf, a->mode, s->denom, s->scale_cond);
+  else if (a->dtype == FYC_F16) hipLaunchKernelGGL(unet_input_scaled_kernel<f16_t>, dim3(grid_for(n)), dim3(256), 0, st, a->latents, a->mask, a->first, (f16_t*)a->x, a->B, a->F, a->HW, a->c_latent, a->c_pad, a->cfg_dup, mf, a->mode, s->denom, s->scale_cond);
+  else hipLaunchKernelGGL(unet_input_scaled_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, a->latents, a->mask, a->first, (float*)a->x, a->B, a->F, a->HW, a->c_latent, a->c_pad, a->cfg_dup, mf, a->mode, s->denom, s->scale_cond);
+  FYC_CHECK_LAUNCH("fyc_unet_input_scaled");
+  return 0;
+}
+
 // the argument checks of the DDIM step, shared by its two entry points
 static int cfg_ddim_check(const fyc_cfg_ddim_args* a) {
   FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_ddim_step: null pointer");
@@ -612,6 +710,87 @@ extern "C" int fyc_cfg_solver_step(const fyc_cfg_solver_args* a, void* stream) {
   else if (a->dtype == FYC_F16) cfg_solver_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
   else cfg_solver_dispatch<float>(a, rescale ? &pl : nullptr, st);
   FYC_CHECK_LAUNCH("fyc_cfg_solver_step");
+  return 0;
+}
+
+// ---- sigma-space samplers (Euler, Euler ancestral, LMS): guidance (+ rescale) + derivative + update -------------------------------
+static fyc_cfg_ddim_args cfg_sigma_guidance(const fyc_cfg_sigma_args* a) {
+  fyc_cfg_ddim_args s = {};
+  s.pred = a->pred; s.latents = a->latents; s.coef = a->coef;
+  s.B = a->B; s.F = a->F; s.HW = a->HW; s.c_latent = a->c_latent; s.ld = a->ld; s.cfg = a->cfg; s.guidance = a->guidance;
+  s.dtype = a->dtype; s.pred_single = a->pred_single; s.video_scale = a->video_scale;
+  return s;
+}
+
+extern "C" int64_t fyc_cfg_sigma_workspace_bytes(const fyc_cfg_sigma_args* a) {
+  CfgRescalePlan pl;
+  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->cfg) return 0;
+  const fyc_cfg_ddim_args s = cfg_sigma_guidance(a);
+  return cfg_rescale_plan(&s, pl) ? pl.bytes : 0;
+}
+
+template <typename T, bool RESCALE>
+static void cfg_sigma_launch(const fyc_cfg_sigma_args* a, const float* factor, hipStream_t st) {
+  const long long n = (long long)a->B * a->F * a->HW;
+  const dim3 grid(grid_for(n));
+  const T* pred = (const T*)a->pred;
+  const T* single = (const T*)a->pred_single;
+#define FYC_SIGMA_LAUNCH(ORDER)                                                                                                      \
+  hipLaunchKernelGGL((cfg_sigma_kernel<T, ORDER, RESCALE>), grid, dim3(256), 0, st, pred, a->latents, a->coef, a->B, a->F, a->HW,    \
+                     a->c_latent, a->ld, a->cfg, a->guidance, single, a->video_scale, a->hist_out, a->hist_1, a->hist_2, a->hist_3,  \
+                     a->noise, factor)
+  if (a->order == 1) FYC_SIGMA_LAUNCH(1);
+  else if (a->order == 2) FYC_SIGMA_LAUNCH(2);
+  else if (a->order == 3) FYC_SIGMA_LAUNCH(3);
+  else FYC_SIGMA_LAUNCH(4);
+#undef FYC_SIGMA_LAUNCH
+}
+
+template <typename T>
+static void cfg_sigma_dispatch(const fyc_cfg_sigma_args* a, const CfgRescalePlan* pl, hipStream_t st) {
+  if (pl == nullptr) return cfg_sigma_launch<T, false>(a, nullptr, st);
+  const fyc_cfg_ddim_args s = cfg_sigma_guidance(a);
+  cfg_sigma_launch<T, true>(a, cfg_rescale_factors<T>(&s, a->workspace, a->guidance_rescale, *pl, st), st);
+}
+
+extern "C" int fyc_cfg_sigma_step(const fyc_cfg_sigma_args* a, void* stream) {
+  FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_sigma_step: null pointer");
+  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_sigma_step: bad dims");
+  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_cfg_sigma_step: bad dtype %d", a->dtype);
+  FYC_REQUIRE(a->order >= 1 && a->order <= 4, "fyc_cfg_sigma_step: order %d (1 .. 4)", a->order);
+  FYC_REQUIRE(a->order < 2 || a->hist_1 != nullptr, "fyc_cfg_sigma_step: order %d needs hist_1", a->order);
+  FYC_REQUIRE(a->order < 3 || a->hist_2 != nullptr, "fyc_cfg_sigma_step: order %d needs hist_2", a->order);
+  FYC_REQUIRE(a->order < 4 || a->hist_3 != nullptr, "fyc_cfg_sigma_step: order 4 needs hist_3");
+  // hist_out and the latents are written while other threads still read the latents, the histories and the noise: any overlap of the
+  // [n] f32 ranges is refused, not only equal bases
+  const int64_t n = (int64_t)a->B * a->c_latent * a->F * a->HW;
+  auto overlaps = [n](const float* p, const float* q) { return p != nullptr && q != nullptr && p < q + n && q < p + n; };
+  FYC_REQUIRE(!overlaps(a->hist_out, a->latents), "fyc_cfg_sigma_step: hist_out aliases latents");
+  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_1), "fyc_cfg_sigma_step: hist_out aliases hist_1");
+  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_2), "fyc_cfg_sigma_step: hist_out aliases hist_2");
+  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_3), "fyc_cfg_sigma_step: hist_out aliases hist_3");
+  FYC_REQUIRE(!overlaps(a->noise, a->hist_out), "fyc_cfg_sigma_step: noise aliases hist_out");
+  FYC_REQUIRE(!overlaps(a->noise, a->latents), "fyc_cfg_sigma_step: noise aliases latents");
+  FYC_REQUIRE(!overlaps(a->noise, a->hist_1), "fyc_cfg_sigma_step: noise aliases hist_1");
+  FYC_REQUIRE(!overlaps(a->noise, a->hist_2), "fyc_cfg_sigma_step: noise aliases hist_2");
+  FYC_REQUIRE(!overlaps(a->noise, a->hist_3), "fyc_cfg_sigma_step: noise aliases hist_3");
+  FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_sigma_step: pred_single needs classifier-free guidance (cfg = 1)");
+  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_sigma_step: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
+  hipStream_t st = (hipStream_t)stream;
+  CfgRescalePlan pl;
+  const bool rescale = a->guidance_rescale > 0.f;
+  if (rescale) {
+    FYC_REQUIRE(a->cfg, "fyc_cfg_sigma_step: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
+    const fyc_cfg_ddim_args s = cfg_sigma_guidance(a);
+    FYC_REQUIRE(cfg_rescale_plan(&s, pl), "fyc_cfg_sigma_step: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)a->F * a->HW * a->c_latent);
+    FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_sigma_step: workspace is null or not 8-byte aligned");
+    FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_sigma_step: workspace_bytes %lld < %lld (fyc_cfg_sigma_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
+  }
+  FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_sigma_step: fyc_init() not called");
+  if (a->dtype == FYC_BF16) cfg_sigma_dispatch<bf16_t>(a, rescale ? &pl : nullptr, st);
+  else if (a->dtype == FYC_F16) cfg_sigma_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
+  else cfg_sigma_dispatch<float>(a, rescale ? &pl : nullptr, st);
+  FYC_CHECK_LAUNCH("fyc_cfg_sigma_step");
   return 0;
 }
 

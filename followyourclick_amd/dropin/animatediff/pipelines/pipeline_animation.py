@@ -250,7 +250,7 @@ class AnimationPipeline:
         # the reference's); the reference's scripts cannot pass it, for them the FYC_GUIDANCE_RESCALE environment switch (unset = 0 = off)
         guidance_rescale = resolve_guidance_rescale(kwargs.get("guidance_rescale"))
         engine = self.unet._get_engine()
-        sampler = make_sampler(engine, self.scheduler.engine_config)      # by the scheduler's engine_config type: DDIM or the multistep solver
+        sampler = make_sampler(engine, self.scheduler.engine_config)      # by the scheduler's engine_config type: DDIM, the multistep solver or a sigma-space sampler
         bar = self.progress_bar(total=num_inference_steps)
 
         def cb(i, t, lat):

@@ -151,3 +151,19 @@ class SolverConfig:
     solver_type: str = "midpoint"
     lower_order_final: bool = True
     rescale_betas_zero_snr: bool = False
+
+
+@dataclass
+class SigmaConfig:
+    """EulerDiscreteScheduler / EulerAncestralDiscreteScheduler / LMSDiscreteScheduler.__init__ kwargs (reference diffusers/schedulers/
+    scheduling_euler_discrete.py:79-87, the other two alike) with the reference's defaults, plus `kind` (which of the three) and
+    rescale_betas_zero_snr (an engine extension as in SolverConfig: the tables use the rescaled betas and set alphas_cumprod[-1] = 2^-24, the
+    convention later diffusers adopted for its sigma-space schedulers, so that sigma_max stays finite)."""
+    kind: str = "euler"                 # "euler" | "euler_ancestral" | "lms"
+    num_train_timesteps: int = 1000
+    beta_start: float = 0.0001
+    beta_end: float = 0.02
+    beta_schedule: str = "linear"
+    trained_betas: object = None
+    prediction_type: str = "epsilon"
+    rescale_betas_zero_snr: bool = False

@@ -8,6 +8,7 @@ of 3 zeros_like + 2 cat), UNet forward on the CFG pair, guidance + DDIM update (
 sync).  Everything that is constant over the loop (text/IP K/V, all time embeddings, DDIM
 coefficients) is prepared once per clip.  SolverSampler is the same loop for a DPM-Solver multistep scheduler
 (the reference's loop is scheduler-agnostic): it shares the input build and the forward and differs in the schedule and the update kernel.
+SigmaSampler is the loop for the sigma-space schedulers (Euler, Euler ancestral, LMS): the input build also divides by sqrt(sigma^2 + 1).
 """
 from __future__ import annotations
 
@@ -16,8 +17,8 @@ from typing import Callable, Optional, Sequence
 
 import torch
 
-from .config import DDIMConfig, SolverConfig
-from .scheduler import DDIMTables, SolverTables
+from .config import DDIMConfig, SigmaConfig, SolverConfig
+from .scheduler import DDIMTables, SigmaTables, SolverTables
 from .unet3d import UNet3DEngine
 from .weights import pad_channels
 
@@ -114,9 +115,11 @@ class DDIMSampler:
                     guidance_rescale=guidance_rescale, **extra)
 
     @torch.no_grad()
-    def predict(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor]):
+    def predict(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
+                input_denom: Optional[float] = None):
         """the part of a step every scheduler shares: pin frame 0 (first_frame_condition), build the UNet input, run the forward(s)
-        -> (pred [cfg B F HW][ld], the per-frame unconditional prediction or None)"""
+        -> (pred [cfg B F HW][ld], the per-frame unconditional prediction or None).  input_denom (a sigma-space scheduler's scale_model_input,
+        sqrt(sigma^2 + 1)): the tensor handed to the UNet is divided by it (ops.unet_input_scaled); None: the launches of an alpha-space scheduler"""
         u, o = self.unet, self.unet.ops
         B, CL, F, H, W = latents.shape
         cp = pad_channels(u.cfg.conv_in_channels)
@@ -133,16 +136,27 @@ class DDIMSampler:
         if u.cfg.use_first_frame_condition_concat:
             # the reference's UNet concatenates `reference_images_latent` (the clean first-frame latents) beside EVERY frame's latents
             # (unet.py:580-586; pipeline_animation.py:705-706 passes the plain latents); conv_in's `/ 2` lives in its packed weights
-            o.unet_input(latents, None, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx, mode=1)
+            # (a sigma-space scheduler scales the pipeline's tensor, the plain latents: the clean first-frame latents stay undivided)
+            if input_denom is None:
+                o.unet_input(latents, None, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx, mode=1)
+            else:
+                o.unet_input_scaled(latents, None, first_image_latents, x, denom=input_denom, scale_cond=False, B=B, F=F, HW=H * W,
+                                    c_latent=CL, c_pad=cp, cfg_dup=dupx, mode=1)
         elif u.cfg.use_first_frame_mask_condition_concat:
-            o.unet_input(latents, mask, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx,
-                         mask_frames=1)
+            if input_denom is None:
+                o.unet_input(latents, mask, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx,
+                             mask_frames=1)
+            else:       # the reference scales the concatenated tensor (pipeline_animation.py:708-712): mask and first-frame block too
+                o.unet_input_scaled(latents, mask, first_image_latents, x, denom=input_denom, scale_cond=True, B=B, F=F, HW=H * W,
+                                    c_latent=CL, c_pad=cp, cfg_dup=dupx, mask_frames=1)
         else:
             # plain latents (the 2-D Stable Diffusion first-image path, reference pipeline_stable_diffusion.py:527-528)
             n = B * F * H * W
             frames = latents.permute(0, 2, 1, 3, 4).reshape(B * F, CL, H * W).contiguous()
+            # (sigma-space: times the f32 reciprocal - one rounding more than the reference's division)
+            scale = 1.0 if input_denom is None else float(torch.tensor(1.0) / torch.tensor(input_denom, dtype=torch.float32))
             for d in range(dupx):
-                o.nchw_to_nhwc(frames, x[d * n:(d + 1) * n], N=B * F, C_=CL, HW=H * W, c_pad=cp, scale=1.0)
+                o.nchw_to_nhwc(frames, x[d * n:(d + 1) * n], N=B * F, C_=CL, HW=H * W, c_pad=cp, scale=scale)
         if share:
             pred = u.forward(x, st["temb"][i], dupn * B, F, H, W, shared_prefix=2)
         else:
@@ -280,10 +294,65 @@ class SolverSampler(DDIMSampler):
                               use_clipped_model_output=False, **kwargs)
 
 
+class SigmaSampler(DDIMSampler):
+    """The same loop with a sigma-space scheduler: Euler, Euler ancestral or LMS (engine/scheduler.py::SigmaTables).  `prepare` is shared; the
+    schedule has fractional timesteps, per-step input denominators sqrt(sigma^2 + 1) handed to `predict`, and the table of collapsed
+    coefficients; the update is ops.cfg_sigma_step.  LMS owns four latent-shaped f32 history buffers (the derivative of this step and of the
+    three before) and rotates their roles per step; the Euler kinds store none.  The ancestral kind draws one noise tensor per step from the
+    caller's generator, as the eta > 0 DDIM path does.  Nothing is replayed from a captured graph; eta and use_clipped_model_output are
+    accepted and unused, as the reference's prepare_extra_step_kwargs drops them for these schedulers; there is no clip_sample.  The latents
+    handed to `sample` are in sigma space: the caller has multiplied the initial noise by tables.init_noise_sigma."""
+
+    def __init__(self, unet: UNet3DEngine, sigma: SigmaConfig):
+        self.unet = unet
+        self.tables = SigmaTables(sigma)
+        self.clip_sample = False
+        self.kind = sigma.kind
+
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
+        ts = self.tables.timesteps(num_steps)
+        coef_host = self.tables.coefficient_table(num_steps)          # (refuses a schedule over an infinite sigma)
+        return ts, coef_host, dict(orders=[self.tables.order(i) for i in range(num_steps)], hist=[],
+                                   input_denom=self.tables.input_denominators(num_steps))
+
+    @torch.no_grad()
+    def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
+             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
+             guidance_rescale: float = 0.0) -> None:
+        """one step, latents (B,4,F,h,w) f32 updated in place; the steps of a clip are taken in order from i = 0 (LMS: the history is the state).
+        variance_noise (latents' shape, f32): the noise of an ancestral step, scaled by the step's sigma_up"""
+        B, CL, F, H, W = latents.shape
+        phi = check_guidance_rescale(guidance_rescale)
+        if phi > 0 and not st["cfg"]:
+            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        if (variance_noise is not None) != (self.kind == "euler_ancestral"):
+            raise ValueError(f"the {self.kind} sampler takes {'a' if self.kind == 'euler_ancestral' else 'no'} noise tensor per step")
+        hist, hk = st["hist"], dict(order=1)
+        if self.kind == "lms":
+            if len(hist) != 4 or hist[0].shape != latents.shape or hist[0].device != latents.device:
+                hist[:] = [torch.empty_like(latents) for _ in range(4)]
+            order = st["orders"][i]
+            hk = dict(order=order, hist_out=hist[i % 4], hist_1=hist[(i - 1) % 4] if order >= 2 else None,
+                      hist_2=hist[(i - 2) % 4] if order >= 3 else None, hist_3=hist[(i - 3) % 4] if order >= 4 else None)
+        pred, single = self.predict(st, i, latents, first_image_latents, mask, input_denom=st["input_denom"][i])
+        self.unet.ops.cfg_sigma_step(pred, latents, st["coef"][i], noise=variance_noise, B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1],
+                                     cfg=st["cfg"], guidance=st["guidance"], pred_single=single, video_scale=st.get("video_scale", 0.0),
+                                     guidance_rescale=phi, **hk)
+
+    @torch.no_grad()
+    def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float, *args, use_graph: Optional[bool] = None,
+               eta: float = 0.0, generator=None, use_clipped_model_output: bool = False, **kwargs) -> Tensor:
+        # (DDIMSampler.sample draws one noise tensor per step from `generator` exactly when its eta is positive: the ancestral kind's switch)
+        return super().sample(latents, text_embeddings, num_steps, guidance_scale, *args, use_graph=False,
+                              eta=1.0 if self.kind == "euler_ancestral" else 0.0, generator=generator, use_clipped_model_output=False, **kwargs)
+
+
 def make_sampler(unet: UNet3DEngine, scheduler_config) -> DDIMSampler:
-    """the sampler of a scheduler's engine_config: SolverConfig -> SolverSampler, DDIMConfig -> DDIMSampler"""
+    """the sampler of a scheduler's engine_config: SolverConfig -> SolverSampler, SigmaConfig -> SigmaSampler, DDIMConfig -> DDIMSampler"""
     if isinstance(scheduler_config, SolverConfig):
         return SolverSampler(unet, scheduler_config)
+    if isinstance(scheduler_config, SigmaConfig):
+        return SigmaSampler(unet, scheduler_config)
     if isinstance(scheduler_config, DDIMConfig):
         return DDIMSampler(unet, scheduler_config)
-    raise TypeError(f"no sampler for a scheduler config of type {type(scheduler_config).__name__} (DDIMConfig or SolverConfig)")
+    raise TypeError(f"no sampler for a scheduler config of type {type(scheduler_config).__name__} (DDIMConfig, SolverConfig or SigmaConfig)")

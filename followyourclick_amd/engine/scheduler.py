@@ -14,7 +14,7 @@ from typing import List
 import numpy as np
 import torch
 
-from .config import DDIMConfig, SolverConfig
+from .config import DDIMConfig, SigmaConfig, SolverConfig
 
 PRED_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 
@@ -249,3 +249,124 @@ class SolverTables:
         for t in ts:
             self.check_step(t)
         return torch.tensor([self.step_coefficients(ts, i, o) for i, o in enumerate(self.plan(num_inference_steps))], dtype=torch.float64).float()
+
+
+SIGMA_KINDS = ("euler", "euler_ancestral", "lms")
+
+
+class SigmaTables:
+    """The sigma-space (k-diffusion) samplers on the host: Euler, Euler ancestral and LMS (reference diffusers/schedulers/
+    scheduling_euler_discrete.py, scheduling_euler_ancestral_discrete.py, scheduling_lms_discrete.py).
+
+    sigma = sqrt((1 - abar) / abar) is the reference's f32 op sequence, interpolated in f64 at the fractional timesteps
+    linspace(0, T - 1, n)[::-1] and cast to f32 (bit-identical tables).  The latents live in sigma space (x = x0 + sigma noise, started at
+    init_noise_sigma), the UNet sees x / sqrt(sigma^2 + 1), and every update of the three is linear in the latents x, the (guided) prediction
+    v, up to three stored derivatives and a noise tensor, so a step collapses to eight numbers:
+
+        d  = a_x x + a_v v                                                  (the derivative (x - x0) / sigma)
+        x' = c_x x + c_0 d + c_1 d_1 + c_2 d_2 + c_3 d_3 + c_n noise
+
+    The scalars the reference forms (dt, sigma_up, sigma_down) are formed in f32 tensor arithmetic in its order, the rest in f64 from the f32
+    sigmas, each coefficient rounded once to f32; the update itself is the fused guidance + step kernel (fyc_cfg_sigma_step).  The LMS
+    coefficients are the integrals of the Lagrange basis polynomials in closed form (the reference integrates them numerically)."""
+
+    def __init__(self, cfg: SigmaConfig):
+        self.cfg = cfg
+        n = cfg.num_train_timesteps
+        if cfg.kind not in SIGMA_KINDS:
+            raise ValueError(f"kind given as {cfg.kind!r} must be one of {SIGMA_KINDS}")
+        if cfg.trained_betas is not None:
+            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
+        elif cfg.beta_schedule == "linear":
+            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
+        elif cfg.beta_schedule == "scaled_linear":
+            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
+        else:
+            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for SigmaTables")
+        if cfg.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type given as {cfg.prediction_type} must be one of `epsilon`, or `v_prediction`")
+        if cfg.rescale_betas_zero_snr:
+            betas = rescale_zero_terminal_snr(betas)
+        self.betas = betas
+        self.alphas = 1.0 - betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        if cfg.rescale_betas_zero_snr:
+            self.alphas_cumprod[-1] = 2.0 ** -24          # sigma_max = sqrt(2^24 - 1) ~ 4096 instead of infinity
+        self.pred_type = PRED_TYPES[cfg.prediction_type]
+        self.train_sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()            # f32 [T], ascending
+        # (the reference's constructor: the reversed table with 0 appended, cast to f32, its maximum)
+        self.init_noise_sigma = float(np.concatenate([self.train_sigmas[::-1], [0.0]]).astype(np.float32).max())
+
+    def timesteps(self, num_inference_steps: int) -> torch.Tensor:
+        """set_timesteps: linspace(0, T - 1, n)[::-1] in float64 - fractional (957.375 at n = 25); the UNet's embedding gets them as they are"""
+        n = int(num_inference_steps)
+        if n < 1:
+            raise ValueError(f"num_inference_steps = {num_inference_steps} must be at least 1")
+        return torch.from_numpy(np.linspace(0, self.cfg.num_train_timesteps - 1, n, dtype=float)[::-1].copy())
+
+    def sigmas(self, num_inference_steps: int) -> torch.Tensor:
+        """[n + 1] f32: the training sigmas interpolated at the timesteps, then 0.  A schedule that touches a timestep where alphas_cumprod is 0
+        (sigma = inf; the reference goes on to inf / NaN latents) is refused."""
+        ts = self.timesteps(num_inference_steps).numpy()
+        sig = np.interp(ts, np.arange(0, len(self.train_sigmas)), self.train_sigmas)
+        if not np.isfinite(sig).all():
+            t = ts[~np.isfinite(sig)][0]
+            raise ValueError(f"timestep {t:g}: alphas_cumprod is 0 there (zero terminal SNR), so sigma is infinite; a sigma-space scheduler "
+                             "needs rescale_betas_zero_snr=True, which rescales the betas itself and ends the table at alphas_cumprod = 2^-24")
+        return torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+
+    def input_denominators(self, num_inference_steps: int) -> List[float]:
+        """per step, the f32 value (sigma^2 + 1) ^ 0.5 that scale_model_input divides the UNet's input by, formed as the reference forms it"""
+        return [float((s ** 2 + 1) ** 0.5) for s in self.sigmas(num_inference_steps)[:-1]]
+
+    def order(self, i: int, max_order: int = 4) -> int:
+        """how many derivatives step i uses: 1 for the Euler samplers, min(i + 1, order) for LMS (scheduling_lms_discrete.py:239)"""
+        return min(i + 1, max_order) if self.cfg.kind == "lms" else 1
+
+    @staticmethod
+    def lms_coefficients(sigmas: torch.Tensor, i: int, order: int) -> List[float]:
+        """c_k = integral from sigmas[i] to sigmas[i + 1] of l_k, the Lagrange basis polynomial on sigmas[i], .., sigmas[i - order + 1]
+        (get_lms_coefficient, :136-156), in closed form in f64 from the f32 sigmas.  In u = tau - sigmas[i] the antiderivative vanishes at the
+        lower limit, so nothing cancels between the two ends."""
+        from numpy.polynomial import polynomial as Poly
+        s = [float(v) for v in sigmas]
+        h = s[i + 1] - s[i]
+        out = []
+        for k in range(order):
+            p = np.array([1.0])
+            for j in range(order):
+                if j != k:
+                    p = Poly.polymul(p, np.array([-(s[i - j] - s[i]), 1.0]) / (s[i - k] - s[i - j]))
+            out.append(float(Poly.polyval(h, Poly.polyint(p))))
+        return out
+
+    def step_coefficients(self, sigmas: torch.Tensor, i: int, order: int = None) -> List[float]:
+        """{a_x, a_v, c_x, c_0, c_1, c_2, c_3, c_n} of step i of the schedule `sigmas` ([n + 1] f32), in f64.  order: how many derivatives an LMS
+        step uses (None = self.order(i))"""
+        kind = self.cfg.kind
+        order = self.order(i) if order is None else order
+        sg, sg_to = sigmas[i], sigmas[i + 1]                # 0-dim f32 tensors: the reference's operands
+        s = float(sg)
+        if self.cfg.prediction_type == "epsilon":           # x0 = x - s v: d = v
+            ax, av = 0.0, 1.0
+        else:                                               # x0 = -s / sqrt(s^2 + 1) v + x / (s^2 + 1): d = s / (s^2 + 1) x + v / sqrt(s^2 + 1)
+            ax, av = s / (s * s + 1.0), 1.0 / (s * s + 1.0) ** 0.5
+        c = [0.0, 0.0, 0.0, 0.0]
+        cn = 0.0
+        if kind == "euler":
+            c[0] = float(sg_to - sg)                                                        # dt (:251, gamma = 0)
+        elif kind == "euler_ancestral":
+            sigma_up = (sg_to ** 2 * (sg ** 2 - sg_to ** 2) / sg ** 2) ** 0.5               # (:220-228)
+            sigma_down = (sg_to ** 2 - sigma_up ** 2) ** 0.5
+            c[0], cn = float(sigma_down - sg), float(sigma_up)
+        else:
+            c[:order] = self.lms_coefficients(sigmas, i, order)
+        return [ax, av, 1.0, *c, cn]
+
+    def coefficient_table(self, num_inference_steps: int) -> torch.Tensor:
+        """[n][8] f32, each entry rounded once"""
+        sig = self.sigmas(num_inference_steps)
+        tab = torch.tensor([self.step_coefficients(sig, i) for i in range(num_inference_steps)], dtype=torch.float64).float()
+        if not torch.isfinite(tab).all():
+            raise ValueError(f"the {self.cfg.kind} schedule of {num_inference_steps} steps has a non-finite coefficient (sigmas {sig.tolist()})")
+        return tab

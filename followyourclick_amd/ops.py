@@ -651,6 +651,51 @@ class HipOps:
             a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
         self._call("fyc_cfg_solver_step", a)
 
+    def cfg_sigma_step(self, pred: Tensor, latents: Tensor, coef: Tensor, *, hist_out: Optional[Tensor] = None, hist_1: Optional[Tensor] = None,
+                       hist_2: Optional[Tensor] = None, hist_3: Optional[Tensor] = None, order: int = 1, noise: Optional[Tensor] = None,
+                       B: int, F: int, HW: int, c_latent: int, ld: int, cfg: bool, guidance: float, pred_single: Optional[Tensor] = None,
+                       video_scale: float = 0.0, guidance_rescale: float = 0.0) -> None:
+        """guidance + one Euler / Euler-ancestral / LMS update (include/fyc.h, fyc_cfg_sigma_step): coef f32[8] = {a_x, a_v, c_x, c_0, c_1, c_2,
+        c_3, c_n}; latents are updated in place, hist_out (None = not stored) receives this step's derivative, hist_k holds that of k steps ago
+        (read only at order > k), noise (None = none) is the ancestral step's.  The moments workspace of the guidance rescale is the one
+        cfg_ddim_step_rescaled keeps."""
+        self.ensure_init(pred.device)
+        if coef.numel() < 8:
+            raise ValueError(f"cfg_sigma_step: coef holds {coef.numel()} values, the kernel's table row has 8")
+        for name, h in (("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2), ("hist_3", hist_3), ("noise", noise)):
+            if h is not None and h.numel() != latents.numel():
+                raise ValueError(f"cfg_sigma_step: {name} must have the latents' shape")
+        if pred_single is not None and pred_single.dtype != pred.dtype:
+            raise TypeError("cfg_sigma_step: pred_single dtype differs from pred")
+        a = L.CfgSigmaArgs()
+        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
+        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
+        a.pred_single, a.video_scale = _p(pred_single), video_scale
+        a.hist_out, a.hist_1, a.hist_2, a.hist_3 = _f32(hist_out, "hist_out"), _f32(hist_1, "hist_1"), _f32(hist_2, "hist_2"), _f32(hist_3, "hist_3")
+        a.order, a.noise = int(order), _f32(noise, "noise")
+        a.guidance_rescale = float(guidance_rescale)
+        key = ("cfg_sigma", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg))
+        need = self._ws_need.get(key)
+        if need is None:
+            need = self._ws_need[key] = int(self.lib.fyc_cfg_sigma_workspace_bytes(C.byref(a)))
+        if need > 0:
+            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
+                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+            a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._call("fyc_cfg_sigma_step", a)
+
+    def unet_input_scaled(self, latents: Tensor, mask: Optional[Tensor], first: Optional[Tensor], x: Tensor, *, denom: float, scale_cond: bool,
+                          B: int, F: int, HW: int, c_latent: int, c_pad: int, cfg_dup: int, mask_frames: int = 1, mode: int = 0) -> None:
+        """unet_input with every stored value divided by denom = sqrt(sigma^2 + 1) (include/fyc.h, fyc_unet_input_scaled); scale_cond: the mask
+        channel and the first-frame block of mode 0 are divided too"""
+        self.ensure_init(latents.device)
+        s = L.UnetInputScaledArgs()
+        a = s.base
+        a.latents, a.mask, a.first, a.x = _f32(latents, "latents"), _f32(mask, "mask"), _f32(first, "first"), _p(x)
+        a.B, a.F, a.HW, a.c_latent, a.c_pad, a.cfg_dup, a.mask_frames, a.dtype, a.mode = B, F, HW, c_latent, c_pad, cfg_dup, mask_frames, _dt(x), mode
+        s.denom, s.scale_cond = float(denom), int(scale_cond)
+        self._call("fyc_unet_input_scaled", s)
+
     def nchw_to_nhwc(self, z: Tensor, x: Tensor, *, N: int, C_: int, HW: int, c_pad: int, scale: float) -> None:
         self.ensure_init(z.device)
         a = L.NchwInArgs()

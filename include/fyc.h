@@ -449,6 +449,43 @@ typedef struct {
 int64_t fyc_cfg_solver_workspace_bytes(const fyc_cfg_solver_args* a);
 int fyc_cfg_solver_step(const fyc_cfg_solver_args* a, void* stream);
 
+/* (308, added entry points) Classifier-free guidance + one step of a sigma-space (k-diffusion) sampler in one pass: Euler, Euler ancestral
+ * and LMS (scheduling_euler_discrete.py:160-258, scheduling_euler_ancestral_discrete.py:159-250, scheduling_lms_discrete.py:184-250).
+ * Their updates are linear in the latents x, the guided prediction v, up to three stored derivatives and (ancestral) a noise tensor; the
+ * host collapses a step to coef (device f32[8]) = {a_x, a_v, c_x, c_0, c_1, c_2, c_3, c_n}:
+ *   v  = the guided prediction exactly as fyc_cfg_ddim_step forms it; with guidance_rescale > 0 times the per-sample factor of
+ *        fyc_cfg_ddim_step_rescaled (the same moments and factor launches run in front: no atomics, the same call gives the same bits)
+ *   d  = a_x x + a_v v                                                          (the ODE derivative (x - x0) / sigma)
+ *   x' = c_x x + c_0 d + c_1 hist_1 + c_2 hist_2 + c_3 hist_3 + c_n noise       (summed left to right)
+ * latents (B,c_latent,F,h,w) f32 is updated in place to x'.  hist_out (same shape, f32) receives d; NULL = not stored (the two Euler
+ * samplers keep no history).  hist_k is the d of k steps ago and is read only when order > k; noise (same shape, f32) is read only when it
+ * is not NULL: a buffer the call does not use may be NULL or uninitialised (NaN included) without reaching the result.  pred, pred_single,
+ * cfg, guidance, video_scale, ld, dtype: as in fyc_cfg_ddim_args.  Refused before anything is launched: everything fyc_cfg_solver_step
+ * refuses (hist_out may be NULL here), an order outside 1..4, a NULL history the order reads, hist_out or noise overlapping the latents, a
+ * history or each other.  Needs fyc_init().  Workspace: fyc_cfg_sigma_workspace_bytes() bytes, 8-byte aligned; 0 = none needed. */
+typedef struct {
+  const void* pred; float* latents; const float* coef;
+  int32_t B, F, HW, c_latent, ld, cfg; float guidance;
+  int32_t dtype;
+  const void* pred_single; float video_scale;
+  float* hist_out; const float* hist_1; const float* hist_2; const float* hist_3;
+  int32_t order;
+  const float* noise;
+  float guidance_rescale; void* workspace; int64_t workspace_bytes;
+} fyc_cfg_sigma_args;
+int64_t fyc_cfg_sigma_workspace_bytes(const fyc_cfg_sigma_args* a);
+int fyc_cfg_sigma_step(const fyc_cfg_sigma_args* a, void* stream);
+
+/* (308, added entry points) fyc_unet_input with every stored value divided by denom = sqrt(sigma^2 + 1), the scale_model_input of the
+ * sigma-space schedulers (pipeline_animation.py:708-712 scales the tensor it hands to the UNet).  `base` keeps the layout of
+ * fyc_unet_input_args.  Each stored value is the f32 value / denom - a true division, as the reference divides - rounded once to dtype.
+ * Mode 0 with scale_cond = 1: the mask channel and the first-frame block are divided as well (the reference scales the concatenated
+ * tensor); scale_cond = 0 leaves them as fyc_unet_input writes them.  Mode 1: only the latents are divided (the UNet concatenates the
+ * clean first-frame latents itself, behind the scaling), scale_cond must be 0.  Pad channels stay 0.  denom = 1 writes the bits of
+ * fyc_unet_input.  Refused: what fyc_unet_input refuses, a denom that is not finite or below 1, scale_cond outside {0, 1} or 1 in mode 1. */
+typedef struct { fyc_unet_input_args base; float denom; int32_t scale_cond; } fyc_unet_input_scaled_args;
+int fyc_unet_input_scaled(const fyc_unet_input_scaled_args* a, void* stream);
+
 /* VAE ends: z (N,4,h,w) f32 * scale -> channels-last [N][hw][c_pad];
  * image channels-last [N][HW][ld] -> (N,3,H,W) f32 = clamp(x/2+0.5, 0, 1) (pipeline_animation.py:402,410) */
 typedef struct { const float* z; void* x; int32_t N, C, HW, c_pad; float scale; int32_t dtype; } fyc_nchw_in_args;
