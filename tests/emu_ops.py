@@ -260,14 +260,16 @@ class EmuOps:
             if key not in cache:
                 cache[key] = (wstream, self._tblock_unpack(wstream, Cc, heads, d))      # (holds the stream: see ff_block)
             w, tab, wo = cache[key][1]
-            Xf = X.float()
-            xn = ((Xf - Xf.mean(-1, keepdim=True)) * (Xf.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()).to(T).to(acc_t)
+            xn = ((X - X.mean(-1, keepdim=True)) * (X.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()).to(T).to(acc_t)      # (statistics in the accumulation type, as ff_block)
             qkv = torch.einsum("bfpc,hsnc->bfphsn", xn, w.to(acc_t)) + tab.to(acc_t).permute(1, 0, 2, 3)[None, :, None]   # b f p h 3 48
             qkv = qkv.to(T).to(acc_t)
             q, k, v = qkv[..., 0, :d], qkv[..., 1, :d], qkv[..., 2, :d]
             S = torch.einsum("bfphd,bgphd->bphfg", q, k) * scale
-            P = S.softmax(dim=-1).to(T).to(acc_t)
-            O = torch.einsum("bphfg,bgphd->bfphd", P, v).to(T).to(acc_t)
+            # csrc/temporal_block_rr.hip:247-249, :262-265: the exponentials are rounded to the storage type BEFORE they are normalised, and the product with v is
+            # divided by the sum of the unrounded ones (the LDS-tile kernel below rounds the normalised weights: temporal_block.hip:219)
+            E = torch.exp(S - S.max(dim=-1, keepdim=True).values)
+            O = torch.einsum("bphfg,bgphd->bfphd", E.to(T).to(acc_t), v) / E.sum(dim=-1).permute(0, 3, 1, 2)[..., None]
+            O = O.to(T).to(acc_t)
             y = X + torch.einsum("bfphk,hnk->bfpn", O, wo.to(acc_t)[:, :, :d]) + b_out.to(acc_t)
             _flat(out)[: y.numel()].reshape(y.shape).copy_(y.to(out.dtype))
             return
@@ -350,10 +352,9 @@ class EmuOps:
             cache[key] = (wstream, self._ff_unpack(wstream, C_, hidden))
         Wp, W1, bi, W2 = cache[key][1]
         X = _flat(x)[: rows * C_].reshape(rows, C_).to(acc_t)
-        Xf = X.float()
-        mean = Xf.mean(-1, keepdim=True)
-        rstd = (Xf.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()
-        xn = ((Xf - mean) * rstd).to(T).to(acc_t)
+        mean = X.mean(-1, keepdim=True)                       # (in the accumulation type: with acc = f64 the value the kernel's f32 statistics approximate)
+        rstd = (X.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()
+        xn = ((X - mean) * rstd).to(T).to(acc_t)
         pre = xn @ W1.to(acc_t).t() + bi.to(acc_t)
         blk = pre.reshape(rows, hidden // 16, 2, 16)
         h = (blk[:, :, 0] * F.gelu(blk[:, :, 1])).reshape(rows, hidden).to(T).to(acc_t)
@@ -410,9 +411,10 @@ class EmuOps:
             cnt = gn_rows_per_sample * cpg
             mean = st[..., 0] / cnt
             rstd = 1.0 / torch.sqrt((st[..., 1] / cnt - mean * mean).clamp_min(0) + gn_eps)
-            scale = rstd.float()[:, :, None] * gn_gamma.float().reshape(gn_groups, cpg)[None]            # [S][groups][cpg]
-            shift = gn_beta.float().reshape(gn_groups, cpg)[None] - mean.float()[:, :, None] * scale
-            Xn = X.float().reshape(S, gn_rows_per_sample, K) * scale.reshape(S, 1, K) + shift.reshape(S, 1, K)
+            # scale, shift and the multiply-add in the accumulation type: the kernel's are f32 (one fused multiply-add per element, csrc/panel_linear.hip:131)
+            scale = rstd.to(acc_t)[:, :, None] * gn_gamma.to(acc_t).reshape(gn_groups, cpg)[None]            # [S][groups][cpg]
+            shift = gn_beta.to(acc_t).reshape(gn_groups, cpg)[None] - mean.to(acc_t)[:, :, None] * scale
+            Xn = X.reshape(S, gn_rows_per_sample, K) * scale.reshape(S, 1, K) + shift.reshape(S, 1, K)
             X = Xn.reshape(rows, K).to(T).to(acc_t)
         y = X @ W.to(acc_t).t()
         if bias is not None:

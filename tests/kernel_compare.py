@@ -81,6 +81,46 @@ there, but the reference does when it is stored: half of that unit is the refere
   fyc_chan_stats_reduce and the fold of fyc_gn_apply_cs: f64 sums of f32 values, n 2^-53 sum |terms|; with integer-valued partials exact.
 A torch model of these rounding points (tests/norm_cases.py: f32 tensors combined in the kernel's order) stays inside every bound (tests/test_norm_cases.py); what the MI355X
 measured is in profiles/norm_bound_coverage.txt.
+
+Row-panel kernels (csrc/panel_linear.hip, csrc/ff_block.hip).  The bounds are computed in tests/row_panel_cases.py beside the reference of EmuOps(acc=float64) and handed to
+compare() as `bound`; u = 2^-24, the constant is 1.  These kernels round INTERMEDIATES to the storage type T, and so does the reference, at the same places.  For such an intermediate
+with exact value z the kernel holds z + d before it rounds, |d| <= e, e the f32 error of the kernel's arithmetic up to there.  If no rounding boundary of T (the middle of two
+neighbouring T numbers) lies within e of z, both sides store the SAME T number and the stage costs nothing; otherwise the kernel may store the neighbour, and the element is charged
+the distance between the T numbers of z - e, z and z + e (one ulp_T unless e exceeds it; row_panel_cases.spread).  The charge goes through the next stage with the absolute values
+of that stage's weights.  The last stage is a GEMM and gets ulp_T(ref) + (K + 8) u S as element_bound does, S including bias and residual.
+  fyc_panel_linear, GroupNorm on the operand registers (panel_linear.hip:104-115, :131): mean and var = q / cnt - mean^2 in f64 from f64 sums (rel64 = 8 2^-53 (q / cnt + mean^2) /
+    (2 (var + eps)) + 64 2^-53 on rstd, the latter for the order of the f64 additions), rstd -> f32 (u), sc = rstd * gamma (u), (float)mean (u), mean * sc (u), sh = beta - mean sc
+    (u |sh|), xn = fmaf(x, sc, sh) (u |xn|), then T:
+        e = |x sc| (2 u + rel64) + |mean sc| (4 u + rel64) + u |sh| + u |xn|;        out: ulp_T(ref) + (K + 8) u (|xn_T| |W|^T + |bias| + |res|) + charge |W|^T   (:163, :179).
+    Without GroupNorm nothing is charged and the bound is element_bound()'s.
+  fyc_ff_block, LayerNorm in registers (ff_block.hip:136-156, :187): a lane adds its 160 tokens pair by pair in a fixed order, the two lanes of a row meet, * (1.0f / 320); the sum of
+    squares about that mean by fmaf.  These are correctly rounded f32 operations in an order the source fixes (the library is built with -ffp-contract=off), so a simulation in f32
+    (row_panel_cases.ff_stats_sim, fmaf emulated exactly) HAS the kernel's mean and variance v, and their error is computed, not bounded: Higham's (n - 1) u sum |x| for a chain of
+    160 would put 1.6 % of a large-mean row's elements beside a bf16 boundary.  Left are rsqrtf (1 ulp = 2 u) and the product (u):  e = |(x - mu) / sqrt(v) - xn| + 3 u |xn|.
+  FF1 + bias (ff_block.hip:204, :222-223): dv, dg = (320 + 8) u (|xn_T| |W1|^T + |b1|) + charge_xn |W1|^T for value and gate.
+  geglu_one (csrc/fyc_common.h): h = v (g Phi_p(g)), Phi_p the degree-7 polynomial in the clamped g.  PHI_ERR = max |Phi_p - Phi| is evaluated in f64 on a dense grid against
+    torch.special.erf (row_panel_cases.phi_poly_error; the test repeats it on a finer grid) - it is 1.4e-4, not the 9e-5 the header quotes for x Phi(x).  Its f32 evaluation (xc^2,
+    seven fmaf, two products, one fmaf): rnd(g) = |xc| / 2 * 16 u sum |c_i| xc^2i + 3 u.  With DG = 1.13 >= |d/dg (g Phi(g))|:
+        e_h = dv |g Phi(g)| + |v| (DG dg + |g| (PHI_ERR + rnd(g))) + DG dv dg + 3 u |h|;
+        out: ulp_T(ref) + (320 + 1280 + 8) u (|x| |Wp|^T + |h_T| |W2'|^T + |b_out| + |res|) + charge_h |W2'|^T        (one f32 chain over projection and FF2: :173, :241, :331).
+  chan_parts of fyc_ff_block (:339-378), against the f64 sums of the values AS STORED by the same launch: L u sum |x| and (L + 1) u sum x^2 with L = 22 + 6 (a thread adds at most
+    22 rows, then the 6 row slices are added), plus the f32 spacing of the reference as stored; an integer-valued output gives the f64 sums bit for bit.
+  The shares of charged elements are a condition on the INPUTS, asserted from the reference alone (tests/test_row_panel_cases.py): at most 1 % of a row's xn and 25 % of a row's
+    hidden elements.  The recipes of row_panel_cases say what that takes - f16 operands kept away from zero, FF1 rows of about 8 weights, gates mostly positive, and in f16 six
+    hidden units per chunk with a value path - because (K + 8) u S of a dense K = 320 row is of the size of the f16 spacing.
+The torch model of these rounding points stays inside every bound and every declared defect leaves it (tests/test_row_panel_cases.py); what the MI355X measured is in
+profiles/row_panel_bound_coverage.txt.
+  fyc_temporal_block (csrc/temporal_block.hip, the LDS-tile kernel; csrc/temporal_block_rr.hip, the register-resident one).  q, k, v are rounded to T by both kernels and by the
+    reference; each element is charged by the boundary test above with
+      rr (:107-137, :175, :186): xn as for fyc_ff_block (row_panel_cases.tb_stats_sim has this kernel's order: 80 tokens per lane in pairs, four lanes per row), then
+        e = (320 + 8) u (|xn_T| |W|^T + |bias + pe|) + charge_xn |W|^T;
+      LDS-tile (:69-84, :166): the raw tokens enter the MFMA, the LayerNorm is folded: rs (acc - mu colsum) + bias + pe with mu and the variance q / C - mu^2 of the simulated f32
+        chain (four threads per row, 80 tokens each) and rs within 2 u of 1 / sqrt:  e = |that value - the f64 one| + rs (321 u |x| |W'|^T + 2 u |mu colsum|) + 6 u (the terms).
+    The attention core is softmax_bound_terms(kind="temporal") on the reference's rounded q, k, v with dq, dk, dv = those charges: the rounding of P is charged there
+    unconditionally (r per weight; the rr kernel rounds the exponentials before it normalises them, :247-249, the LDS-tile kernel after, :219 - the emulator now does each as its
+    kernel does), and the reference's own rounded weights are within r sum w |v| of the exact ones.  The attention output is rounded to T on both sides: charged by the boundary
+    test with e = rest + r sum_j w_j |v_j|, which in practice charges every element.  Output projection over 8 heads x 64 k-slots, bias and residual:
+        out: ulp_T(ref) + (512 + 8) u (|x| + |O_T| |Wo|^T + |b_out|) + charge_O |Wo|^T.
 """
 import math
 from collections import namedtuple
@@ -121,10 +161,11 @@ LOG2E, LN2 = 1.4426950408889634, math.log(2.0)
 Labels = namedtuple("Labels", ["row", "col"])
 
 
-def softmax_bound_terms(q, k, v, *, scale, dtype, kind, dq=None, dk=None):
+def softmax_bound_terms(q, k, v, *, scale, dtype, kind, dq=None, dk=None, dv=None):
     """One (batch, head), or a few with leading dimensions: q [n_q][d], k [n_k][d], v [n_k][d] as f64 -> (o, rest, w): the f64 reference output [n_q][d], the bound WITHOUT its ulp_T(ref)
     term (the caller rounds o into its buffer and adds the ulp of what it stored) and the reference weights [n_q][n_k].  kind: "flash" or "temporal"
-    (16-bit or f32 by dtype); dq, dk: per-element uncertainty of the rotated q and k (RoPE), same shapes.  The middle term is O(n_q n_k d): call per head."""
+    (16-bit or f32 by dtype); dq, dk: per-element uncertainty of the rotated q and k (RoPE), same shapes; dv: per-element uncertainty of v, charged as w @ dv with the kernel's own weights (at most
+    (w_j + w_j eta_j) / den).  The middle term is O(n_q n_k d): call per head."""
     assert q.dtype == k.dtype == v.dtype == torch.float64 and kind in ("flash", "temporal")
     d, n_k, u, f32 = q.shape[-1], k.shape[-2], U[dtype], 2.0 ** -24
     r = u if kind == "flash" else R[dtype]      # what one rounding to T is charged (module docstring)
@@ -140,6 +181,8 @@ def softmax_bound_terms(q, k, v, *, scale, dtype, kind, dq=None, dk=None):
     dev = (v[..., None, :, :] - o[..., :, None, :]).abs() if kind == "flash" else v.abs()[..., None, :, :]
     den = (w * torch.exp(-arg)).sum(dim=-1, keepdim=True)      # sum_j w_j (1 + e_j) >= sum_j w_j exp(-a_j) (>= 1 - sum_j w_j eta_j, and never 0)
     rest = (we[..., None] * dev).sum(dim=-2) / den + (n_k + 8) * f32 * (w @ v.abs())
+    if dv is not None:
+        rest = rest + ((w + we) @ dv.abs()) / den
     return o, rest, w
 
 
@@ -156,10 +199,11 @@ def _bits(t):
     return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
 
-def compare(got, ref, *, dtype, bound_terms=None, guard=None, tag, bound=None, rtol=None, labels=None):
+def compare(got, ref, *, dtype, bound_terms=None, guard=None, tag, bound=None, rtol=None, labels=None, lines=False):
     """With `bound` ([rows][columns] f64, a precomputed per-element bound: the softmax bounds of the module docstring), `rtol` (the global tolerance to
     assert) and `labels` (a Labels): (a), (b), (d), (e) below.  (c) is skipped: a single attention row whose arithmetic is right can sit at several times
     the project's global tolerance (one rounding of a dominant probability moves the whole row), which is exactly why the bound is per element.
+    `lines=True` runs (c) in this form as well, at `rtol` (the row-panel kernels: a row or a column is a dot product of hundreds of terms, none of which dominates).
 
     got, ref: [rows][columns], the kernel's output window and the reference from EmuOps(acc=torch.float64), both in the storage type `dtype`
     ("bf16" / "f16" / "f32").  Asserts, in this order: (a) finite everywhere, (b) global relative L2 <= RTOL[dtype], (c) relative L2 of every row and
@@ -189,7 +233,7 @@ def compare(got, ref, *, dtype, bound_terms=None, guard=None, tag, bound=None, r
     fig.update(global_rel=rel, elem_ratio=ratio.max().item())
     assert rel <= rtol, f"{tag}: global rel-L2 {rel:.3e} > {rtol:.1e}; worst element {ratio.max().item():.3g} x its bound at {_where(wi, wj, tile)}"
     # (c)
-    for axis, what in ((1, "row"), (0, "column")) if bound_terms is not None else ():
+    for axis, what in ((1, "row"), (0, "column")) if (bound_terms is not None or lines) else ():
         rn, dn, bnorm = r.norm(dim=axis), diff.norm(dim=axis), bound.norm(dim=axis)
         judged = rn > bnorm
         rel_ax = torch.where(judged, dn / rn.clamp_min(1e-300), torch.zeros_like(dn))
