@@ -137,6 +137,15 @@ class CfgSigmaArgs(C.Structure):      # (308, added entry points) fyc_cfg_sigma_
                 ("guidance_rescale", f32), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+class CfgPndmArgs(C.Structure):      # (308, added entry points) fyc_cfg_pndm_step: guidance + one PNDM evaluation (PLMS / Runge-Kutta mode)
+    _fields_ = [("pred", vp), ("latents", vp), ("coef", vp),
+                ("B", i32), ("F", i32), ("HW", i32), ("c_latent", i32), ("ld", i32), ("cfg", i32), ("guidance", f32),
+                ("dtype", i32), ("pred_single", vp), ("video_scale", f32),
+                ("sample_in", vp), ("sample_out", vp),
+                ("hist_out", vp), ("hist_1", vp), ("hist_2", vp), ("hist_3", vp), ("order", i32), ("acc_in", vp), ("acc_out", vp),
+                ("guidance_rescale", f32), ("workspace", vp), ("workspace_bytes", i64)]
+
+
 class UnetInputScaledArgs(C.Structure):      # (308, added entry points) fyc_unet_input_scaled: the input build's arguments as they are, the divisor behind them
     _fields_ = [("base", UnetInputArgs), ("denom", f32), ("scale_cond", i32)]
 
@@ -196,11 +205,12 @@ OPS = {
     "fyc_pack_conv3x3": PackConv3x3Args, "fyc_pack_geglu": PackGegluArgs, "fyc_temporal_block": TemporalBlockArgs,
     "fyc_ff_block": FFBlockArgs, "fyc_panel_linear": PanelLinearArgs, "fyc_repeat": RepeatArgs,
     "fyc_conv_up_phases": ConvUpPhasesArgs, "fyc_cfg_sigma_step": CfgSigmaArgs, "fyc_unet_input_scaled": UnetInputScaledArgs,
+    "fyc_cfg_pndm_step": CfgPndmArgs,
 }
 MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set_tuning", "fyc_gemm_row_parts", "fyc_gemm_stat_layout", "fyc_gemm_workspace_bytes", "fyc_gn_stats_workspace", "fyc_temporal_block_supported", "fyc_temporal_block_wstream_bytes",
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes",
         "fyc_cfg_ddim_rescale_workspace_bytes", "fyc_cfg_solver_workspace_bytes", "fyc_conv_up_phases_stat_layout", "fyc_conv_up_phases_supported",
-        "fyc_cfg_sigma_workspace_bytes"]
+        "fyc_cfg_sigma_workspace_bytes", "fyc_cfg_pndm_workspace_bytes"]
 
 _lib = None
 FYC_VERSION = 308        # the ABI version this binding's ctypes structs mirror (include/fyc.h::FYC_VERSION)
@@ -264,6 +274,9 @@ def load() -> C.CDLL:
     if not ab_build or hasattr(lib, "fyc_cfg_sigma_workspace_bytes"):
         lib.fyc_cfg_sigma_workspace_bytes.argtypes = [C.POINTER(CfgSigmaArgs)]
         lib.fyc_cfg_sigma_workspace_bytes.restype = i64
+    if not ab_build or hasattr(lib, "fyc_cfg_pndm_workspace_bytes"):
+        lib.fyc_cfg_pndm_workspace_bytes.argtypes = [C.POINTER(CfgPndmArgs)]
+        lib.fyc_cfg_pndm_workspace_bytes.restype = i64
     if not ab_build or hasattr(lib, "fyc_conv_up_phases_supported"):
         lib.fyc_conv_up_phases_supported.argtypes = [i32] * 7
         lib.fyc_conv_up_phases_supported.restype = C.c_int

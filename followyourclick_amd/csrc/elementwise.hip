@@ -264,6 +264,51 @@ __global__ void __launch_bounds__(256) cfg_sigma_kernel(const T* __restrict__ pr
   }
 }
 
+// Guidance + one evaluation of the PNDM scheduler, PLMS or Runge-Kutta mode (fyc_cfg_pndm_step).  coef = {c_x, c_0, c_1, c_2, c_3, s_g} gives
+// x' = c_x x + c_0 g + c_1 h1 + c_2 h2 + c_3 h3, summed left to right, with g the guided (and rescaled) prediction as it is - the histories
+// hold raw guided predictions, the v-prediction conversion is folded into c_x and the c_k - and x the saved sample (sample_in) when one is
+// handed over, the latents otherwise.  ORDER is a template parameter as in cfg_solver_kernel: a history the order does not use is never
+// loaded.  sample_in, sample_out, hist_out, acc_in and acc_out are NULL for the evaluations without them (one uniform branch each): nothing
+// is stored, nothing is loaded.  sample_out receives the latents as they were, acc_out = acc_in + s_g g (acc_in NULL: s_g g; acc_in may be
+// acc_out: element j is read and then written by the same thread).
+template <typename T, int ORDER, bool RESCALE>
+__global__ void __launch_bounds__(256) cfg_pndm_kernel(const T* __restrict__ pred, float* __restrict__ lat,
+                                                       const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
+                                                       int cfg, float guidance, const T* __restrict__ single, float video_scale,
+                                                       const float* __restrict__ sample_in, float* __restrict__ sample_out,
+                                                       float* __restrict__ hist_out, const float* __restrict__ hist_1,
+                                                       const float* __restrict__ hist_2, const float* __restrict__ hist_3,
+                                                       const float* acc_in, float* acc_out, const float* __restrict__ factor) {
+  const float cx = coef[0], c0 = coef[1], c1 = coef[2], c2 = coef[3], c3 = coef[4], sg = coef[5];
+  const long long total = (long long)B * F * HW;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int p = (int)(i % HW);
+    const long long bf = i / HW;
+    const int f = (int)(bf % F), b = (int)(bf / F);
+    const T* pu = pred + i * ld;                                   // uncond (or the only) half
+    const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
+    for (int c = 0; c < CL; ++c) {
+      float g = ElemIO<T>::ld(pu + c);
+      if (cfg) {
+        const float u = g, cnd = ElemIO<T>::ld(pc + c);
+        g = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
+        if (RESCALE) g *= factor[b];
+      }
+      const long long j = (((long long)b * CL + c) * F + f) * HW + p;
+      const float before = (sample_out || !sample_in) ? lat[j] : 0.f;      // with a saved sample to step from, the latents are not read
+      if (sample_out) sample_out[j] = before;
+      const float x = sample_in ? sample_in[j] : before;
+      float nx = cx * x + c0 * g;
+      if (ORDER >= 2) nx += c1 * hist_1[j];
+      if (ORDER >= 3) nx += c2 * hist_2[j];
+      if (ORDER >= 4) nx += c3 * hist_3[j];
+      lat[j] = nx;
+      if (hist_out) hist_out[j] = g;
+      if (acc_out) acc_out[j] = (acc_in ? acc_in[j] : 0.f) + sg * g;
+    }
+  }
+}
+
 // Moments pass of the guidance rescale.  Block (b, part) owns rows [part * CFG_MOMENT_ROWS, +CFG_MOMENT_ROWS) of the F * HW pixel-rows
 // of sample b - a run fixed by the shape; thread t takes rows t, t + 256, ... of the run.  c and v are the f32 values the step kernel
 // forms; {sum c, sum c^2, sum v, sum v^2} are accumulated in f64 (the squares of f32 values are exact there), reduced over the block by a
@@ -791,6 +836,90 @@ extern "C" int fyc_cfg_sigma_step(const fyc_cfg_sigma_args* a, void* stream) {
   else if (a->dtype == FYC_F16) cfg_sigma_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
   else cfg_sigma_dispatch<float>(a, rescale ? &pl : nullptr, st);
   FYC_CHECK_LAUNCH("fyc_cfg_sigma_step");
+  return 0;
+}
+
+// ---- PNDM (PLMS and Runge-Kutta modes): guidance (+ rescale) + update from the latents or the saved sample ------------------------
+static fyc_cfg_ddim_args cfg_pndm_guidance(const fyc_cfg_pndm_args* a) {
+  fyc_cfg_ddim_args s = {};
+  s.pred = a->pred; s.latents = a->latents; s.coef = a->coef;
+  s.B = a->B; s.F = a->F; s.HW = a->HW; s.c_latent = a->c_latent; s.ld = a->ld; s.cfg = a->cfg; s.guidance = a->guidance;
+  s.dtype = a->dtype; s.pred_single = a->pred_single; s.video_scale = a->video_scale;
+  return s;
+}
+
+extern "C" int64_t fyc_cfg_pndm_workspace_bytes(const fyc_cfg_pndm_args* a) {
+  CfgRescalePlan pl;
+  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->cfg) return 0;
+  const fyc_cfg_ddim_args s = cfg_pndm_guidance(a);
+  return cfg_rescale_plan(&s, pl) ? pl.bytes : 0;
+}
+
+template <typename T, bool RESCALE>
+static void cfg_pndm_launch(const fyc_cfg_pndm_args* a, const float* factor, hipStream_t st) {
+  const long long n = (long long)a->B * a->F * a->HW;
+  const dim3 grid(grid_for(n));
+  const T* pred = (const T*)a->pred;
+  const T* single = (const T*)a->pred_single;
+#define FYC_PNDM_LAUNCH(ORDER)                                                                                                       \
+  hipLaunchKernelGGL((cfg_pndm_kernel<T, ORDER, RESCALE>), grid, dim3(256), 0, st, pred, a->latents, a->coef, a->B, a->F, a->HW,     \
+                     a->c_latent, a->ld, a->cfg, a->guidance, single, a->video_scale, a->sample_in, a->sample_out, a->hist_out,      \
+                     a->hist_1, a->hist_2, a->hist_3, a->acc_in, a->acc_out, factor)
+  if (a->order == 1) FYC_PNDM_LAUNCH(1);
+  else if (a->order == 2) FYC_PNDM_LAUNCH(2);
+  else if (a->order == 3) FYC_PNDM_LAUNCH(3);
+  else FYC_PNDM_LAUNCH(4);
+#undef FYC_PNDM_LAUNCH
+}
+
+template <typename T>
+static void cfg_pndm_dispatch(const fyc_cfg_pndm_args* a, const CfgRescalePlan* pl, hipStream_t st) {
+  if (pl == nullptr) return cfg_pndm_launch<T, false>(a, nullptr, st);
+  const fyc_cfg_ddim_args s = cfg_pndm_guidance(a);
+  cfg_pndm_launch<T, true>(a, cfg_rescale_factors<T>(&s, a->workspace, a->guidance_rescale, *pl, st), st);
+}
+
+extern "C" int fyc_cfg_pndm_step(const fyc_cfg_pndm_args* a, void* stream) {
+  FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_pndm_step: null pointer");
+  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_pndm_step: bad dims");
+  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_cfg_pndm_step: bad dtype %d", a->dtype);
+  FYC_REQUIRE(a->order >= 1 && a->order <= 4, "fyc_cfg_pndm_step: order %d (1 .. 4)", a->order);
+  FYC_REQUIRE(a->order < 2 || a->hist_1 != nullptr, "fyc_cfg_pndm_step: order %d needs hist_1", a->order);
+  FYC_REQUIRE(a->order < 3 || a->hist_2 != nullptr, "fyc_cfg_pndm_step: order %d needs hist_2", a->order);
+  FYC_REQUIRE(a->order < 4 || a->hist_3 != nullptr, "fyc_cfg_pndm_step: order 4 needs hist_3");
+  // the latents and the outputs are written while other threads still read the inputs: any overlap of the [n] f32 ranges is refused,
+  // not only equal bases.  The one alias allowed is acc_out == acc_in (element j is read, then written, by the same thread).
+  const int64_t n = (int64_t)a->B * a->c_latent * a->F * a->HW;
+  auto overlaps = [n](const float* p, const float* q) { return p != nullptr && q != nullptr && p < q + n && q < p + n; };
+  FYC_REQUIRE(!overlaps(a->sample_in, a->latents), "fyc_cfg_pndm_step: sample_in aliases latents");
+  const float* const outs[3] = {a->sample_out, a->hist_out, a->acc_out};
+  const char* const out_names[3] = {"sample_out", "hist_out", "acc_out"};
+  const float* const ins[6] = {a->latents, a->hist_1, a->hist_2, a->hist_3, a->sample_in, a->acc_in};
+  const char* const in_names[6] = {"latents", "hist_1", "hist_2", "hist_3", "sample_in", "acc_in"};
+  for (int o = 0; o < 3; ++o) {
+    for (int k = 0; k < 6; ++k) {
+      if (o == 2 && k == 5 && a->acc_out == a->acc_in) continue;
+      FYC_REQUIRE(!overlaps(outs[o], ins[k]), "fyc_cfg_pndm_step: %s aliases %s", out_names[o], in_names[k]);
+    }
+    for (int k = o + 1; k < 3; ++k) FYC_REQUIRE(!overlaps(outs[o], outs[k]), "fyc_cfg_pndm_step: %s aliases %s", out_names[o], out_names[k]);
+  }
+  FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_pndm_step: pred_single needs classifier-free guidance (cfg = 1)");
+  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_pndm_step: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
+  hipStream_t st = (hipStream_t)stream;
+  CfgRescalePlan pl;
+  const bool rescale = a->guidance_rescale > 0.f;
+  if (rescale) {
+    FYC_REQUIRE(a->cfg, "fyc_cfg_pndm_step: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
+    const fyc_cfg_ddim_args s = cfg_pndm_guidance(a);
+    FYC_REQUIRE(cfg_rescale_plan(&s, pl), "fyc_cfg_pndm_step: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)a->F * a->HW * a->c_latent);
+    FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_pndm_step: workspace is null or not 8-byte aligned");
+    FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_pndm_step: workspace_bytes %lld < %lld (fyc_cfg_pndm_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
+  }
+  FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_pndm_step: fyc_init() not called");
+  if (a->dtype == FYC_BF16) cfg_pndm_dispatch<bf16_t>(a, rescale ? &pl : nullptr, st);
+  else if (a->dtype == FYC_F16) cfg_pndm_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
+  else cfg_pndm_dispatch<float>(a, rescale ? &pl : nullptr, st);
+  FYC_CHECK_LAUNCH("fyc_cfg_pndm_step");
   return 0;
 }
 

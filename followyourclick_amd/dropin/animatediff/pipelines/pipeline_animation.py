@@ -250,13 +250,15 @@ class AnimationPipeline:
         # the reference's); the reference's scripts cannot pass it, for them the FYC_GUIDANCE_RESCALE environment switch (unset = 0 = off)
         guidance_rescale = resolve_guidance_rescale(kwargs.get("guidance_rescale"))
         engine = self.unet._get_engine()
-        sampler = make_sampler(engine, self.scheduler.engine_config)      # by the scheduler's engine_config type: DDIM, the multistep solver or a sigma-space sampler
-        bar = self.progress_bar(total=num_inference_steps)
+        sampler = make_sampler(engine, self.scheduler.engine_config)      # by the scheduler's engine_config type: DDIM, the multistep solver, a sigma-space sampler or PNDM
+        bar = self.progress_bar(total=len(self.scheduler.timesteps))          # (PNDM evaluates the UNet more often than it has steps)
+        # the reference's loop holds the caller's callback back over the warm-up evaluations (:688, :770): PNDM's 1 (PLMS) or 9 (Runge-Kutta); 0 for every other scheduler
+        warmup = len(self.scheduler.timesteps) - num_inference_steps * self.scheduler.order
 
         def cb(i, t, lat):
             if hasattr(bar, "update"):
                 bar.update()
-            if callback is not None and i % callback_steps == 0:
+            if callback is not None and i % callback_steps == 0 and i >= warmup:
                 callback(i, t, lat)
 
         latents_out = sampler.sample(latents, text_embeddings, num_inference_steps, guidance_scale,

@@ -6,5 +6,6 @@ from .schedulers.scheduling_dpmsolver_multistep import DPMSolverMultistepSchedul
 from .schedulers.scheduling_euler_ancestral_discrete import EulerAncestralDiscreteScheduler  # noqa: F401,E402
 from .schedulers.scheduling_euler_discrete import EulerDiscreteScheduler  # noqa: F401,E402
 from .schedulers.scheduling_lms_discrete import LMSDiscreteScheduler  # noqa: F401,E402
+from .schedulers.scheduling_pndm import PNDMScheduler  # noqa: F401,E402
 from .models.unet_2d_condition import UNet2DConditionModel  # noqa: F401,E402
 from .pipelines.stable_diffusion import StableDiffusionPipeline  # noqa: F401,E402

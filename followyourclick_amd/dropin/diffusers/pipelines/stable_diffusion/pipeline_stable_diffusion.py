@@ -166,7 +166,8 @@ class StableDiffusionPipeline:
         if eta != 0.0:
             raise NotImplementedError("StableDiffusionPipeline on the MI355X engine: eta > 0 (stochastic DDIM) is not implemented")
         if not hasattr(self.scheduler, "engine_config"):
-            raise TypeError("scheduler must be the drop-in diffusers.DDIMScheduler or DPMSolverMultistepScheduler (the update runs as a fused HIP kernel)")
+            raise TypeError("scheduler must be one of the drop-in diffusers schedulers - DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, "
+                            "EulerAncestralDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler (the update runs as a fused HIP kernel)")
         batch_size = 1 if isinstance(prompt, str) else len(prompt)
         device = self._execution_device
         cfg_on = guidance_scale > 1.0
@@ -175,12 +176,14 @@ class StableDiffusionPipeline:
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.in_channels, height, width, text_embeddings.dtype,
                                        device, generator, latents)
         sampler = make_sampler(self.unet._get_engine(), self.scheduler.engine_config)
-        bar = self.progress_bar(total=num_inference_steps)
+        bar = self.progress_bar(total=len(self.scheduler.timesteps))          # (PNDM evaluates the UNet more often than it has steps)
+        # the reference's loop holds the caller's callback back over the warm-up evaluations (:521, :540): PNDM's 1 (PLMS) or 9 (Runge-Kutta); 0 for every other scheduler
+        warmup = len(self.scheduler.timesteps) - num_inference_steps * self.scheduler.order
 
         def cb(i, t, lat):
             if hasattr(bar, "update"):
                 bar.update()
-            if callback is not None and i % callback_steps == 0:
+            if callback is not None and i % callback_steps == 0 and i >= warmup:
                 callback(i, t, lat[:, :, 0])
 
         out = sampler.sample(latents[:, :, None], text_embeddings, num_inference_steps, guidance_scale, callback=cb)[:, :, 0]

@@ -1,2 +1,2 @@
 """Host-side engine: weight packing, UNet3D / VAE-decoder op schedules, DDIM tables, sampling loop."""
-from .config import DDIMConfig, SigmaConfig, SolverConfig, UNet3DConfig, VAEDecoderConfig  # noqa: F401
+from .config import DDIMConfig, PNDMConfig, SigmaConfig, SolverConfig, UNet3DConfig, VAEDecoderConfig  # noqa: F401

@@ -167,3 +167,20 @@ class SigmaConfig:
     trained_betas: object = None
     prediction_type: str = "epsilon"
     rescale_betas_zero_snr: bool = False
+
+
+@dataclass
+class PNDMConfig:
+    """PNDMScheduler.__init__ kwargs (reference diffusers/schedulers/scheduling_pndm.py:100-111) with the reference's defaults, plus
+    rescale_betas_zero_snr (an engine extension as in SolverConfig).  skip_prk_steps = True is the PLMS mode Stable Diffusion 1.x ships
+    (n + 1 evaluations of n steps); False, the class default, runs twelve Runge-Kutta evaluations first (n + 9 evaluations)."""
+    num_train_timesteps: int = 1000
+    beta_start: float = 0.0001
+    beta_end: float = 0.02
+    beta_schedule: str = "linear"
+    trained_betas: object = None
+    skip_prk_steps: bool = False
+    set_alpha_to_one: bool = False
+    prediction_type: str = "epsilon"
+    steps_offset: int = 0
+    rescale_betas_zero_snr: bool = False

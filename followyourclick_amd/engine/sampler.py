@@ -9,6 +9,7 @@ sync).  Everything that is constant over the loop (text/IP K/V, all time embeddi
 coefficients) is prepared once per clip.  SolverSampler is the same loop for a DPM-Solver multistep scheduler
 (the reference's loop is scheduler-agnostic): it shares the input build and the forward and differs in the schedule and the update kernel.
 SigmaSampler is the loop for the sigma-space schedulers (Euler, Euler ancestral, LMS): the input build also divides by sqrt(sigma^2 + 1).
+PNDMSampler is the loop for PNDM in its PLMS and Runge-Kutta modes: one pass per entry of its timestep list, n + 1 or n + 9 of them.
 """
 from __future__ import annotations
 
@@ -17,8 +18,8 @@ from typing import Callable, Optional, Sequence
 
 import torch
 
-from .config import DDIMConfig, SigmaConfig, SolverConfig
-from .scheduler import DDIMTables, SigmaTables, SolverTables
+from .config import DDIMConfig, PNDMConfig, SigmaConfig, SolverConfig
+from .scheduler import DDIMTables, PNDMTables, SigmaTables, SolverTables
 from .unet3d import UNet3DEngine
 from .weights import pad_channels
 
@@ -97,7 +98,7 @@ class DDIMSampler:
             idx = torch.arange(nf) % (2 * batch)
             u.prepare_context(text_embeddings[idx], None)
             _, temb_s = u.prepare_time_embeddings(ts.tolist(), None, None, nf)
-            extra = dict(ctx_single=u.ctx_cache, temb_single=temb_s.reshape(num_steps, nf, -1), video_scale=float(video_scale))
+            extra = dict(ctx_single=u.ctx_cache, temb_single=temb_s.reshape(len(ts), nf, -1), video_scale=float(video_scale))
         if first_frame_condition:
             # `use_first_frame_condition` (reference :691-692; unet.py:523-524): frame 0 of the latents is pinned to the clean
             # first-frame latents and every ResNet gives that frame the embedding of timestep 0
@@ -110,7 +111,8 @@ class DDIMSampler:
         emb, temb = u.prepare_time_embeddings(ts.tolist(), dup(fps), dup(flow), beff, camera=dup(camera))
         coef = coef_host.to(u.device)
         extra.update(sched)
-        return dict(timesteps=ts, temb=temb.reshape(num_steps, beff, -1), coef=coef, cfg=cfg_on, beff=beff,
+        # (one row per entry of the timestep list: PNDM evaluates the UNet more often than it has steps)
+        return dict(timesteps=ts, temb=temb.reshape(len(ts), beff, -1), coef=coef, cfg=cfg_on, beff=beff,
                     guidance=float(guidance_scale), steps=num_steps, batch=batch, ctx_main=u.ctx_cache,
                     guidance_rescale=guidance_rescale, **extra)
 
@@ -347,12 +349,67 @@ class SigmaSampler(DDIMSampler):
                               eta=1.0 if self.kind == "euler_ancestral" else 0.0, generator=generator, use_clipped_model_output=False, **kwargs)
 
 
+class PNDMSampler(DDIMSampler):
+    """The same loop with the PNDM scheduler (engine/scheduler.py::PNDMTables), PLMS mode (skip_prk_steps) or Runge-Kutta mode.  `prepare`
+    and `predict` are shared; the schedule is the reference's timestep list - n + 1 entries in PLMS mode, n + 9 in Runge-Kutta mode, one UNet
+    evaluation each: time embeddings, callbacks and the loop follow that list, not num_inference_steps -, the per-evaluation plan and the
+    table of collapsed coefficients; the update is ops.cfg_pndm_step.  The sampler owns four latent-shaped f32 history buffers of guided
+    predictions whose roles rotate by the plan, one buffer for the saved sample and one for the Runge-Kutta accumulator.  With
+    use_first_frame_condition `predict` pins frame 0 before the input build, so the saved sample is the pinned one, as in the reference.
+    Nothing is replayed from a captured graph; eta, generator and use_clipped_model_output are accepted and unused, as the reference's
+    prepare_extra_step_kwargs drops them for this scheduler; there is no clip_sample."""
+
+    def __init__(self, unet: UNet3DEngine, pndm: PNDMConfig):
+        self.unet = unet
+        self.tables = PNDMTables(pndm)
+        self.clip_sample = False
+
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
+        ts = self.tables.timesteps(num_steps)
+        coef_host = self.tables.coefficient_table(num_steps)          # (refuses a step at alphas_cumprod = 0 with the timestep named)
+        return ts, coef_host, dict(plan=self.tables.plan(num_steps), buffers={})
+
+    @torch.no_grad()
+    def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
+             variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
+             guidance_rescale: float = 0.0) -> None:
+        """evaluation i of the timestep list, latents (B,4,F,h,w) f32 updated in place; the evaluations of a clip are taken in order from
+        i = 0 (the histories, the saved sample and the accumulator are the state)"""
+        B, CL, F, H, W = latents.shape
+        phi = check_guidance_rescale(guidance_rescale)
+        if phi > 0 and not st["cfg"]:
+            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        buf = st["buffers"]
+        if "sample" not in buf or buf["sample"].shape != latents.shape or buf["sample"].device != latents.device:
+            buf.update(hist=[torch.empty_like(latents) for _ in range(4)], sample=torch.empty_like(latents), acc=torch.empty_like(latents))
+        ev = st["plan"][i]
+        slot = lambda s: buf["acc"] if s == "acc" else buf["hist"][s]      # noqa: E731
+        hists = [slot(s) for s in ev.hist] + [None] * (4 - ev.order)
+        pred, single = self.predict(st, i, latents, first_image_latents, mask)
+        self.unet.ops.cfg_pndm_step(pred, latents, st["coef"][i], sample_in=buf["sample"] if ev.sample_in else None,
+                                    sample_out=buf["sample"] if ev.sample_out else None,
+                                    hist_out=None if ev.hist_out is None else buf["hist"][ev.hist_out], hist_1=hists[0], hist_2=hists[1],
+                                    hist_3=hists[2], order=ev.order, acc_in=buf["acc"] if ev.acc_in else None,
+                                    acc_out=buf["acc"] if ev.acc_out else None, B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1],
+                                    cfg=st["cfg"], guidance=st["guidance"], pred_single=single, video_scale=st.get("video_scale", 0.0),
+                                    guidance_rescale=phi)
+
+    @torch.no_grad()
+    def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float, *args, use_graph: Optional[bool] = None,
+               eta: float = 0.0, generator=None, use_clipped_model_output: bool = False, **kwargs) -> Tensor:
+        return super().sample(latents, text_embeddings, num_steps, guidance_scale, *args, use_graph=False, eta=0.0, generator=None,
+                              use_clipped_model_output=False, **kwargs)
+
+
 def make_sampler(unet: UNet3DEngine, scheduler_config) -> DDIMSampler:
-    """the sampler of a scheduler's engine_config: SolverConfig -> SolverSampler, SigmaConfig -> SigmaSampler, DDIMConfig -> DDIMSampler"""
+    """the sampler of a scheduler's engine_config: SolverConfig -> SolverSampler, SigmaConfig -> SigmaSampler, PNDMConfig -> PNDMSampler,
+    DDIMConfig -> DDIMSampler"""
+    if isinstance(scheduler_config, PNDMConfig):
+        return PNDMSampler(unet, scheduler_config)
     if isinstance(scheduler_config, SolverConfig):
         return SolverSampler(unet, scheduler_config)
     if isinstance(scheduler_config, SigmaConfig):
         return SigmaSampler(unet, scheduler_config)
     if isinstance(scheduler_config, DDIMConfig):
         return DDIMSampler(unet, scheduler_config)
-    raise TypeError(f"no sampler for a scheduler config of type {type(scheduler_config).__name__} (DDIMConfig, SolverConfig or SigmaConfig)")
+    raise TypeError(f"no sampler for a scheduler config of type {type(scheduler_config).__name__} (DDIMConfig, SolverConfig, SigmaConfig or PNDMConfig)")

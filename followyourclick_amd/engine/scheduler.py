@@ -9,12 +9,13 @@ update itself is the fused guidance+DDIM kernel (fyc_cfg_ddim_step).
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import List
 
 import numpy as np
 import torch
 
-from .config import DDIMConfig, SigmaConfig, SolverConfig
+from .config import DDIMConfig, PNDMConfig, SigmaConfig, SolverConfig
 
 PRED_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 
@@ -369,4 +370,133 @@ class SigmaTables:
         tab = torch.tensor([self.step_coefficients(sig, i) for i in range(num_inference_steps)], dtype=torch.float64).float()
         if not torch.isfinite(tab).all():
             raise ValueError(f"the {self.cfg.kind} schedule of {num_inference_steps} steps has a non-finite coefficient (sigmas {sig.tolist()})")
+        return tab
+
+
+# one evaluation of a PNDM schedule: what _get_prev_sample sees (timestep, prev_timestep), the weights of the combined model output on
+# (g, h_1, h_2, h_3), which buffers the launch reads and writes.  hist: the slot of h_1 .. h_{order-1} - 0..3 a history buffer, "acc" the
+# Runge-Kutta accumulator; hist_out: the slot that receives g (None: not stored); s_g: the weight of g in the accumulator (0: none)
+PNDMEval = namedtuple("PNDMEval", ["counter", "timestep", "prev_timestep", "order", "weights", "hist", "hist_out", "sample_in", "sample_out",
+                                   "acc_in", "acc_out", "s_g"])
+PLMS_WEIGHTS = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}      # Adams-Bashforth (:323-335)
+
+
+class PNDMTables:
+    """PNDM on the host, PLMS mode (skip_prk_steps, what Stable Diffusion 1.x ships) and Runge-Kutta mode (reference diffusers/schedulers/
+    scheduling_pndm.py; arXiv:2202.09778).
+
+    The timestep list has n + 1 entries in PLMS mode (the second one repeated) and n + 9 in Runge-Kutta mode (twelve PRK evaluations on
+    half steps, then PLMS).  Some evaluations update not the latents they were handed but a sample saved earlier (PLMS: counter == 1; PRK:
+    the three later evaluations of each group of four), PRK sums e/6 + e/3 + e/3 + e/6 over a group, and the v-prediction conversion is
+    applied to the COMBINED model output with the current sample and timestep (:376-377) - so the history holds raw (guided) predictions.
+    All of it is linear, and an evaluation collapses to six numbers:
+
+        x' = c_x x_src + c_0 g + c_1 h_1 + c_2 h_2 + c_3 h_3,      acc' = acc + s_g g
+
+    with g the guided prediction, h_k the stored predictions (or the PRK accumulator) and x_src the latents or the saved sample.  Formula (9)
+    (_get_prev_sample, :358-399) gives x' = sc x - k m with sc = sqrt(a_prev / a_t), k = (a_prev - a_t) / (a_t sqrt(1 - a_prev) +
+    sqrt(a_t (1 - a_t) a_prev)); m = sum w_i h_i for epsilon prediction, sqrt(a_t) sum w_i h_i + sqrt(1 - a_t) x for v_prediction.  The
+    coefficients are collapsed in f64 from the f32 alphas_cumprod entries the reference indexes and rounded once each to f32; the update
+    itself is the fused guidance + step kernel (fyc_cfg_pndm_step)."""
+
+    PRK_EVALUATIONS = 12          # three groups of four on the schedule's first three steps (pndm_order = 4; :178-185)
+
+    def __init__(self, cfg: PNDMConfig):
+        self.cfg = cfg
+        n = cfg.num_train_timesteps
+        if cfg.trained_betas is not None:
+            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
+        elif cfg.beta_schedule == "linear":
+            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
+        elif cfg.beta_schedule == "scaled_linear":
+            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
+        else:
+            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for PNDMTables")
+        if cfg.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type given as {cfg.prediction_type} must be one of `epsilon` or `v_prediction`")
+        if cfg.rescale_betas_zero_snr:
+            betas = rescale_zero_terminal_snr(betas)
+        self.betas = betas
+        self.alphas = 1.0 - betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if cfg.set_alpha_to_one else self.alphas_cumprod[0]
+        self.pred_type = PRED_TYPES[cfg.prediction_type]
+
+    def split_timesteps(self, num_inference_steps: int):
+        """set_timesteps (:153-187) -> (prk_timesteps, plms_timesteps), numpy arrays as the reference keeps them.  steps_offset and
+        skip_prk_steps are read from the config at every call: the pipelines patch steps_offset after construction, as the reference's do."""
+        n, T = int(num_inference_steps), self.cfg.num_train_timesteps
+        if not 1 <= n <= T:
+            raise ValueError(f"num_inference_steps = {num_inference_steps} must lie in 1 .. {T}")
+        base = (np.arange(0, n) * (T // n)).round()
+        base += self.cfg.steps_offset
+        if self.cfg.skip_prk_steps:
+            return np.array([]), np.concatenate([base[:-1], base[-2:-1], base[-1:]])[::-1].copy()
+        if n < 4:       # the reference dies in a numpy broadcast (the last four timesteps against a tile of eight)
+            raise ValueError(f"num_inference_steps = {n}: the Runge-Kutta mode (skip_prk_steps=False) needs at least 4 inference steps")
+        prk = np.array(base[-4:]).repeat(2) + np.tile(np.array([0, T // n // 2]), 4)
+        return (prk[:-1].repeat(2)[1:-1])[::-1].copy(), base[:-3][::-1].copy()
+
+    def timesteps(self, num_inference_steps: int) -> torch.Tensor:
+        """[n + 1] (PLMS) or [n + 9] (Runge-Kutta) int64: one entry per UNet evaluation"""
+        return torch.from_numpy(np.concatenate(self.split_timesteps(num_inference_steps)).astype(np.int64))
+
+    def plan(self, num_inference_steps: int) -> List[PNDMEval]:
+        """the reference's state machine (step / step_prk / step_plms: counter, ets, cur_sample, cur_model_output) run over the timestep
+        list, with buffer slots in place of tensors.  Four history slots are enough: step_plms keeps ets[-3:] before it appends."""
+        ts = self.timesteps(num_inference_steps).tolist()
+        ratio = self.cfg.num_train_timesteps // int(num_inference_steps)
+        n_prk = 0 if self.cfg.skip_prk_steps else self.PRK_EVALUATIONS
+        ets, plan = [], []
+
+        def store():
+            ets.append(next(s for s in range(4) if s not in ets))
+            return ets[-1]
+        for counter, t in enumerate(ts):
+            if counter < n_prk:         # step_prk (:251-270): every evaluation of a group steps from the sample saved at its first one
+                prev_t, t_group, r = t - (0 if counter % 2 else ratio // 2), ts[counter // 4 * 4], counter % 4
+                if r == 0:
+                    ev = PNDMEval(counter, t_group, prev_t, 1, (1.0,), (), store(), False, True, False, True, 1 / 6)
+                elif r < 3:
+                    ev = PNDMEval(counter, t_group, prev_t, 1, (1.0,), (), None, True, False, True, True, 1 / 3)
+                else:                   # e' = acc + e / 6: the accumulator is the second term
+                    ev = PNDMEval(counter, t_group, prev_t, 2, (1 / 6, 1.0), ("acc",), None, True, False, False, False, 0.0)
+            elif counter == 1:          # step_plms (:316-329): the second evaluation redoes step 0 from the saved sample with (e + e_0) / 2
+                ev = PNDMEval(counter, t + ratio, t, 2, (0.5, 0.5), (ets[-1],), None, True, False, False, False, 0.0)
+            else:
+                del ets[:-3]
+                slot = store()
+                order = len(ets)
+                ev = PNDMEval(counter, t, t - ratio, order, PLMS_WEIGHTS[order], tuple(ets[-2::-1]), slot, False, counter == 0, False, False, 0.0)
+            plan.append(ev)
+        return plan
+
+    def check_step(self, t: int) -> None:
+        """formula (9) divides by alphas_cumprod[t]: a step where it is 0 (timestep T - 1 of a zero-terminal-SNR table; the reference goes on to
+        NaN) is refused, as is a timestep outside the table (a steps_offset that pushes the first step past it)"""
+        if not 0 <= t < len(self.alphas_cumprod):
+            raise ValueError(f"timestep {t} lies outside the {len(self.alphas_cumprod)} training timesteps (steps_offset = {self.cfg.steps_offset})")
+        if float(self.alphas_cumprod[t]) == 0.0:
+            raise ValueError(f"timestep {t}: alphas_cumprod is 0 there (zero terminal SNR) and PNDM's formula (9) divides by it; choose a "
+                             "schedule that does not start there (leading spacing with steps_offset = 1 never does)")
+
+    def step_coefficients(self, ev: PNDMEval) -> List[float]:
+        """{c_x, c_0, c_1, c_2, c_3, s_g} of one evaluation, in f64 from the f32 table entries"""
+        self.check_step(ev.timestep)
+        a_t = float(self.alphas_cumprod[ev.timestep])
+        a_p = float(self.alphas_cumprod[ev.prev_timestep] if ev.prev_timestep >= 0 else self.final_alpha_cumprod)
+        sc = (a_p / a_t) ** 0.5
+        k = (a_p - a_t) / (a_t * (1 - a_p) ** 0.5 + (a_t * (1 - a_t) * a_p) ** 0.5)
+        if self.cfg.prediction_type == "v_prediction":          # m = sqrt(a_t) e' + sqrt(1 - a_t) x
+            cx, w = sc - k * (1 - a_t) ** 0.5, -k * a_t ** 0.5
+        else:
+            cx, w = sc, -k
+        c = [w * wi for wi in ev.weights] + [0.0] * (4 - ev.order)
+        return [cx, *c, ev.s_g]
+
+    def coefficient_table(self, num_inference_steps: int) -> torch.Tensor:
+        """[evaluations][6] f32, each entry rounded once"""
+        tab = torch.tensor([self.step_coefficients(ev) for ev in self.plan(num_inference_steps)], dtype=torch.float64).float()
+        if not torch.isfinite(tab).all():
+            raise ValueError(f"the PNDM schedule of {num_inference_steps} steps has a non-finite coefficient")
         return tab

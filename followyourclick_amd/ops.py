@@ -684,6 +684,42 @@ class HipOps:
             a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
         self._call("fyc_cfg_sigma_step", a)
 
+    def cfg_pndm_step(self, pred: Tensor, latents: Tensor, coef: Tensor, *, sample_in: Optional[Tensor] = None, sample_out: Optional[Tensor] = None,
+                      hist_out: Optional[Tensor] = None, hist_1: Optional[Tensor] = None, hist_2: Optional[Tensor] = None,
+                      hist_3: Optional[Tensor] = None, order: int = 1, acc_in: Optional[Tensor] = None, acc_out: Optional[Tensor] = None,
+                      B: int, F: int, HW: int, c_latent: int, ld: int, cfg: bool, guidance: float, pred_single: Optional[Tensor] = None,
+                      video_scale: float = 0.0, guidance_rescale: float = 0.0) -> None:
+        """guidance + one PNDM evaluation, PLMS or Runge-Kutta mode (include/fyc.h, fyc_cfg_pndm_step): coef f32[6] = {c_x, c_0, c_1, c_2, c_3,
+        s_g}; latents are updated in place from sample_in (None = from themselves); sample_out (None = not stored) receives the latents as they
+        were, hist_out the guided prediction, acc_out = acc_in + s_g g (acc_in None = 0; acc_in may be acc_out); hist_k is the stored prediction
+        k places back (read only at order > k).  The moments workspace of the guidance rescale is the one cfg_ddim_step_rescaled keeps."""
+        self.ensure_init(pred.device)
+        if coef.numel() < 6:
+            raise ValueError(f"cfg_pndm_step: coef holds {coef.numel()} values, the kernel's table row has 6")
+        for name, h in (("sample_in", sample_in), ("sample_out", sample_out), ("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2),
+                        ("hist_3", hist_3), ("acc_in", acc_in), ("acc_out", acc_out)):
+            if h is not None and h.numel() != latents.numel():
+                raise ValueError(f"cfg_pndm_step: {name} must have the latents' shape")
+        if pred_single is not None and pred_single.dtype != pred.dtype:
+            raise TypeError("cfg_pndm_step: pred_single dtype differs from pred")
+        a = L.CfgPndmArgs()
+        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
+        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
+        a.pred_single, a.video_scale = _p(pred_single), video_scale
+        a.sample_in, a.sample_out = _f32(sample_in, "sample_in"), _f32(sample_out, "sample_out")
+        a.hist_out, a.hist_1, a.hist_2, a.hist_3 = _f32(hist_out, "hist_out"), _f32(hist_1, "hist_1"), _f32(hist_2, "hist_2"), _f32(hist_3, "hist_3")
+        a.order, a.acc_in, a.acc_out = int(order), _f32(acc_in, "acc_in"), _f32(acc_out, "acc_out")
+        a.guidance_rescale = float(guidance_rescale)
+        key = ("cfg_pndm", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg))
+        need = self._ws_need.get(key)
+        if need is None:
+            need = self._ws_need[key] = int(self.lib.fyc_cfg_pndm_workspace_bytes(C.byref(a)))
+        if need > 0:
+            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
+                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+            a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._call("fyc_cfg_pndm_step", a)
+
     def unet_input_scaled(self, latents: Tensor, mask: Optional[Tensor], first: Optional[Tensor], x: Tensor, *, denom: float, scale_cond: bool,
                           B: int, F: int, HW: int, c_latent: int, c_pad: int, cfg_dup: int, mask_frames: int = 1, mode: int = 0) -> None:
         """unet_input with every stored value divided by denom = sqrt(sigma^2 + 1) (include/fyc.h, fyc_unet_input_scaled); scale_cond: the mask

@@ -486,6 +486,36 @@ int fyc_cfg_sigma_step(const fyc_cfg_sigma_args* a, void* stream);
 typedef struct { fyc_unet_input_args base; float denom; int32_t scale_cond; } fyc_unet_input_scaled_args;
 int fyc_unet_input_scaled(const fyc_unet_input_scaled_args* a, void* stream);
 
+/* (308, added entry points) Classifier-free guidance + one evaluation of the PNDM scheduler in one pass, PLMS mode (skip_prk_steps) and
+ * Runge-Kutta mode alike (scheduling_pndm.py:223-343 step_prk / step_plms, :358-399 _get_prev_sample).  Every PNDM update is linear in a
+ * source sample, the guided prediction and up to three stored ones; the host folds the Adams-Bashforth weights, formula (9) and the
+ * v-prediction conversion of the COMBINED output into coef (device f32[6]) = {c_x, c_0, c_1, c_2, c_3, s_g}:
+ *   g  = the guided prediction exactly as fyc_cfg_ddim_step forms it; with guidance_rescale > 0 times the per-sample factor of
+ *        fyc_cfg_ddim_step_rescaled (the same moments and factor launches run in front: no atomics, the same call gives the same bits)
+ *   x  = sample_in[j] when sample_in is not NULL (the sample saved at an earlier evaluation; the latents are then not read), else latents[j]
+ *   x' = c_x x + c_0 g + c_1 hist_1 + c_2 hist_2 + c_3 hist_3                    (summed left to right), written to latents[j]
+ * All buffers but pred are (B,c_latent,F,h,w) f32.  hist_k is read only when order > k.  Optional stores, NULL = nothing stored:
+ *   sample_out[j] = latents[j] as it was before the update;  hist_out[j] = g;  acc_out[j] = (acc_in ? acc_in[j] : 0) + s_g g
+ * (the running combination of the Runge-Kutta mode; acc_in NULL is not read).  A buffer the call does not use may be NULL or
+ * uninitialised (NaN included) without reaching a result.  pred, pred_single, cfg, guidance, video_scale, ld, dtype: as in
+ * fyc_cfg_ddim_args.  Refused before anything is launched: everything fyc_cfg_sigma_step refuses of pointers, dims, dtype, order,
+ * pred_single without cfg, guidance_rescale and its workspace; sample_in overlapping the latents; sample_out, hist_out or acc_out
+ * overlapping the latents, a history, sample_in, acc_in or each other - except acc_out == acc_in, the one alias allowed.  Needs fyc_init().
+ * Workspace: fyc_cfg_pndm_workspace_bytes() bytes, 8-byte aligned; 0 = none needed. */
+typedef struct {
+  const void* pred; float* latents; const float* coef;
+  int32_t B, F, HW, c_latent, ld, cfg; float guidance;
+  int32_t dtype;
+  const void* pred_single; float video_scale;
+  const float* sample_in; float* sample_out;
+  float* hist_out; const float* hist_1; const float* hist_2; const float* hist_3;
+  int32_t order;
+  const float* acc_in; float* acc_out;
+  float guidance_rescale; void* workspace; int64_t workspace_bytes;
+} fyc_cfg_pndm_args;
+int64_t fyc_cfg_pndm_workspace_bytes(const fyc_cfg_pndm_args* a);
+int fyc_cfg_pndm_step(const fyc_cfg_pndm_args* a, void* stream);
+
 /* VAE ends: z (N,4,h,w) f32 * scale -> channels-last [N][hw][c_pad];
  * image channels-last [N][HW][ld] -> (N,3,H,W) f32 = clamp(x/2+0.5, 0, 1) (pipeline_animation.py:402,410) */
 typedef struct { const float* z; void* x; int32_t N, C, HW, c_pad; float scale; int32_t dtype; } fyc_nchw_in_args;
