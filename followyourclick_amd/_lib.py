@@ -146,7 +146,21 @@ class CfgPndmArgs(C.Structure):      # (308, added entry points) fyc_cfg_pndm_st
                 ("guidance_rescale", f32), ("workspace", vp), ("workspace_bytes", i64)]
 
 
-class UnetInputScaledArgs(C.Structure):      # (308, added entry points) fyc_unet_input_scaled: the input build's arguments as they are, the divisor behind them
+class PosteriorLatentsArgs(C.Structure):      # (308, added entry points) fyc_posterior_latents: VAE moments -> noised start latents
+    _fields_ = [("moments", vp), ("noise_post", vp), ("noise_add", vp), ("latents", vp), ("clean_out", vp),
+                ("N", i32), ("C", i32), ("HW", i32), ("scale", f32), ("c_x", f32), ("c_n", f32)]
+
+
+class InpaintPrepareArgs(C.Structure):      # (308, added entry points) fyc_inpaint_prepare: masked image + latent-size mask
+    _fields_ = [("image", vp), ("mask", vp), ("masked", vp), ("mask_latent", vp), ("N", i32), ("H", i32), ("W", i32)]
+
+
+class RenoiseBlendArgs(C.Structure):      # (308, added entry points) fyc_renoise_blend: the legacy inpainting loop's blend with the re-noised original
+    _fields_ = [("latents", vp), ("orig", vp), ("noise", vp), ("mask", vp),
+                ("B", i32), ("C", i32), ("F", i32), ("HW", i32), ("src_frames", i32), ("c_x", f32), ("c_n", f32)]
+
+
+class UnetInputScaledArgs(C.Structure):     # (308, added entry points) fyc_unet_input_scaled: the input build's arguments as they are, the divisor behind them
     _fields_ = [("base", UnetInputArgs), ("denom", f32), ("scale_cond", i32)]
 
 
@@ -206,6 +220,7 @@ OPS = {
     "fyc_ff_block": FFBlockArgs, "fyc_panel_linear": PanelLinearArgs, "fyc_repeat": RepeatArgs,
     "fyc_conv_up_phases": ConvUpPhasesArgs, "fyc_cfg_sigma_step": CfgSigmaArgs, "fyc_unet_input_scaled": UnetInputScaledArgs,
     "fyc_cfg_pndm_step": CfgPndmArgs,
+    "fyc_posterior_latents": PosteriorLatentsArgs, "fyc_inpaint_prepare": InpaintPrepareArgs, "fyc_renoise_blend": RenoiseBlendArgs,
 }
 MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set_tuning", "fyc_gemm_row_parts", "fyc_gemm_stat_layout", "fyc_gemm_workspace_bytes", "fyc_gn_stats_workspace", "fyc_temporal_block_supported", "fyc_temporal_block_wstream_bytes",
         "fyc_ff_block_supported", "fyc_ff_block_wstream_bytes", "fyc_panel_linear_supported", "fyc_panel_linear_wstream_bytes",

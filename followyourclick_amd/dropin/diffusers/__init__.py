@@ -9,3 +9,4 @@ from .schedulers.scheduling_lms_discrete import LMSDiscreteScheduler  # noqa: F4
 from .schedulers.scheduling_pndm import PNDMScheduler  # noqa: F401,E402
 from .models.unet_2d_condition import UNet2DConditionModel  # noqa: F401,E402
 from .pipelines.stable_diffusion import StableDiffusionPipeline  # noqa: F401,E402
+from .pipelines.stable_diffusion import StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionInpaintPipelineLegacy  # noqa: F401,E402

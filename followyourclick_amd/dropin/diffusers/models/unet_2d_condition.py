@@ -48,6 +48,12 @@ class UNet2DConditionModel(UNet3DConditionModel):
         if only_cross_attention or downsample_padding != 1 or mid_block_scale_factor != 1:
             raise NotImplementedError("only_cross_attention / non-default downsample_padding, mid_block_scale_factor")
         kw3 = dict(cfg2d, down_block_types=tuple(down3), up_block_types=tuple(up3), mid_block_type=mid3)
+        # a Stable Diffusion inpainting UNet (in_channels = 9 = latents | mask | masked-image latents): the engine's mask + first-frame concat
+        # layout on a one-frame clip has the same channel order (fyc_unet_input mode 0), so it is an engine with out_channels latent channels
+        # and that concat; conv_in.weight keeps its (320, 9, 3, 3) and `.config.in_channels` its 9
+        concat = in_channels == 2 * out_channels + 1
+        if concat:
+            kw3.update(in_channels=out_channels, use_first_frame_mask_condition_concat=True)
         super().__init__(**kw3, use_motion_module=False, compute_dtype=compute_dtype)
         for k, v in cfg2d.items():          # `.config` and attributes show the 2-D constructor arguments
             setattr(self, k, v)

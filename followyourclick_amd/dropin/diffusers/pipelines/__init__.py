@@ -1,1 +1,2 @@
-from .stable_diffusion import StableDiffusionPipeline  # noqa: F401
+from .stable_diffusion import (StableDiffusionImg2ImgPipeline, StableDiffusionInpaintPipeline, StableDiffusionInpaintPipelineLegacy,  # noqa: F401
+                               StableDiffusionPipeline)

@@ -163,11 +163,7 @@ class StableDiffusionPipeline:
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
-        if eta != 0.0:
-            raise NotImplementedError("StableDiffusionPipeline on the MI355X engine: eta > 0 (stochastic DDIM) is not implemented")
-        if not hasattr(self.scheduler, "engine_config"):
-            raise TypeError("scheduler must be one of the drop-in diffusers schedulers - DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, "
-                            "EulerAncestralDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler (the update runs as a fused HIP kernel)")
+        self.check_scheduler()
         batch_size = 1 if isinstance(prompt, str) else len(prompt)
         device = self._execution_device
         cfg_on = guidance_scale > 1.0
@@ -175,21 +171,51 @@ class StableDiffusionPipeline:
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.in_channels, height, width, text_embeddings.dtype,
                                        device, generator, latents)
+        # eta reaches the DDIM sampler (its per-step noise comes from `generator`); the other samplers drop it, as the reference's
+        # prepare_extra_step_kwargs does.  eta = 0 is the call it always was
+        extra = dict(eta=float(eta), generator=generator) if eta != 0.0 else {}
+        out = self.run_sampler(latents, text_embeddings, num_inference_steps, guidance_scale, callback, callback_steps, **extra)
+        return self.finish(out, output_type, return_dict)
+
+    def check_scheduler(self) -> None:
+        if not hasattr(self.scheduler, "engine_config"):
+            raise TypeError("scheduler must be one of the drop-in diffusers schedulers - DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, "
+                            "EulerAncestralDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler (the update runs as a fused HIP kernel)")
+
+    def run_sampler(self, latents, text_embeddings, num_inference_steps, guidance_scale, callback, callback_steps, start_index: int = 0, **kwargs):
+        """the denoising loop of all 2-D pipelines: (N, 4, h, w) latents in -> out, on the engine's sampler for self.scheduler.  start_index:
+        the first entry of the scheduler's timestep list (img2img / legacy inpainting `strength`); kwargs go to the sampler's `sample`"""
         sampler = make_sampler(self.unet._get_engine(), self.scheduler.engine_config)
-        bar = self.progress_bar(total=len(self.scheduler.timesteps))          # (PNDM evaluates the UNet more often than it has steps)
+        entries = len(self.scheduler.timesteps) - start_index
+        bar = self.progress_bar(total=entries)          # (PNDM evaluates the UNet more often than it has steps)
         # the reference's loop holds the caller's callback back over the warm-up evaluations (:521, :540): PNDM's 1 (PLMS) or 9 (Runge-Kutta); 0 for every other scheduler
-        warmup = len(self.scheduler.timesteps) - num_inference_steps * self.scheduler.order
+        warmup = entries - (num_inference_steps - start_index) * self.scheduler.order
+        if start_index:
+            kwargs["start_index"] = start_index
+        # the reference's EulerDiscreteScheduler.step draws its churn noise from the caller's generator at every step, used or not (gamma = 0 here:
+        # never used); the editing pipelines draw and drop it too, so that a generator shared with other code advances as it does there
+        idle_draw = kwargs.pop("idle_step_noise", None)          # (a torch.Generator or None)
+        if getattr(self.scheduler, "kind", None) != "euler" or not isinstance(idle_draw, torch.Generator):
+            idle_draw = None
 
         def cb(i, t, lat):
+            if idle_draw is not None:
+                torch.randn(lat[:, :, 0].shape, generator=idle_draw, device=idle_draw.device, dtype=lat.dtype)
             if hasattr(bar, "update"):
                 bar.update()
             if callback is not None and i % callback_steps == 0 and i >= warmup:
                 callback(i, t, lat[:, :, 0])
 
-        out = sampler.sample(latents[:, :, None], text_embeddings, num_inference_steps, guidance_scale, callback=cb)[:, :, 0]
+        for key in ("first_image_latents", "first_images_mask"):
+            if kwargs.get(key) is not None:
+                kwargs[key] = kwargs[key][:, :, None]
+        out = sampler.sample(latents[:, :, None], text_embeddings, num_inference_steps, guidance_scale, callback=cb, **kwargs)[:, :, 0]
         if hasattr(bar, "close"):
             bar.close()
-        image = self.decode_latents(out)
+        return out
+
+    def finish(self, latents, output_type, return_dict):
+        image = self.decode_latents(latents)
         if output_type == "pil":
             image = self.numpy_to_pil(image)
         if not return_dict:

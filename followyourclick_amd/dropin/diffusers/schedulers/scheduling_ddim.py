@@ -95,3 +95,9 @@ class DDIMScheduler:
         if not return_dict:
             return (prev,)
         return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """x_t = sqrt(abar_t) x_0 + sqrt(1 - abar_t) noise (reference scheduling_ddim.py:378-399)"""
+        abar = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)[timesteps.to(original_samples.device)]
+        shape = (-1,) + (1,) * (original_samples.dim() - 1)
+        return (abar ** 0.5).reshape(shape) * original_samples + ((1 - abar) ** 0.5).reshape(shape) * noise

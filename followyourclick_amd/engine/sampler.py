@@ -10,6 +10,8 @@ coefficients) is prepared once per clip.  SolverSampler is the same loop for a D
 (the reference's loop is scheduler-agnostic): it shares the input build and the forward and differs in the schedule and the update kernel.
 SigmaSampler is the loop for the sigma-space schedulers (Euler, Euler ancestral, LMS): the input build also divides by sqrt(sigma^2 + 1).
 PNDMSampler is the loop for PNDM in its PLMS and Runge-Kutta modes: one pass per entry of its timestep list, n + 1 or n + 9 of them.
+All four start part-way on request (`sample(start_index=k)`: the img2img / legacy inpainting `strength`, reference
+pipeline_stable_diffusion_img2img.py:393-400) and re-impose a known region after every step (`blend=`: ops.renoise_blend, the legacy inpainting loop).
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from .config import DDIMConfig, PNDMConfig, SigmaConfig, SolverConfig
-from .scheduler import DDIMTables, PNDMTables, SigmaTables, SolverTables
+from .scheduler import DDIMTables, PNDMTables, SigmaTables, SolverTables, check_start_index
 from .unet3d import UNet3DEngine
 from .weights import pad_channels
 
@@ -52,12 +54,15 @@ class DDIMSampler:
         self.tables = DDIMTables(ddim)
         self.clip_sample = bool(ddim.clip_sample)
 
-    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
-        """-> (timesteps, the host coefficient table [n][.] f32, further per-clip entries of the state `prepare` returns)"""
-        ts = self.tables.timesteps(num_steps)
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool, start_index: int = 0):
+        """-> (timesteps, the host coefficient table [n][.] f32, further per-clip entries of the state `prepare` returns).  start_index = k > 0:
+        entries k .. of the scheduler's timestep list and their rows - what the reference's img2img / legacy inpainting loops hand a scheduler
+        whose state starts from zero (`strength`); every sampler's schedule follows its own scheduler class there"""
+        k = check_start_index(start_index, num_steps)
+        ts = self.tables.timesteps(num_steps)[k:]
         for t in ts.tolist():           # a step at abar_t = 0 (trailing spacing on a zero-SNR table) that would divide by it
             self.tables.check_step(t, use_clipped_model_output)
-        coef_host = self.tables.coefficient_table(num_steps, eta)
+        coef_host = self.tables.coefficient_table(num_steps, eta)[k:]
         return ts, coef_host, dict(sigma=coef_host[:, 4].tolist())           # eta > 0: per-step std of the added noise (0 for eta = 0)
 
     @torch.no_grad()
@@ -65,8 +70,9 @@ class DDIMSampler:
                 fps: Optional[Sequence[float]] = None, flow: Optional[Sequence[float]] = None,
                 ip_tokens: Optional[Tensor] = None, video_scale: float = 0.0, frames: int = 0,
                 first_frame_condition: bool = False, eta: float = 0.0, camera: Optional[Sequence[float]] = None,
-                guidance_rescale: float = 0.0, use_clipped_model_output: bool = False) -> dict:
+                guidance_rescale: float = 0.0, use_clipped_model_output: bool = False, start_index: int = 0) -> dict:
         """text_embeddings: (cfg*batch, 77, D) with the unconditional half first (reference :397).
+        start_index: the first entry of the timestep list this run takes (`schedule`); the state's rows are those of the entries taken.
         guidance_rescale (0 = off .. 1) is checked here and handed to every `step` by `sample`: the guided prediction of every sample is rescaled
         towards the standard deviation of its conditional one (ops.cfg_ddim_step_rescaled); it needs classifier-free guidance.  use_clipped_model_output is only checked here, against the schedule."""
         u = self.unet
@@ -78,7 +84,7 @@ class DDIMSampler:
         beff = batch * (2 if cfg_on else 1)
         if text_embeddings.shape[0] != beff:
             raise ValueError(f"text_embeddings batch {text_embeddings.shape[0]} != {beff}")
-        ts, coef_host, sched = self.schedule(num_steps, eta, use_clipped_model_output)
+        ts, coef_host, sched = self.schedule(num_steps, eta, use_clipped_model_output, start_index)
 
         def dup(v):
             if v is None:
@@ -114,7 +120,7 @@ class DDIMSampler:
         # (one row per entry of the timestep list: PNDM evaluates the UNet more often than it has steps)
         return dict(timesteps=ts, temb=temb.reshape(len(ts), beff, -1), coef=coef, cfg=cfg_on, beff=beff,
                     guidance=float(guidance_scale), steps=num_steps, batch=batch, ctx_main=u.ctx_cache,
-                    guidance_rescale=guidance_rescale, **extra)
+                    guidance_rescale=guidance_rescale, start_index=int(start_index), **extra)
 
     @torch.no_grad()
     def predict(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
@@ -148,8 +154,9 @@ class DDIMSampler:
             if input_denom is None:
                 o.unet_input(latents, mask, first_image_latents, x, B=B, F=F, HW=H * W, c_latent=CL, c_pad=cp, cfg_dup=dupx,
                              mask_frames=1)
-            else:       # the reference scales the concatenated tensor (pipeline_animation.py:708-712): mask and first-frame block too
-                o.unet_input_scaled(latents, mask, first_image_latents, x, denom=input_denom, scale_cond=True, B=B, F=F, HW=H * W,
+            else:       # the reference scales the concatenated tensor (pipeline_animation.py:708-712): mask and first-frame block too;
+                # the 2-D inpainting pipeline scales the latents before the concat (scale_condition = False)
+                o.unet_input_scaled(latents, mask, first_image_latents, x, denom=input_denom, scale_cond=st.get("scale_condition", True), B=B, F=F, HW=H * W,
                                     c_latent=CL, c_pad=cp, cfg_dup=dupx, mask_frames=1)
         else:
             # plain latents (the 2-D Stable Diffusion first-image path, reference pipeline_stable_diffusion.py:527-528)
@@ -199,11 +206,19 @@ class DDIMSampler:
                ip_tokens: Optional[Tensor] = None, callback: Optional[Callable] = None, callback_steps: int = 1,
                use_graph: Optional[bool] = None, video_scale: float = 0.0, first_frame_condition: bool = False,
                eta: float = 0.0, generator=None, use_clipped_model_output: bool = False,
-               camera: Optional[Sequence[float]] = None, guidance_rescale: float = 0.0) -> Tensor:
+               camera: Optional[Sequence[float]] = None, guidance_rescale: float = 0.0, start_index: int = 0,
+               blend: Optional[Sequence[Tensor]] = None, scale_condition: bool = True) -> Tensor:
         """use_graph: replay steps 1..n-1 from one captured hipGraph (None = the FYC_HIPGRAPH environment switch, default off).
         Measured on MI355X it buys nothing: at cfg2 the loop is GPU-bound (56 ms of kernels per step) and even the 2-D
         one-frame case (13.7 ms / step, ~700 small kernels) is bound by the kernels' own execution, not by launch overhead
-        (profiles/r01_front_end_rows.json).  Kept as an option for hosts with slow Python."""
+        (profiles/r01_front_end_rows.json).  Kept as an option for hosts with slow Python.
+        start_index = k: entries k .. of the timestep list (`strength` of the img2img / legacy inpainting pipelines); the latents are the
+        noised start latents of entry k as they are.  blend = (orig, noise, mask): after the step kernel of every entry the known region is
+        re-imposed, latents = (c_x orig + c_n noise) mask + latents (1 - mask) (ops.renoise_blend) with (c_x, c_n) the add_noise
+        coefficients of that entry's own timestep (reference pipeline_stable_diffusion_inpaint_legacy.py:573-575); orig and noise
+        (B, C, h, w) or the latents' shape, mask (B, 1, h, w) or (B, C, h, w) with equal channels.  Either one runs the eager loop.
+        scale_condition = False: a sigma-space scheduler's divisor reaches the latents only, not the mask and image channels of the concat
+        input (the 2-D inpainting pipeline scales before it concatenates, pipeline_stable_diffusion_inpaint.py:699-703)."""
         u = self.unet
         latents = latents.to(device=u.device, dtype=torch.float32).contiguous().clone()
         B, CL, F, H, W = latents.shape
@@ -214,20 +229,39 @@ class DDIMSampler:
             mask = first_images_mask.to(u.device, torch.float32)[:, :, 0].reshape(B, 1, H * W).contiguous()
         st = self.prepare(text_embeddings, num_steps, B, guidance_scale, fps, flow, ip_tokens, video_scale=video_scale, frames=F,
                           first_frame_condition=first_frame_condition, eta=eta, camera=camera, guidance_rescale=guidance_rescale,
-                          use_clipped_model_output=use_clipped_model_output)
+                          use_clipped_model_output=use_clipped_model_output, start_index=start_index)
+        if not scale_condition:
+            st["scale_condition"] = False
         ts, phi = st["timesteps"].tolist(), st["guidance_rescale"]
         if use_graph is None:
             use_graph = os.environ.get("FYC_HIPGRAPH", "0") == "1"
         if eta > 0:
             use_graph = False             # the noise of every step comes from the generator: nothing to replay
+        blend_co = None
+        if blend is not None:
+            orig, bnoise, bmask = blend
+            orig, bnoise = [t.to(u.device, torch.float32).reshape(B, CL, -1, H * W).contiguous() for t in (orig, bnoise)]
+            if orig.shape != bnoise.shape or orig.shape[2] not in (1, F):
+                raise ValueError(f"blend: orig {tuple(blend[0].shape)} and noise {tuple(blend[1].shape)} must be (B, C, h, w) or the latents' shape")
+            bmask = bmask.to(u.device, torch.float32).reshape(B, -1, H * W)
+            if bmask.shape[1] > 1 and not bool((bmask == bmask[:, :1]).all()):
+                raise ValueError("blend: the mask's channels differ; the kernel broadcasts one mask over the channels")
+            bmask = bmask[:, :1].contiguous()
+            blend_co = [self.tables.add_noise_coefficients(t, num_steps) for t in ts]
+        if start_index > 0 or blend is not None:
+            use_graph = False             # a sliced or blended run is the eager loop
         if not (use_graph and latents.is_cuda and num_steps >= 3):
             for i, t in enumerate(ts):
                 noise = None
                 if eta > 0:
                     # drawn exactly as the reference's scheduler draws it (scheduling_ddim.py:355-361): on the latents' device, in
-                    # their dtype, from the caller's generator (or the device's global one)
-                    noise = torch.randn(latents.shape, generator=generator, device=latents.device, dtype=latents.dtype)
+                    # their dtype, from the caller's generator (or the device's global one); a generator of another device (a seeded CPU
+                    # one beside latents on the GPU, which the reference's call refuses) draws on its own device
+                    gdev = latents.device if generator is None else generator.device
+                    noise = torch.randn(latents.shape, generator=generator, device=gdev, dtype=latents.dtype).to(latents.device)
                 self.step(st, i, latents, first, mask, variance_noise=noise, use_clipped_model_output=use_clipped_model_output, guidance_rescale=phi)
+                if blend_co is not None:
+                    u.ops.renoise_blend(latents, orig, bnoise, bmask, c_x=blend_co[i][0], c_n=blend_co[i][1], B=B, C_=CL, F=F, HW=H * W)
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, latents)
             return latents
@@ -265,10 +299,11 @@ class SolverSampler(DDIMSampler):
         self.tables = SolverTables(solver)
         self.clip_sample = False
 
-    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
-        ts = self.tables.timesteps(num_steps)
-        coef_host = self.tables.coefficient_table(num_steps)          # (checks every step: a zero-SNR first step the family cannot take)
-        return ts, coef_host, dict(orders=self.tables.plan(num_steps), hist=[])
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool, start_index: int = 0):
+        k = check_start_index(start_index, num_steps)
+        ts = self.tables.timesteps(num_steps)[k:]
+        coef_host = self.tables.coefficient_table(num_steps, k)          # (checks every step: a zero-SNR first step the family cannot take)
+        return ts, coef_host, dict(orders=self.tables.plan(num_steps, k), hist=[])
 
     @torch.no_grad()
     def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
@@ -311,11 +346,12 @@ class SigmaSampler(DDIMSampler):
         self.clip_sample = False
         self.kind = sigma.kind
 
-    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
-        ts = self.tables.timesteps(num_steps)
-        coef_host = self.tables.coefficient_table(num_steps)          # (refuses a schedule over an infinite sigma)
-        return ts, coef_host, dict(orders=[self.tables.order(i) for i in range(num_steps)], hist=[],
-                                   input_denom=self.tables.input_denominators(num_steps))
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool, start_index: int = 0):
+        k = check_start_index(start_index, num_steps)
+        ts = self.tables.timesteps(num_steps)[k:]
+        coef_host = self.tables.coefficient_table(num_steps, k)          # (refuses a schedule over an infinite sigma)
+        # (a sliced LMS run: the order of the step's place in the list, cut to the derivatives stored since entry k - SigmaTables.plan)
+        return ts, coef_host, dict(orders=self.tables.plan(num_steps, k), hist=[], input_denom=self.tables.input_denominators(num_steps)[k:])
 
     @torch.no_grad()
     def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
@@ -364,10 +400,11 @@ class PNDMSampler(DDIMSampler):
         self.tables = PNDMTables(pndm)
         self.clip_sample = False
 
-    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool):
-        ts = self.tables.timesteps(num_steps)
-        coef_host = self.tables.coefficient_table(num_steps)          # (refuses a step at alphas_cumprod = 0 with the timestep named)
-        return ts, coef_host, dict(plan=self.tables.plan(num_steps), buffers={})
+    def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool, start_index: int = 0):
+        plan = self.tables.plan(num_steps, start_index)               # (refuses a start part-way in Runge-Kutta mode)
+        ts = self.tables.timesteps(num_steps)[start_index:]
+        coef_host = self.tables.coefficient_table(num_steps, start_index)          # (refuses a step at alphas_cumprod = 0 with the timestep named)
+        return ts, coef_host, dict(plan=plan, buffers={})
 
     @torch.no_grad()
     def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],

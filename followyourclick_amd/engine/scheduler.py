@@ -31,6 +31,24 @@ def rescale_zero_terminal_snr(betas: torch.Tensor) -> torch.Tensor:
     return 1 - alphas
 
 
+def alpha_add_noise_coefficients(alphas_cumprod: torch.Tensor, t) -> tuple:
+    """(sqrt(abar_t), sqrt(1 - abar_t)) as the reference's add_noise forms them (scheduling_ddim.py:388-393): f32 tensor arithmetic on the
+    table entry -> python floats holding those f32 values"""
+    t = int(t)
+    if not 0 <= t < len(alphas_cumprod):
+        raise ValueError(f"timestep {t} lies outside the {len(alphas_cumprod)} training timesteps")
+    a_t = alphas_cumprod[t]
+    return float(a_t ** 0.5), float((1 - a_t) ** 0.5)
+
+
+def check_start_index(start_index, entries: int) -> int:
+    """the first entry of the scheduler's timestep list a sliced run takes (what `strength` selects): 0 .. entries - 1"""
+    k = int(start_index)
+    if not 0 <= k < entries:
+        raise ValueError(f"start_index = {start_index} leaves no step of a schedule of {entries} entries (0 .. {entries - 1})")
+    return k
+
+
 class DDIMTables:
     def __init__(self, cfg: DDIMConfig):
         self.cfg = cfg
@@ -101,6 +119,10 @@ class DDIMTables:
         ts = self.timesteps(num_inference_steps).tolist()
         return torch.tensor([self.step_coefficients(t, num_inference_steps, eta) for t in ts], dtype=torch.float32)
 
+    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
+        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
+        return alpha_add_noise_coefficients(self.alphas_cumprod, t)
+
 
 class SolverTables:
     """DPM-Solver multistep on the host (reference diffusers/schedulers/scheduling_dpmsolver_multistep.py; arXiv:2206.00927, arXiv:2211.01095).
@@ -167,10 +189,12 @@ class SolverTables:
             return 2
         return 3
 
-    def plan(self, num_inference_steps: int) -> List[int]:
-        """per step, the order actually used: the warm-up from first order and the lower-order final steps of a schedule shorter than 15"""
+    def plan(self, num_inference_steps: int, start_index: int = 0) -> List[int]:
+        """per step, the order actually used: the warm-up from first order and the lower-order final steps of a schedule shorter than 15.
+        start_index > 0: the steps start_index .. n - 1 of a sliced run - the warm-up starts over (the scheduler's history is empty), the
+        lower-order final steps are found by the place in the full list, as the reference's step() finds them"""
         orders, low = [], 0
-        for i in range(num_inference_steps):
+        for i in range(check_start_index(start_index, num_inference_steps), num_inference_steps):
             orders.append(self.next_order(i, num_inference_steps, low))
             low = min(low + 1, self.cfg.solver_order)
         return orders
@@ -244,12 +268,17 @@ class SolverTables:
             c0, c1, c2 = c0 + g0, g1 - g0, -g1
         return [*self.convert_coefficients(ts[i]), s["cx"], c0, c1, c2, 0.0, 0.0]
 
-    def coefficient_table(self, num_inference_steps: int) -> torch.Tensor:
-        """[n][8] f32, each entry rounded once, for the orders of plan(n)"""
+    def coefficient_table(self, num_inference_steps: int, start_index: int = 0) -> torch.Tensor:
+        """[n - start_index][8] f32, each entry rounded once, for the orders of plan(n, start_index)"""
         ts = self.timesteps(num_inference_steps).tolist()
-        for t in ts:
+        for t in ts[start_index:]:
             self.check_step(t)
-        return torch.tensor([self.step_coefficients(ts, i, o) for i, o in enumerate(self.plan(num_inference_steps))], dtype=torch.float64).float()
+        return torch.tensor([self.step_coefficients(ts, start_index + j, o) for j, o in enumerate(self.plan(num_inference_steps, start_index))],
+                            dtype=torch.float64).float()
+
+    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
+        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
+        return alpha_add_noise_coefficients(self.alphas_cumprod, t)
 
 
 SIGMA_KINDS = ("euler", "euler_ancestral", "lms")
@@ -341,11 +370,15 @@ class SigmaTables:
             out.append(float(Poly.polyval(h, Poly.polyint(p))))
         return out
 
-    def step_coefficients(self, sigmas: torch.Tensor, i: int, order: int = None) -> List[float]:
+    def step_coefficients(self, sigmas: torch.Tensor, i: int, order: int = None, stored: int = None) -> List[float]:
         """{a_x, a_v, c_x, c_0, c_1, c_2, c_3, c_n} of step i of the schedule `sigmas` ([n + 1] f32), in f64.  order: how many derivatives an LMS
-        step uses (None = self.order(i))"""
+        step uses (None = self.order(i)).  stored (None = order): how many derivatives the scheduler holds at that step - fewer than `order` in
+        a run that starts at a later entry of the list: the reference takes its order from the step's place in the list, integrates the
+        Lagrange basis of that order and zips the coefficients with the derivatives it has, which drops the last ones (scheduling_lms_discrete.py
+        :239-248)"""
         kind = self.cfg.kind
         order = self.order(i) if order is None else order
+        stored = order if stored is None else min(int(stored), order)
         sg, sg_to = sigmas[i], sigmas[i + 1]                # 0-dim f32 tensors: the reference's operands
         s = float(sg)
         if self.cfg.prediction_type == "epsilon":           # x0 = x - s v: d = v
@@ -361,16 +394,33 @@ class SigmaTables:
             sigma_down = (sg_to ** 2 - sigma_up ** 2) ** 0.5
             c[0], cn = float(sigma_down - sg), float(sigma_up)
         else:
-            c[:order] = self.lms_coefficients(sigmas, i, order)
+            c[:stored] = self.lms_coefficients(sigmas, i, order)[:stored]
         return [ax, av, 1.0, *c, cn]
 
-    def coefficient_table(self, num_inference_steps: int) -> torch.Tensor:
-        """[n][8] f32, each entry rounded once"""
+    def plan(self, num_inference_steps: int, start_index: int = 0) -> List[int]:
+        """per step of a run over the entries start_index .. n - 1, how many derivatives the update reads: 1 for the Euler samplers; for LMS
+        the order of the step's place in the list, cut to the derivatives stored since the run began"""
+        k = check_start_index(start_index, num_inference_steps)
+        return [min(self.order(i), i - k + 1) for i in range(k, num_inference_steps)]
+
+    def coefficient_table(self, num_inference_steps: int, start_index: int = 0) -> torch.Tensor:
+        """[n - start_index][8] f32, each entry rounded once"""
         sig = self.sigmas(num_inference_steps)
-        tab = torch.tensor([self.step_coefficients(sig, i) for i in range(num_inference_steps)], dtype=torch.float64).float()
+        k = check_start_index(start_index, num_inference_steps)
+        tab = torch.tensor([self.step_coefficients(sig, i, stored=i - k + 1) for i in range(k, num_inference_steps)], dtype=torch.float64).float()
         if not torch.isfinite(tab).all():
             raise ValueError(f"the {self.cfg.kind} schedule of {num_inference_steps} steps has a non-finite coefficient (sigmas {sig.tolist()})")
         return tab
+
+    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
+        """(1, sigma_t) of add_noise at an entry t of the schedule of n steps: x_t = x_0 + sigma_t noise, sigma looked up by `timesteps == t`
+        as the reference's add_noise does (scheduling_euler_discrete.py:276-279)"""
+        if num_inference_steps is None:
+            raise ValueError("a sigma-space add_noise looks the timestep up in a schedule: num_inference_steps is needed")
+        hit = (self.timesteps(num_inference_steps) == float(t)).nonzero()
+        if hit.numel() != 1:
+            raise ValueError(f"timestep {t} is not an entry of the schedule of {num_inference_steps} steps")
+        return 1.0, float(self.sigmas(num_inference_steps)[int(hit)])
 
 
 # one evaluation of a PNDM schedule: what _get_prev_sample sees (timestep, prev_timestep), the weights of the combined model output on
@@ -441,10 +491,17 @@ class PNDMTables:
         """[n + 1] (PLMS) or [n + 9] (Runge-Kutta) int64: one entry per UNet evaluation"""
         return torch.from_numpy(np.concatenate(self.split_timesteps(num_inference_steps)).astype(np.int64))
 
-    def plan(self, num_inference_steps: int) -> List[PNDMEval]:
+    def plan(self, num_inference_steps: int, start_index: int = 0) -> List[PNDMEval]:
         """the reference's state machine (step / step_prk / step_plms: counter, ets, cur_sample, cur_model_output) run over the timestep
-        list, with buffer slots in place of tensors.  Four history slots are enough: step_plms keeps ets[-3:] before it appends."""
+        list, with buffer slots in place of tensors.  Four history slots are enough: step_plms keeps ets[-3:] before it appends.
+        start_index > 0 (PLMS mode only): the machine runs over the entries start_index .. with its counter at zero, as the reference's
+        does when a pipeline slices the list - its second evaluation redoes its first step whatever timestep that entry carries."""
         ts = self.timesteps(num_inference_steps).tolist()
+        start_index = check_start_index(start_index, len(ts))
+        if start_index > 0 and not self.cfg.skip_prk_steps:
+            raise ValueError(f"start_index = {start_index}: a PNDM schedule in Runge-Kutta mode (skip_prk_steps=False) cannot start part-way - "
+                             "the slice cuts into a group of four evaluations that share one step; use skip_prk_steps=True (PLMS)")
+        ts = ts[start_index:]
         ratio = self.cfg.num_train_timesteps // int(num_inference_steps)
         n_prk = 0 if self.cfg.skip_prk_steps else self.PRK_EVALUATIONS
         ets, plan = [], []
@@ -494,9 +551,13 @@ class PNDMTables:
         c = [w * wi for wi in ev.weights] + [0.0] * (4 - ev.order)
         return [cx, *c, ev.s_g]
 
-    def coefficient_table(self, num_inference_steps: int) -> torch.Tensor:
+    def coefficient_table(self, num_inference_steps: int, start_index: int = 0) -> torch.Tensor:
         """[evaluations][6] f32, each entry rounded once"""
-        tab = torch.tensor([self.step_coefficients(ev) for ev in self.plan(num_inference_steps)], dtype=torch.float64).float()
+        tab = torch.tensor([self.step_coefficients(ev) for ev in self.plan(num_inference_steps, start_index)], dtype=torch.float64).float()
         if not torch.isfinite(tab).all():
             raise ValueError(f"the PNDM schedule of {num_inference_steps} steps has a non-finite coefficient")
         return tab
+
+    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
+        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
+        return alpha_add_noise_coefficients(self.alphas_cumprod, t)

@@ -732,6 +732,62 @@ class HipOps:
         s.denom, s.scale_cond = float(denom), int(scale_cond)
         self._call("fyc_unet_input_scaled", s)
 
+    @staticmethod
+    def _contiguous(what: str, *tensors) -> None:
+        if any(t is not None and not t.is_contiguous() for t in tensors):
+            raise ValueError(f"{what}: every tensor must be contiguous")
+
+    def posterior_latents(self, moments: Tensor, latents: Tensor, *, noise_post: Optional[Tensor] = None, noise_add: Optional[Tensor] = None,
+                          clean_out: Optional[Tensor] = None, scale: float, c_x: float = 1.0, c_n: float = 0.0) -> None:
+        """VAE moments (N, 2C, h, w) f32 -> noised start latents (N, C, h, w) f32 (include/fyc.h, fyc_posterior_latents): z = (mean + std *
+        noise_post) * scale (noise_post None: the mode, mean * scale), clean_out = z (None = not stored), latents = c_x z + c_n noise_add
+        (noise_add None: c_x z)"""
+        self.ensure_init(moments.device)
+        N, C2, H, W = moments.shape
+        if C2 % 2 or tuple(latents.shape) != (N, C2 // 2, H, W):
+            raise ValueError(f"posterior_latents: moments {tuple(moments.shape)} do not give latents {tuple(latents.shape)}")
+        for name, t in (("noise_post", noise_post), ("noise_add", noise_add), ("clean_out", clean_out)):
+            if t is not None and tuple(t.shape) != tuple(latents.shape):
+                raise ValueError(f"posterior_latents: {name} must have the latents' shape")
+        self._contiguous("posterior_latents", moments, latents, noise_post, noise_add, clean_out)
+        a = L.PosteriorLatentsArgs()
+        a.moments, a.noise_post, a.noise_add = _f32(moments, "moments"), _f32(noise_post, "noise_post"), _f32(noise_add, "noise_add")
+        a.latents, a.clean_out = _f32(latents, "latents"), _f32(clean_out, "clean_out")
+        a.N, a.C, a.HW, a.scale, a.c_x, a.c_n = N, C2 // 2, H * W, float(scale), float(c_x), float(c_n)
+        self._call("fyc_posterior_latents", a)
+
+    def inpaint_prepare(self, image: Optional[Tensor], mask: Tensor, *, masked: Optional[Tensor] = None, mask_latent: Optional[Tensor] = None) -> None:
+        """image (N, 3, H, W) f32 in [-1, 1], mask (N, 1, H, W) f32 in [0, 1] -> masked (N, 3, H, W) = image * (mask < 0.5), mask_latent
+        (N, 1, H/8, W/8) = the binarised mask at pixel (8i, 8j) (include/fyc.h, fyc_inpaint_prepare); an output left None is not stored"""
+        self.ensure_init(mask.device)
+        N, one, H, W = mask.shape
+        if one != 1 or H % 8 or W % 8:
+            raise ValueError(f"inpaint_prepare: mask {tuple(mask.shape)} must be (N, 1, H, W) with H and W multiples of 8")
+        if masked is not None and (image is None or tuple(image.shape) != (N, 3, H, W) or tuple(masked.shape) != (N, 3, H, W)):
+            raise ValueError(f"inpaint_prepare: image and masked must be ({N}, 3, {H}, {W})")
+        if mask_latent is not None and tuple(mask_latent.shape) != (N, 1, H // 8, W // 8):
+            raise ValueError(f"inpaint_prepare: mask_latent must be ({N}, 1, {H // 8}, {W // 8})")
+        self._contiguous("inpaint_prepare", image, mask, masked, mask_latent)
+        a = L.InpaintPrepareArgs()
+        a.image, a.mask, a.masked, a.mask_latent = _f32(image, "image"), _f32(mask, "mask"), _f32(masked, "masked"), _f32(mask_latent, "mask_latent")
+        a.N, a.H, a.W = N, H, W
+        self._call("fyc_inpaint_prepare", a)
+
+    def renoise_blend(self, latents: Tensor, orig: Tensor, noise: Tensor, mask: Tensor, *, c_x: float, c_n: float, B: int, C_: int, F: int,
+                      HW: int) -> None:
+        """latents (B, C, F, HW) f32 in place = (c_x orig + c_n noise) * mask + latents * (1 - mask) (include/fyc.h, fyc_renoise_blend); mask
+        (B, 1, HW); orig and noise (B, C, HW) - broadcast over the frames - or the latents' shape"""
+        self.ensure_init(latents.device)
+        n = B * C_ * F * HW
+        if latents.numel() != n or mask.numel() != B * HW or orig.numel() != noise.numel() or orig.numel() not in (n, n // F):
+            raise ValueError(f"renoise_blend: latents {tuple(latents.shape)}, orig {tuple(orig.shape)}, noise {tuple(noise.shape)}, mask "
+                             f"{tuple(mask.shape)} do not fit B = {B}, C = {C_}, F = {F}, HW = {HW}")
+        self._contiguous("renoise_blend", latents, orig, noise, mask)
+        a = L.RenoiseBlendArgs()
+        a.latents, a.orig, a.noise, a.mask = _f32(latents, "latents"), _f32(orig, "orig"), _f32(noise, "noise"), _f32(mask, "mask")
+        a.B, a.C, a.F, a.HW, a.src_frames, a.c_x, a.c_n = B, C_, F, HW, (F if orig.numel() == n else 1), float(c_x), float(c_n)
+        self._call("fyc_renoise_blend", a)
+
     def nchw_to_nhwc(self, z: Tensor, x: Tensor, *, N: int, C_: int, HW: int, c_pad: int, scale: float) -> None:
         self.ensure_init(z.device)
         a = L.NchwInArgs()

@@ -516,6 +516,40 @@ typedef struct {
 int64_t fyc_cfg_pndm_workspace_bytes(const fyc_cfg_pndm_args* a);
 int fyc_cfg_pndm_step(const fyc_cfg_pndm_args* a, void* stream);
 
+/* ---- (308, added entry points) the front end of the image-editing pipelines (csrc/image_edit.hip) ------------------------------------
+ * Three f32 kernels, all arithmetic in f32 in the written order, no atomics: the same call gives the same bits.  A NULL input is not
+ * loaded, a NULL output is not stored.  Each takes 16-byte loads / stores when the innermost extent is a multiple of 4 and every pointer is
+ * 16-byte aligned, scalar ones otherwise (the same bits either way).  Outputs overlapping an input or each other are refused.
+ *
+ * fyc_posterior_latents: VAE moments (N, 2C, h, w) = [mean | logvar] -> noised start latents (N, C, h, w), HW = h w:
+ *   z       = (mean + expf(0.5 clamp(logvar, -30, 20)) * noise_post) * scale      (DiagonalGaussianDistribution.sample, diffusers/models/
+ *             vae.py:341-361, then `0.18215 *`); noise_post NULL: z = mean * scale (mode(); the log-variance is not loaded)
+ *   clean_out = z (NULL = not stored)
+ *   latents = c_x z + c_n noise_add      (add_noise); noise_add NULL: latents = c_x z */
+typedef struct {
+  const float* moments; const float* noise_post; const float* noise_add; float* latents; float* clean_out;
+  int32_t N, C, HW; float scale, c_x, c_n;
+} fyc_posterior_latents_args;
+int fyc_posterior_latents(const fyc_posterior_latents_args* a, void* stream);
+
+/* fyc_inpaint_prepare: image (N, 3, H, W) in [-1, 1], mask (N, 1, H, W) in [0, 1], H and W multiples of 8 ->
+ *   masked (N, 3, H, W)            = image * (mask < 0.5 ? 1 : 0): the NCHW f32 tensor the VAE encoder takes
+ *   mask_latent (N, 1, H/8, W/8)   = mask at pixel (8i, 8j) < 0.5 ? 0 : 1
+ * (prepare_mask_and_masked_image and F.interpolate(mode="nearest"), pipeline_stable_diffusion_inpaint.py:38-139, 499-501).  Either output
+ * may be NULL, not both; masked == NULL: the image is not read and may be NULL.  image, mask and masked must be 16-byte aligned. */
+typedef struct { const float* image; const float* mask; float* masked; float* mask_latent; int32_t N, H, W; } fyc_inpaint_prepare_args;
+int fyc_inpaint_prepare(const fyc_inpaint_prepare_args* a, void* stream);
+
+/* fyc_renoise_blend: latents (B, C, F, HW) updated in place,
+ *   latents = (c_x orig + c_n noise) * m + latents * (1 - m)      (pipeline_stable_diffusion_inpaint_legacy.py:573-575)
+ * m (B, 1, HW) is broadcast over channels and frames; orig and noise are (B, C, src_frames, HW) with src_frames = 1 (broadcast over the
+ * frames) or F. */
+typedef struct {
+  float* latents; const float* orig; const float* noise; const float* mask;
+  int32_t B, C, F, HW, src_frames; float c_x, c_n;
+} fyc_renoise_blend_args;
+int fyc_renoise_blend(const fyc_renoise_blend_args* a, void* stream);
+
 /* VAE ends: z (N,4,h,w) f32 * scale -> channels-last [N][hw][c_pad];
  * image channels-last [N][HW][ld] -> (N,3,H,W) f32 = clamp(x/2+0.5, 0, 1) (pipeline_animation.py:402,410) */
 typedef struct { const float* z; void* x; int32_t N, C, HW, c_pad; float scale; int32_t dtype; } fyc_nchw_in_args;
