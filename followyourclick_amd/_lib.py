@@ -280,18 +280,11 @@ def load() -> C.CDLL:
         lib.fyc_panel_linear_supported.restype = C.c_int
         lib.fyc_panel_linear_wstream_bytes.argtypes = [i32, i32]
         lib.fyc_panel_linear_wstream_bytes.restype = i64
-    if not ab_build or hasattr(lib, "fyc_cfg_ddim_rescale_workspace_bytes"):
-        lib.fyc_cfg_ddim_rescale_workspace_bytes.argtypes = [C.POINTER(CfgDdimRescaleArgs)]
-        lib.fyc_cfg_ddim_rescale_workspace_bytes.restype = i64
-    if not ab_build or hasattr(lib, "fyc_cfg_solver_workspace_bytes"):
-        lib.fyc_cfg_solver_workspace_bytes.argtypes = [C.POINTER(CfgSolverArgs)]
-        lib.fyc_cfg_solver_workspace_bytes.restype = i64
-    if not ab_build or hasattr(lib, "fyc_cfg_sigma_workspace_bytes"):
-        lib.fyc_cfg_sigma_workspace_bytes.argtypes = [C.POINTER(CfgSigmaArgs)]
-        lib.fyc_cfg_sigma_workspace_bytes.restype = i64
-    if not ab_build or hasattr(lib, "fyc_cfg_pndm_workspace_bytes"):
-        lib.fyc_cfg_pndm_workspace_bytes.argtypes = [C.POINTER(CfgPndmArgs)]
-        lib.fyc_cfg_pndm_workspace_bytes.restype = i64
+    for name, st in (("fyc_cfg_ddim_rescale_workspace_bytes", CfgDdimRescaleArgs), ("fyc_cfg_solver_workspace_bytes", CfgSolverArgs),
+                     ("fyc_cfg_sigma_workspace_bytes", CfgSigmaArgs), ("fyc_cfg_pndm_workspace_bytes", CfgPndmArgs)):
+        if not ab_build or hasattr(lib, name):
+            getattr(lib, name).argtypes = [C.POINTER(st)]
+            getattr(lib, name).restype = i64
     if not ab_build or hasattr(lib, "fyc_conv_up_phases_supported"):
         lib.fyc_conv_up_phases_supported.argtypes = [i32] * 7
         lib.fyc_conv_up_phases_supported.restype = C.c_int

@@ -1,5 +1,7 @@
 // Small HBM-bound kernels around the UNet/VAE: layout changes at the API boundary
 // ((b,c,f,h,w) f32 <-> channels-last), channel concat, guidance + DDIM update, casts.
+#include <type_traits>
+
 #include "fyc_common.h"
 
 namespace {
@@ -125,7 +127,32 @@ __device__ __forceinline__ float cfg_guided(float u, float cnd, bool has_single,
   return u + guidance * (cnd - u);
 }
 
-// guidance + DDIM update of pixel-row i = (b, f, p): the body of both step kernels.  RESCALE: the guided prediction of sample b is
+// the guided prediction of channel c of one pixel-row, as every step kernel forms it: the plain prediction without cfg; with it
+// cfg_guided() of the two halves (and the per-frame row, single_row != NULL).  RESCALE: times factor_b, the sample's guidance-rescale factor
+template <typename T, bool RESCALE>
+__device__ __forceinline__ float guided_value(const T* pu, const T* pc, const T* single_row, int c, float guidance, float video_scale, int cfg,
+                                              float factor_b) {
+  float v = ElemIO<T>::ld(pu + c);
+  if (cfg) {
+    const float u = v, cnd = ElemIO<T>::ld(pc + c);
+    v = cfg_guided(u, cnd, single_row != nullptr, single_row ? ElemIO<T>::ld(single_row + c) : 0.f, video_scale, guidance);
+    if (RESCALE) v *= factor_b;
+  }
+  return v;
+}
+
+// pixel-row i = (b, f, p) of the channels-last prediction, and where its channel c lies in the (B, CL, F, HW) latents
+struct PixelRow {
+  int b, f, p;
+  __device__ __forceinline__ PixelRow(long long i, int F, int HW) : p((int)(i % HW)) {
+    const long long bf = i / HW;
+    f = (int)(bf % F);
+    b = (int)(bf / F);
+  }
+  __device__ __forceinline__ long long latent(int c, int CL, int F, int HW) const { return (((long long)b * CL + c) * F + f) * HW + p; }
+};
+
+// guidance + DDIM update of pixel-row i = (b, f, p): the body of the DDIM step kernel.  RESCALE: the guided prediction of sample b is
 // multiplied by factor[b] (guidance rescale, fyc_cfg_ddim_step_rescaled) before anything else sees it
 template <typename T, bool RESCALE>
 __device__ __forceinline__ void cfg_ddim_row(long long i, const T* __restrict__ pred, float* __restrict__ lat, float sa, float sb,
@@ -133,20 +160,14 @@ __device__ __forceinline__ void cfg_ddim_row(long long i, const T* __restrict__ 
                                              int pred_type, int clip, const T* __restrict__ single, float video_scale,
                                              const float* __restrict__ noise, float sigma, int reclip,
                                              const float* __restrict__ factor) {
-  const int p = (int)(i % HW);
-  const long long bf = i / HW;
-  const int f = (int)(bf % F), b = (int)(bf / F);
+  const PixelRow r(i, F, HW);
   const T* pu = pred + i * ld;                                   // uncond (or the only) half
   const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
+  const T* ps = single ? single + i * ld : nullptr;
   for (int c = 0; c < CL; ++c) {
-    float v = ElemIO<T>::ld(pu + c);
-    if (cfg) {
-      const float u = v, cnd = ElemIO<T>::ld(pc + c);
-      v = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
-      if (RESCALE) v *= factor[b];
-    }
-    float* lp = lat + (((long long)b * CL + c) * F + f) * HW + p;
-    const float x = *lp;
+    const float v = guided_value<T, RESCALE>(pu, pc, ps, c, guidance, video_scale, cfg, RESCALE ? factor[r.b] : 0.f);
+    const long long j = r.latent(c, CL, F, HW);
+    const float x = lat[j];
     float x0, eps;
     if (pred_type == 1) { x0 = sa * x - sb * v; eps = sa * v + sb * x; }
     else if (pred_type == 0) { x0 = (x - sb * v) / sa; eps = v; }
@@ -154,157 +175,75 @@ __device__ __forceinline__ void cfg_ddim_row(long long i, const T* __restrict__ 
     if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     if (reclip) eps = (x - sa * x0) / sb;                        // use_clipped_model_output (scheduling_ddim.py:342-344)
     float nx = sap * x0 + sbp * eps;
-    if (noise) nx += sigma * noise[(((long long)b * CL + c) * F + f) * HW + p];      // eta > 0 (:346-363)
-    *lp = nx;
+    if (noise) nx += sigma * noise[j];                           // eta > 0 (:346-363)
+    lat[j] = nx;
   }
 }
 
-template <typename T>
+// fyc_cfg_ddim_step (RESCALE = false, factor = NULL) and fyc_cfg_ddim_step_rescaled (cfg is on: the host refuses the rest)
+template <typename T, bool RESCALE>
 __global__ void __launch_bounds__(256) cfg_ddim_kernel(const T* __restrict__ pred, float* __restrict__ lat,
                                                        const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
                                                        int cfg, float guidance, int pred_type, int clip,
                                                        const T* __restrict__ single, float video_scale,
-                                                       const float* __restrict__ noise, float sigma, int reclip) {
+                                                       const float* __restrict__ noise, float sigma, int reclip,
+                                                       const float* __restrict__ factor) {
   const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
   const long long total = (long long)B * F * HW;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
-    cfg_ddim_row<T, false>(i, pred, lat, sa, sb, sap, sbp, B, F, HW, CL, ld, cfg, guidance, pred_type, clip, single, video_scale, noise,
-                           sigma, reclip, nullptr);
+    cfg_ddim_row<T, RESCALE>(i, pred, lat, sa, sb, sap, sbp, B, F, HW, CL, ld, cfg, guidance, pred_type, clip, single, video_scale, noise,
+                             sigma, reclip, factor);
 }
 
-// the same step with the per-sample factor of the guidance rescale (cfg is on: the host refuses the rest)
-template <typename T>
-__global__ void __launch_bounds__(256) cfg_ddim_rescaled_kernel(const T* __restrict__ pred, float* __restrict__ lat,
-                                                                const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
-                                                                float guidance, int pred_type, int clip,
-                                                                const T* __restrict__ single, float video_scale,
-                                                                const float* __restrict__ noise, float sigma, int reclip,
-                                                                const float* __restrict__ factor) {
-  const float sa = coef[0], sb = coef[1], sap = coef[2], sbp = coef[3];
-  const long long total = (long long)B * F * HW;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
-    cfg_ddim_row<T, true>(i, pred, lat, sa, sb, sap, sbp, B, F, HW, CL, ld, 1, guidance, pred_type, clip, single, video_scale, noise,
-                          sigma, reclip, factor);
-}
+// the optional buffers of a linear step, all (B, CL, F, HW) f32; NULL = not read / not written (one uniform branch each).  acc_in may be
+// acc_out (element j is read and then written by the same thread), so nothing here is __restrict__
+struct StepBuffers {
+  const float* sample_in; float* sample_out;
+  float* hist_out; const float* hist[3];
+  const float* noise;
+  const float* acc_in; float* acc_out;
+};
 
-// Guidance + one step of the DPM-Solver multistep family (fyc_cfg_solver_step).  Every update of the family is linear in the latents x,
-// the guided prediction v and the stored converted outputs: coef = {a_x, a_v, c_x, c_0, c_1, c_2} gives m0 = a_x x + a_v v and
-// x' = c_x x + c_0 m0 + c_1 m1 + c_2 m2.  ORDER is a template parameter so that a history buffer the order does not use is never
-// loaded: 0 * NaN is NaN, and the first step's history is whatever the allocator left.
-template <typename T, int ORDER, bool RESCALE>
-__global__ void __launch_bounds__(256) cfg_solver_kernel(const T* __restrict__ pred, float* __restrict__ lat,
-                                                         const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
-                                                         int cfg, float guidance, const T* __restrict__ single, float video_scale,
-                                                         float* __restrict__ hist_out, const float* __restrict__ hist_1,
-                                                         const float* __restrict__ hist_2, const float* __restrict__ factor) {
-  const float ax = coef[0], av = coef[1], cx = coef[2], c0 = coef[3], c1 = coef[4], c2 = coef[5];
-  const long long total = (long long)B * F * HW;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const long long bf = i / HW;
-    const int f = (int)(bf % F), b = (int)(bf / F);
-    const T* pu = pred + i * ld;                                   // uncond (or the only) half
-    const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
-    for (int c = 0; c < CL; ++c) {
-      float v = ElemIO<T>::ld(pu + c);
-      if (cfg) {
-        const float u = v, cnd = ElemIO<T>::ld(pc + c);
-        v = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
-        if (RESCALE) v *= factor[b];
-      }
-      const long long j = (((long long)b * CL + c) * F + f) * HW + p;
-      const float x = lat[j];
-      const float m0 = ax * x + av * v;
-      float nx = cx * x + c0 * m0;
-      if (ORDER >= 2) nx += c1 * hist_1[j];
-      if (ORDER >= 3) nx += c2 * hist_2[j];
-      lat[j] = nx;
-      hist_out[j] = m0;
-    }
-  }
-}
-
-// Guidance + one step of a sigma-space (k-diffusion) sampler: Euler, Euler ancestral, LMS (fyc_cfg_sigma_step).  coef = {a_x, a_v, c_x, c_0,
-// c_1, c_2, c_3, c_n} gives the derivative d = a_x x + a_v v and x' = c_x x + c_0 d + c_1 d1 + c_2 d2 + c_3 d3 + c_n noise, summed left to
-// right.  ORDER is a template parameter as in cfg_solver_kernel: a history the order does not use is never loaded.  hist_out and noise are
-// NULL for the variants without them (one uniform branch each): nothing is stored, nothing is loaded.
-template <typename T, int ORDER, bool RESCALE>
-__global__ void __launch_bounds__(256) cfg_sigma_kernel(const T* __restrict__ pred, float* __restrict__ lat,
-                                                        const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
-                                                        int cfg, float guidance, const T* __restrict__ single, float video_scale,
-                                                        float* __restrict__ hist_out, const float* __restrict__ hist_1,
-                                                        const float* __restrict__ hist_2, const float* __restrict__ hist_3,
-                                                        const float* __restrict__ noise, const float* __restrict__ factor) {
-  const float ax = coef[0], av = coef[1], cx = coef[2], c0 = coef[3], c1 = coef[4], c2 = coef[5], c3 = coef[6], cn = coef[7];
+// Guidance + one step of every sampler whose update is linear in the latents, the guided prediction and stored ones: the DPM-Solver
+// multistep family (fyc_cfg_solver_step), the sigma-space samplers Euler, Euler ancestral and LMS (fyc_cfg_sigma_step) and PNDM in its
+// PLMS and Runge-Kutta modes (fyc_cfg_pndm_step).  With v the guided (and rescaled) prediction and x the saved sample (sample_in) when one
+// is handed over, the latents otherwise:
+//   CONVERT:  coef = {a_x, a_v, row},  m = a_x x + a_v v   (the converted output m0 of the solver, the derivative d of the sigma samplers)
+//   else:     coef = row,              m = v               (PNDM: the v-prediction conversion is folded into the row)
+//   row = {c_x, c_0, c_1, c_2, c_3, tail}:  x' = c_x x + c_0 m + c_1 hist[0] + c_2 hist[1] + c_3 hist[2] + tail noise,  summed left to right
+// ORDER is a template parameter so that a history the order does not use is never loaded: 0 * NaN is NaN, and the first step's history
+// is whatever the allocator left.  Stores: the latents <- x';  sample_out <- the latents as they were (with sample_in and no sample_out
+// the latents are not read);  hist_out <- m;  acc_out <- acc_in + tail m (acc_in NULL: tail m).  tail is c_n where there is noise, s_g
+// where there is an accumulator, padding otherwise.
+template <typename T, int ORDER, bool CONVERT, bool RESCALE>
+__global__ void __launch_bounds__(256) cfg_linear_step_kernel(const T* __restrict__ pred, float* __restrict__ lat,
+                                                              const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
+                                                              int cfg, float guidance, const T* __restrict__ single, float video_scale,
+                                                              StepBuffers buf, const float* __restrict__ factor) {
+  const float ax = CONVERT ? coef[0] : 0.f, av = CONVERT ? coef[1] : 0.f;
+  const float* row = coef + (CONVERT ? 2 : 0);
+  const float cx = row[0], c0 = row[1], c1 = row[2], c2 = row[3], c3 = row[4], tail = row[5];
   const long long total = (long long)B * F * HW;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const long long bf = i / HW;
-    const int f = (int)(bf % F), b = (int)(bf / F);
+    const PixelRow r(i, F, HW);
     const T* pu = pred + i * ld;                                   // uncond (or the only) half
     const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
+    const T* ps = single ? single + i * ld : nullptr;
     for (int c = 0; c < CL; ++c) {
-      float v = ElemIO<T>::ld(pu + c);
-      if (cfg) {
-        const float u = v, cnd = ElemIO<T>::ld(pc + c);
-        v = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
-        if (RESCALE) v *= factor[b];
-      }
-      const long long j = (((long long)b * CL + c) * F + f) * HW + p;
-      const float x = lat[j];
-      const float d = ax * x + av * v;
-      float nx = cx * x + c0 * d;
-      if (ORDER >= 2) nx += c1 * hist_1[j];
-      if (ORDER >= 3) nx += c2 * hist_2[j];
-      if (ORDER >= 4) nx += c3 * hist_3[j];
-      if (noise) nx += cn * noise[j];
+      const float v = guided_value<T, RESCALE>(pu, pc, ps, c, guidance, video_scale, cfg, RESCALE ? factor[r.b] : 0.f);
+      const long long j = r.latent(c, CL, F, HW);
+      const float before = (buf.sample_out || !buf.sample_in) ? lat[j] : 0.f;
+      if (buf.sample_out) buf.sample_out[j] = before;
+      const float x = buf.sample_in ? buf.sample_in[j] : before;
+      const float m = CONVERT ? ax * x + av * v : v;
+      float nx = cx * x + c0 * m;
+      if (ORDER >= 2) nx += c1 * buf.hist[0][j];
+      if (ORDER >= 3) nx += c2 * buf.hist[1][j];
+      if (ORDER >= 4) nx += c3 * buf.hist[2][j];
+      if (buf.noise) nx += tail * buf.noise[j];
       lat[j] = nx;
-      if (hist_out) hist_out[j] = d;
-    }
-  }
-}
-
-// Guidance + one evaluation of the PNDM scheduler, PLMS or Runge-Kutta mode (fyc_cfg_pndm_step).  coef = {c_x, c_0, c_1, c_2, c_3, s_g} gives
-// x' = c_x x + c_0 g + c_1 h1 + c_2 h2 + c_3 h3, summed left to right, with g the guided (and rescaled) prediction as it is - the histories
-// hold raw guided predictions, the v-prediction conversion is folded into c_x and the c_k - and x the saved sample (sample_in) when one is
-// handed over, the latents otherwise.  ORDER is a template parameter as in cfg_solver_kernel: a history the order does not use is never
-// loaded.  sample_in, sample_out, hist_out, acc_in and acc_out are NULL for the evaluations without them (one uniform branch each): nothing
-// is stored, nothing is loaded.  sample_out receives the latents as they were, acc_out = acc_in + s_g g (acc_in NULL: s_g g; acc_in may be
-// acc_out: element j is read and then written by the same thread).
-template <typename T, int ORDER, bool RESCALE>
-__global__ void __launch_bounds__(256) cfg_pndm_kernel(const T* __restrict__ pred, float* __restrict__ lat,
-                                                       const float* __restrict__ coef, int B, int F, int HW, int CL, int ld,
-                                                       int cfg, float guidance, const T* __restrict__ single, float video_scale,
-                                                       const float* __restrict__ sample_in, float* __restrict__ sample_out,
-                                                       float* __restrict__ hist_out, const float* __restrict__ hist_1,
-                                                       const float* __restrict__ hist_2, const float* __restrict__ hist_3,
-                                                       const float* acc_in, float* acc_out, const float* __restrict__ factor) {
-  const float cx = coef[0], c0 = coef[1], c1 = coef[2], c2 = coef[3], c3 = coef[4], sg = coef[5];
-  const long long total = (long long)B * F * HW;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int p = (int)(i % HW);
-    const long long bf = i / HW;
-    const int f = (int)(bf % F), b = (int)(bf / F);
-    const T* pu = pred + i * ld;                                   // uncond (or the only) half
-    const T* pc = pred + ((long long)B * F * HW + i) * ld;         // cond half
-    for (int c = 0; c < CL; ++c) {
-      float g = ElemIO<T>::ld(pu + c);
-      if (cfg) {
-        const float u = g, cnd = ElemIO<T>::ld(pc + c);
-        g = cfg_guided(u, cnd, single != nullptr, single ? ElemIO<T>::ld(single + i * ld + c) : 0.f, video_scale, guidance);
-        if (RESCALE) g *= factor[b];
-      }
-      const long long j = (((long long)b * CL + c) * F + f) * HW + p;
-      const float before = (sample_out || !sample_in) ? lat[j] : 0.f;      // with a saved sample to step from, the latents are not read
-      if (sample_out) sample_out[j] = before;
-      const float x = sample_in ? sample_in[j] : before;
-      float nx = cx * x + c0 * g;
-      if (ORDER >= 2) nx += c1 * hist_1[j];
-      if (ORDER >= 3) nx += c2 * hist_2[j];
-      if (ORDER >= 4) nx += c3 * hist_3[j];
-      lat[j] = nx;
-      if (hist_out) hist_out[j] = g;
-      if (acc_out) acc_out[j] = (acc_in ? acc_in[j] : 0.f) + sg * g;
+      if (buf.hist_out) buf.hist_out[j] = m;
+      if (buf.acc_out) buf.acc_out[j] = (buf.acc_in ? buf.acc_in[j] : 0.f) + tail * m;
     }
   }
 }
@@ -592,6 +531,30 @@ extern "C" int fyc_unet_input_scaled(const fyc_unet_input_scaled_args* s, void* 
   return 0;
 }
 
+// fn(TypeTag<T>{}) for the element type T of a dtype code; false = no such dtype, nothing ran
+template <typename T> struct TypeTag { using type = T; };
+template <typename Fn>
+static bool with_dtype(int dtype, Fn&& fn) {
+  if (dtype == FYC_BF16) fn(TypeTag<bf16_t>{});
+  else if (dtype == FYC_F16) fn(TypeTag<f16_t>{});
+  else if (dtype == FYC_F32) fn(TypeTag<float>{});
+  else return false;
+  return true;
+}
+
+// the guidance operands every cfg step starts from: the leading fields of fyc_cfg_ddim_args, _solver_args, _sigma_args and _pndm_args
+struct CfgOperands {
+  const void* pred; float* latents; const float* coef;
+  int B, F, HW, c_latent, ld, cfg; float guidance;
+  int dtype;
+  const void* pred_single; float video_scale;
+};
+
+template <typename A>
+static CfgOperands cfg_operands(const A& a) {
+  return {a.pred, a.latents, a.coef, a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype, a.pred_single, a.video_scale};
+}
+
 // the argument checks of the DDIM step, shared by its two entry points
 static int cfg_ddim_check(const fyc_cfg_ddim_args* a) {
   FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_ddim_step: null pointer");
@@ -602,14 +565,19 @@ static int cfg_ddim_check(const fyc_cfg_ddim_args* a) {
   return 0;
 }
 
+template <typename T, bool RESCALE>
+static void cfg_ddim_launch(const fyc_cfg_ddim_args* a, const float* factor, hipStream_t st) {
+  const long long n = (long long)a->B * a->F * a->HW;
+  hipLaunchKernelGGL((cfg_ddim_kernel<T, RESCALE>), dim3(grid_for(n)), dim3(256), 0, st, (const T*)a->pred, a->latents, a->coef, a->B, a->F,
+                     a->HW, a->c_latent, a->ld, a->cfg, a->guidance, a->pred_type, a->clip_sample, (const T*)a->pred_single, a->video_scale,
+                     a->variance_noise, a->sigma, a->clipped_model_output, factor);
+}
+
 extern "C" int fyc_cfg_ddim_step(const fyc_cfg_ddim_args* a, void* stream) {
   if (int rc = cfg_ddim_check(a)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const long long n = (long long)a->B * a->F * a->HW;
-  FYC_DT(a,
-         hipLaunchKernelGGL(cfg_ddim_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, (const bf16_t*)a->pred, a->latents, a->coef, a->B, a->F, a->HW, a->c_latent, a->ld, a->cfg, a->guidance, a->pred_type, a->clip_sample, (const bf16_t*)a->pred_single, a->video_scale, a->variance_noise, a->sigma, a->clipped_model_output),
-         hipLaunchKernelGGL(cfg_ddim_kernel<f16_t>, dim3(grid_for(n)), dim3(256), 0, st, (const f16_t*)a->pred, a->latents, a->coef, a->B, a->F, a->HW, a->c_latent, a->ld, a->cfg, a->guidance, a->pred_type, a->clip_sample, (const f16_t*)a->pred_single, a->video_scale, a->variance_noise, a->sigma, a->clipped_model_output),
-         hipLaunchKernelGGL(cfg_ddim_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (const float*)a->pred, a->latents, a->coef, a->B, a->F, a->HW, a->c_latent, a->ld, a->cfg, a->guidance, a->pred_type, a->clip_sample, (const float*)a->pred_single, a->video_scale, a->variance_noise, a->sigma, a->clipped_model_output));
+  if (!with_dtype(a->dtype, [&](auto tag) { cfg_ddim_launch<typename decltype(tag)::type, false>(a, nullptr, st); }))
+    FYC_FAIL(-2, "bad dtype %d", a->dtype);
   FYC_CHECK_LAUNCH("fyc_cfg_ddim_step");
   return 0;
 }
@@ -618,50 +586,55 @@ extern "C" int fyc_cfg_ddim_step(const fyc_cfg_ddim_args* a, void* stream) {
 // workspace = [B * nparts][4] f64 partials, then [B] f32 factors
 struct CfgRescalePlan { int rows, nparts; int64_t part_bytes, bytes; };
 
-static bool cfg_rescale_plan(const fyc_cfg_ddim_args* s, CfgRescalePlan& pl) {
-  if (!(s->B > 0 && s->F > 0 && s->HW > 0 && s->c_latent > 0 && s->ld >= s->c_latent)) return false;
-  const int64_t rows = (int64_t)s->F * s->HW;
-  if (rows > INT32_MAX - CFG_MOMENT_ROWS || rows * s->c_latent < 2) return false;
+static bool cfg_rescale_plan(int B, int F, int HW, int c_latent, int ld, CfgRescalePlan& pl) {
+  if (!(B > 0 && F > 0 && HW > 0 && c_latent > 0 && ld >= c_latent)) return false;
+  const int64_t rows = (int64_t)F * HW;
+  if (rows > INT32_MAX - CFG_MOMENT_ROWS || rows * c_latent < 2) return false;
   const int64_t nparts = ceil_div64(rows, CFG_MOMENT_ROWS);
-  if (nparts * s->B > INT32_MAX) return false;
+  if (nparts * B > INT32_MAX) return false;
   pl.rows = (int)rows;
   pl.nparts = (int)nparts;
-  pl.part_bytes = nparts * s->B * 4 * (int64_t)sizeof(double);
-  pl.bytes = (pl.part_bytes + (int64_t)s->B * (int64_t)sizeof(float) + 255) / 256 * 256;
+  pl.part_bytes = nparts * B * 4 * (int64_t)sizeof(double);
+  pl.bytes = (pl.part_bytes + (int64_t)B * (int64_t)sizeof(float) + 255) / 256 * 256;
   return true;
 }
 
-extern "C" int64_t fyc_cfg_ddim_rescale_workspace_bytes(const fyc_cfg_ddim_rescale_args* a) {
+// what the four workspace queries answer: 0 without a rescale to do (phi outside (0, 1], NaN included, or no cfg) or for dims the step refuses
+static int64_t rescale_workspace_bytes(int B, int F, int HW, int c_latent, int ld, int cfg, float phi) {
   CfgRescalePlan pl;
-  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->step.cfg) return 0;
-  return cfg_rescale_plan(&a->step, pl) ? pl.bytes : 0;
+  return phi > 0.f && phi <= 1.f && cfg && cfg_rescale_plan(B, F, HW, c_latent, ld, pl) ? pl.bytes : 0;
 }
 
-// the moments and factor launches, shared by the DDIM and the solver step -> the device factors [B] inside the workspace
+extern "C" int64_t fyc_cfg_ddim_rescale_workspace_bytes(const fyc_cfg_ddim_rescale_args* a) {
+  return a ? rescale_workspace_bytes(a->step.B, a->step.F, a->step.HW, a->step.c_latent, a->step.ld, a->step.cfg, a->guidance_rescale) : 0;
+}
+
+// the moments and factor launches, shared by every step -> the device factors [B] inside the workspace
 template <typename T>
-static const float* cfg_rescale_factors(const fyc_cfg_ddim_args* s, void* workspace, float phi, const CfgRescalePlan& pl, hipStream_t st) {
+static const float* cfg_rescale_factors(const CfgOperands& g, void* workspace, float phi, const CfgRescalePlan& pl, hipStream_t st) {
   double* parts = (double*)workspace;
   float* factor = (float*)((char*)workspace + pl.part_bytes);
-  const T* pred = (const T*)s->pred;
-  const T* single = (const T*)s->pred_single;
+  const T* pred = (const T*)g.pred;
+  const T* single = (const T*)g.pred_single;
   // one vector load per row: 4 latent channels, rows pitched in multiples of 4 elements from bases on such a boundary
   const uintptr_t row_align = 4 * sizeof(T);
-  const bool vec = s->c_latent == 4 && s->ld % 4 == 0 && ((uintptr_t)pred % row_align) == 0 && ((uintptr_t)single % row_align) == 0;
-  const dim3 grid((unsigned)(s->B * pl.nparts));
-  if (vec) hipLaunchKernelGGL((cfg_moments_kernel<T, true>), grid, dim3(256), 0, st, pred, parts, s->B, pl.rows, s->c_latent, s->ld, pl.nparts, s->guidance, single, s->video_scale);
-  else hipLaunchKernelGGL((cfg_moments_kernel<T, false>), grid, dim3(256), 0, st, pred, parts, s->B, pl.rows, s->c_latent, s->ld, pl.nparts, s->guidance, single, s->video_scale);
-  hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(s->B), dim3(64), 0, st, (const double*)parts, factor, pl.nparts, (double)pl.rows * s->c_latent, phi);
+  const bool vec = g.c_latent == 4 && g.ld % 4 == 0 && ((uintptr_t)pred % row_align) == 0 && ((uintptr_t)single % row_align) == 0;
+  const dim3 grid((unsigned)(g.B * pl.nparts));
+  if (vec) hipLaunchKernelGGL((cfg_moments_kernel<T, true>), grid, dim3(256), 0, st, pred, parts, g.B, pl.rows, g.c_latent, g.ld, pl.nparts, g.guidance, single, g.video_scale);
+  else hipLaunchKernelGGL((cfg_moments_kernel<T, false>), grid, dim3(256), 0, st, pred, parts, g.B, pl.rows, g.c_latent, g.ld, pl.nparts, g.guidance, single, g.video_scale);
+  hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(g.B), dim3(64), 0, st, (const double*)parts, factor, pl.nparts, (double)pl.rows * g.c_latent, phi);
   return factor;
 }
 
-template <typename T>
-static void cfg_rescale_launch(const fyc_cfg_ddim_rescale_args* a, const CfgRescalePlan& pl, hipStream_t st) {
-  const fyc_cfg_ddim_args* s = &a->step;
-  const float* factor = cfg_rescale_factors<T>(s, a->workspace, a->guidance_rescale, pl, st);
-  const T* pred = (const T*)s->pred;
-  const T* single = (const T*)s->pred_single;
-  const long long n = (long long)s->B * pl.rows;
-  hipLaunchKernelGGL(cfg_ddim_rescaled_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, pred, s->latents, s->coef, s->B, s->F, s->HW, s->c_latent, s->ld, s->guidance, s->pred_type, s->clip_sample, single, s->video_scale, s->variance_noise, s->sigma, s->clipped_model_output, (const float*)factor);
+// what a positive guidance_rescale asks of cfg, the dims and the workspace, for every entry point that takes one (who: "fyc_cfg_<family>_step",
+// whose workspace query is fyc_cfg_<family>_workspace_bytes)
+static int cfg_rescale_check(const char* who, const char* query, const CfgOperands& g, float phi, const void* workspace, int64_t workspace_bytes,
+                             CfgRescalePlan& pl) {
+  FYC_REQUIRE(g.cfg, "%s: guidance_rescale %g needs classifier-free guidance (cfg = 1)", who, (double)phi);
+  FYC_REQUIRE(cfg_rescale_plan(g.B, g.F, g.HW, g.c_latent, g.ld, pl), "%s: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", who, (long long)g.F * g.HW * g.c_latent);
+  FYC_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 7) == 0, "%s: workspace is null or not 8-byte aligned", who);
+  FYC_REQUIRE(workspace_bytes >= pl.bytes, "%s: workspace_bytes %lld < %lld (%s)", who, (long long)workspace_bytes, (long long)pl.bytes, query);
+  return 0;
 }
 
 extern "C" int fyc_cfg_ddim_step_rescaled(const fyc_cfg_ddim_rescale_args* a, void* stream) {
@@ -672,255 +645,153 @@ extern "C" int fyc_cfg_ddim_step_rescaled(const fyc_cfg_ddim_rescale_args* a, vo
   FYC_REQUIRE(s->cfg, "fyc_cfg_ddim_step_rescaled: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
   if (int rc = cfg_ddim_check(s)) return rc;
   FYC_REQUIRE(s->dtype == FYC_BF16 || s->dtype == FYC_F16 || s->dtype == FYC_F32, "fyc_cfg_ddim_step_rescaled: bad dtype %d", s->dtype);
+  const CfgOperands g = cfg_operands(*s);
   CfgRescalePlan pl;
-  FYC_REQUIRE(cfg_rescale_plan(s, pl), "fyc_cfg_ddim_step_rescaled: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)s->F * s->HW * s->c_latent);
-  FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_ddim_step_rescaled: workspace is null or not 8-byte aligned");
-  FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_ddim_step_rescaled: workspace_bytes %lld < %lld (fyc_cfg_ddim_rescale_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
+  if (int rc = cfg_rescale_check("fyc_cfg_ddim_step_rescaled", "fyc_cfg_ddim_rescale_workspace_bytes", g, a->guidance_rescale, a->workspace, a->workspace_bytes, pl)) return rc;
   FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_ddim_step_rescaled: fyc_init() not called");
   hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == FYC_BF16) cfg_rescale_launch<bf16_t>(a, pl, st);
-  else if (s->dtype == FYC_F16) cfg_rescale_launch<f16_t>(a, pl, st);
-  else cfg_rescale_launch<float>(a, pl, st);
+  with_dtype(s->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    cfg_ddim_launch<T, true>(s, cfg_rescale_factors<T>(g, a->workspace, a->guidance_rescale, pl, st), st);
+  });
   FYC_CHECK_LAUNCH("fyc_cfg_ddim_step_rescaled");
   return 0;
 }
 
-// ---- DPM-Solver multistep: guidance (+ rescale) + conversion + update -----------------------------------------------------------
-// the guidance fields of the solver's arguments as the DDIM step's struct: what the rescale plan and its moments launch read
-static fyc_cfg_ddim_args cfg_solver_guidance(const fyc_cfg_solver_args* a) {
-  fyc_cfg_ddim_args s = {};
-  s.pred = a->pred; s.latents = a->latents; s.coef = a->coef;
-  s.B = a->B; s.F = a->F; s.HW = a->HW; s.c_latent = a->c_latent; s.ld = a->ld; s.cfg = a->cfg; s.guidance = a->guidance;
-  s.dtype = a->dtype; s.pred_single = a->pred_single; s.video_scale = a->video_scale;
-  return s;
+// ---- the linear steps (DPM-Solver multistep, sigma-space, PNDM): one host path for fyc_cfg_solver_step / _sigma_step / _pndm_step -----------
+// one call of cfg_linear_step_kernel as an entry point describes it
+struct StepCall {
+  CfgOperands g;
+  StepBuffers buf;
+  int order, max_order;           // the histories read are hist[0 .. order - 2]
+  bool convert;                   // coef starts with {a_x, a_v} (the kernel's CONVERT)
+  bool needs_init;                // fyc_init() is asked for without a guidance rescale too
+  float guidance_rescale; void* workspace; int64_t workspace_bytes;
+  const char* who;                // the entry point, in front of every message
+  const char* query;              // its workspace query, named where the workspace is short
+};
+
+// the fields the three argument structs share by name; the entry point adds its buffers
+template <typename A>
+static StepCall step_call(const A& a, int max_order, bool convert, bool needs_init, const char* who, const char* query) {
+  return {cfg_operands(a), {}, a.order, max_order, convert, needs_init, a.guidance_rescale, a.workspace, a.workspace_bytes, who, query};
 }
 
-extern "C" int64_t fyc_cfg_solver_workspace_bytes(const fyc_cfg_solver_args* a) {
-  CfgRescalePlan pl;
-  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->cfg) return 0;
-  const fyc_cfg_ddim_args s = cfg_solver_guidance(a);
-  return cfg_rescale_plan(&s, pl) ? pl.bytes : 0;
-}
-
-template <typename T, bool RESCALE>
-static void cfg_solver_launch(const fyc_cfg_solver_args* a, const float* factor, hipStream_t st) {
-  const long long n = (long long)a->B * a->F * a->HW;
-  const dim3 grid(grid_for(n));
-  const T* pred = (const T*)a->pred;
-  const T* single = (const T*)a->pred_single;
-#define FYC_SOLVER_LAUNCH(ORDER)                                                                                                      \
-  hipLaunchKernelGGL((cfg_solver_kernel<T, ORDER, RESCALE>), grid, dim3(256), 0, st, pred, a->latents, a->coef, a->B, a->F, a->HW,    \
-                     a->c_latent, a->ld, a->cfg, a->guidance, single, a->video_scale, a->hist_out, a->hist_1, a->hist_2, factor)
-  if (a->order == 1) FYC_SOLVER_LAUNCH(1);
-  else if (a->order == 2) FYC_SOLVER_LAUNCH(2);
-  else FYC_SOLVER_LAUNCH(3);
-#undef FYC_SOLVER_LAUNCH
-}
-
-template <typename T>
-static void cfg_solver_dispatch(const fyc_cfg_solver_args* a, const CfgRescalePlan* pl, hipStream_t st) {
-  if (pl == nullptr) return cfg_solver_launch<T, false>(a, nullptr, st);
-  const fyc_cfg_ddim_args s = cfg_solver_guidance(a);
-  cfg_solver_launch<T, true>(a, cfg_rescale_factors<T>(&s, a->workspace, a->guidance_rescale, *pl, st), st);
-}
-
-extern "C" int fyc_cfg_solver_step(const fyc_cfg_solver_args* a, void* stream) {
-  FYC_REQUIRE(a && a->pred && a->latents && a->coef && a->hist_out, "fyc_cfg_solver_step: null pointer");
-  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_solver_step: bad dims");
-  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_cfg_solver_step: bad dtype %d", a->dtype);
-  FYC_REQUIRE(a->order >= 1 && a->order <= 3, "fyc_cfg_solver_step: order %d (1 .. 3)", a->order);
-  FYC_REQUIRE(a->order < 2 || a->hist_1 != nullptr, "fyc_cfg_solver_step: order %d needs hist_1", a->order);
-  FYC_REQUIRE(a->order < 3 || a->hist_2 != nullptr, "fyc_cfg_solver_step: order 3 needs hist_2");
-  // hist_out is written while other threads still read the latents and the histories: any overlap of the [n] f32 ranges is refused,
-  // not only equal bases
-  const int64_t n = (int64_t)a->B * a->c_latent * a->F * a->HW;
-  auto overlaps = [n](const float* p, const float* q) { return q != nullptr && p < q + n && q < p + n; };
-  FYC_REQUIRE(!overlaps(a->hist_out, a->latents), "fyc_cfg_solver_step: hist_out aliases latents");
-  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_1), "fyc_cfg_solver_step: hist_out aliases hist_1");
-  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_2), "fyc_cfg_solver_step: hist_out aliases hist_2");
-  FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_solver_step: pred_single needs classifier-free guidance (cfg = 1)");
-  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_solver_step: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
-  hipStream_t st = (hipStream_t)stream;
-  CfgRescalePlan pl;
-  const bool rescale = a->guidance_rescale > 0.f;
-  if (rescale) {
-    FYC_REQUIRE(a->cfg, "fyc_cfg_solver_step: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
-    const fyc_cfg_ddim_args s = cfg_solver_guidance(a);
-    FYC_REQUIRE(cfg_rescale_plan(&s, pl), "fyc_cfg_solver_step: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)a->F * a->HW * a->c_latent);
-    FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_solver_step: workspace is null or not 8-byte aligned");
-    FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_solver_step: workspace_bytes %lld < %lld (fyc_cfg_solver_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
-    FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_solver_step: fyc_init() not called");
-  }
-  if (a->dtype == FYC_BF16) cfg_solver_dispatch<bf16_t>(a, rescale ? &pl : nullptr, st);
-  else if (a->dtype == FYC_F16) cfg_solver_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
-  else cfg_solver_dispatch<float>(a, rescale ? &pl : nullptr, st);
-  FYC_CHECK_LAUNCH("fyc_cfg_solver_step");
+// pointers, dims, dtype, order, the histories the order reads, pred_single, the rescale and its workspace; pl is set with a positive rescale
+static int step_check(const StepCall& c, CfgRescalePlan& pl) {
+  const CfgOperands& g = c.g;
+  FYC_REQUIRE(g.pred && g.latents && g.coef, "%s: null pointer", c.who);
+  FYC_REQUIRE(g.B > 0 && g.F > 0 && g.HW > 0 && g.c_latent > 0 && g.ld >= g.c_latent, "%s: bad dims", c.who);
+  FYC_REQUIRE(g.dtype == FYC_BF16 || g.dtype == FYC_F16 || g.dtype == FYC_F32, "%s: bad dtype %d", c.who, g.dtype);
+  FYC_REQUIRE(c.order >= 1 && c.order <= c.max_order, "%s: order %d (1 .. %d)", c.who, c.order, c.max_order);
+  for (int k = 1; k < c.order; ++k) FYC_REQUIRE(c.buf.hist[k - 1] != nullptr, "%s: order %d needs hist_%d", c.who, c.order, k);
+  FYC_REQUIRE(g.pred_single == nullptr || g.cfg, "%s: pred_single needs classifier-free guidance (cfg = 1)", c.who);
+  FYC_REQUIRE(c.guidance_rescale >= 0.f && c.guidance_rescale <= 1.f, "%s: guidance_rescale %g (0 = off .. 1)", c.who, (double)c.guidance_rescale);
+  if (c.guidance_rescale > 0.f) return cfg_rescale_check(c.who, c.query, g, c.guidance_rescale, c.workspace, c.workspace_bytes, pl);
   return 0;
 }
 
-// ---- sigma-space samplers (Euler, Euler ancestral, LMS): guidance (+ rescale) + derivative + update -------------------------------
-static fyc_cfg_ddim_args cfg_sigma_guidance(const fyc_cfg_sigma_args* a) {
-  fyc_cfg_ddim_args s = {};
-  s.pred = a->pred; s.latents = a->latents; s.coef = a->coef;
-  s.B = a->B; s.F = a->F; s.HW = a->HW; s.c_latent = a->c_latent; s.ld = a->ld; s.cfg = a->cfg; s.guidance = a->guidance;
-  s.dtype = a->dtype; s.pred_single = a->pred_single; s.video_scale = a->video_scale;
-  return s;
-}
+// The latents and the outputs are written while other threads still read the inputs: any overlap of the [n] f32 ranges is refused, not only
+// equal bases.  Every row must be disjoint from every column and from the rows after it; NULL overlaps nothing.  The one alias allowed is
+// acc_out == acc_in (element j is read, then written, by the same thread).
+struct NamedBuffer { const char* name; const float* p; };
+static const char kAccIn[] = "acc_in", kAccOut[] = "acc_out";
 
-extern "C" int64_t fyc_cfg_sigma_workspace_bytes(const fyc_cfg_sigma_args* a) {
-  CfgRescalePlan pl;
-  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->cfg) return 0;
-  const fyc_cfg_ddim_args s = cfg_sigma_guidance(a);
-  return cfg_rescale_plan(&s, pl) ? pl.bytes : 0;
-}
-
-template <typename T, bool RESCALE>
-static void cfg_sigma_launch(const fyc_cfg_sigma_args* a, const float* factor, hipStream_t st) {
-  const long long n = (long long)a->B * a->F * a->HW;
-  const dim3 grid(grid_for(n));
-  const T* pred = (const T*)a->pred;
-  const T* single = (const T*)a->pred_single;
-#define FYC_SIGMA_LAUNCH(ORDER)                                                                                                      \
-  hipLaunchKernelGGL((cfg_sigma_kernel<T, ORDER, RESCALE>), grid, dim3(256), 0, st, pred, a->latents, a->coef, a->B, a->F, a->HW,    \
-                     a->c_latent, a->ld, a->cfg, a->guidance, single, a->video_scale, a->hist_out, a->hist_1, a->hist_2, a->hist_3,  \
-                     a->noise, factor)
-  if (a->order == 1) FYC_SIGMA_LAUNCH(1);
-  else if (a->order == 2) FYC_SIGMA_LAUNCH(2);
-  else if (a->order == 3) FYC_SIGMA_LAUNCH(3);
-  else FYC_SIGMA_LAUNCH(4);
-#undef FYC_SIGMA_LAUNCH
-}
-
-template <typename T>
-static void cfg_sigma_dispatch(const fyc_cfg_sigma_args* a, const CfgRescalePlan* pl, hipStream_t st) {
-  if (pl == nullptr) return cfg_sigma_launch<T, false>(a, nullptr, st);
-  const fyc_cfg_ddim_args s = cfg_sigma_guidance(a);
-  cfg_sigma_launch<T, true>(a, cfg_rescale_factors<T>(&s, a->workspace, a->guidance_rescale, *pl, st), st);
-}
-
-extern "C" int fyc_cfg_sigma_step(const fyc_cfg_sigma_args* a, void* stream) {
-  FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_sigma_step: null pointer");
-  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_sigma_step: bad dims");
-  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_cfg_sigma_step: bad dtype %d", a->dtype);
-  FYC_REQUIRE(a->order >= 1 && a->order <= 4, "fyc_cfg_sigma_step: order %d (1 .. 4)", a->order);
-  FYC_REQUIRE(a->order < 2 || a->hist_1 != nullptr, "fyc_cfg_sigma_step: order %d needs hist_1", a->order);
-  FYC_REQUIRE(a->order < 3 || a->hist_2 != nullptr, "fyc_cfg_sigma_step: order %d needs hist_2", a->order);
-  FYC_REQUIRE(a->order < 4 || a->hist_3 != nullptr, "fyc_cfg_sigma_step: order 4 needs hist_3");
-  // hist_out and the latents are written while other threads still read the latents, the histories and the noise: any overlap of the
-  // [n] f32 ranges is refused, not only equal bases
-  const int64_t n = (int64_t)a->B * a->c_latent * a->F * a->HW;
+template <int n_rows, int n_cols>
+static int step_overlap_check(const StepCall& c, const NamedBuffer (&rows)[n_rows], const NamedBuffer (&cols)[n_cols]) {
+  const int64_t n = (int64_t)c.g.B * c.g.c_latent * c.g.F * c.g.HW;
   auto overlaps = [n](const float* p, const float* q) { return p != nullptr && q != nullptr && p < q + n && q < p + n; };
-  FYC_REQUIRE(!overlaps(a->hist_out, a->latents), "fyc_cfg_sigma_step: hist_out aliases latents");
-  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_1), "fyc_cfg_sigma_step: hist_out aliases hist_1");
-  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_2), "fyc_cfg_sigma_step: hist_out aliases hist_2");
-  FYC_REQUIRE(!overlaps(a->hist_out, a->hist_3), "fyc_cfg_sigma_step: hist_out aliases hist_3");
-  FYC_REQUIRE(!overlaps(a->noise, a->hist_out), "fyc_cfg_sigma_step: noise aliases hist_out");
-  FYC_REQUIRE(!overlaps(a->noise, a->latents), "fyc_cfg_sigma_step: noise aliases latents");
-  FYC_REQUIRE(!overlaps(a->noise, a->hist_1), "fyc_cfg_sigma_step: noise aliases hist_1");
-  FYC_REQUIRE(!overlaps(a->noise, a->hist_2), "fyc_cfg_sigma_step: noise aliases hist_2");
-  FYC_REQUIRE(!overlaps(a->noise, a->hist_3), "fyc_cfg_sigma_step: noise aliases hist_3");
-  FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_sigma_step: pred_single needs classifier-free guidance (cfg = 1)");
-  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_sigma_step: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
-  hipStream_t st = (hipStream_t)stream;
-  CfgRescalePlan pl;
-  const bool rescale = a->guidance_rescale > 0.f;
-  if (rescale) {
-    FYC_REQUIRE(a->cfg, "fyc_cfg_sigma_step: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
-    const fyc_cfg_ddim_args s = cfg_sigma_guidance(a);
-    FYC_REQUIRE(cfg_rescale_plan(&s, pl), "fyc_cfg_sigma_step: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)a->F * a->HW * a->c_latent);
-    FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_sigma_step: workspace is null or not 8-byte aligned");
-    FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_sigma_step: workspace_bytes %lld < %lld (fyc_cfg_sigma_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
-  }
-  FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_sigma_step: fyc_init() not called");
-  if (a->dtype == FYC_BF16) cfg_sigma_dispatch<bf16_t>(a, rescale ? &pl : nullptr, st);
-  else if (a->dtype == FYC_F16) cfg_sigma_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
-  else cfg_sigma_dispatch<float>(a, rescale ? &pl : nullptr, st);
-  FYC_CHECK_LAUNCH("fyc_cfg_sigma_step");
-  return 0;
-}
-
-// ---- PNDM (PLMS and Runge-Kutta modes): guidance (+ rescale) + update from the latents or the saved sample ------------------------
-static fyc_cfg_ddim_args cfg_pndm_guidance(const fyc_cfg_pndm_args* a) {
-  fyc_cfg_ddim_args s = {};
-  s.pred = a->pred; s.latents = a->latents; s.coef = a->coef;
-  s.B = a->B; s.F = a->F; s.HW = a->HW; s.c_latent = a->c_latent; s.ld = a->ld; s.cfg = a->cfg; s.guidance = a->guidance;
-  s.dtype = a->dtype; s.pred_single = a->pred_single; s.video_scale = a->video_scale;
-  return s;
-}
-
-extern "C" int64_t fyc_cfg_pndm_workspace_bytes(const fyc_cfg_pndm_args* a) {
-  CfgRescalePlan pl;
-  if (a == nullptr || !(a->guidance_rescale > 0.f && a->guidance_rescale <= 1.f) || !a->cfg) return 0;
-  const fyc_cfg_ddim_args s = cfg_pndm_guidance(a);
-  return cfg_rescale_plan(&s, pl) ? pl.bytes : 0;
-}
-
-template <typename T, bool RESCALE>
-static void cfg_pndm_launch(const fyc_cfg_pndm_args* a, const float* factor, hipStream_t st) {
-  const long long n = (long long)a->B * a->F * a->HW;
-  const dim3 grid(grid_for(n));
-  const T* pred = (const T*)a->pred;
-  const T* single = (const T*)a->pred_single;
-#define FYC_PNDM_LAUNCH(ORDER)                                                                                                       \
-  hipLaunchKernelGGL((cfg_pndm_kernel<T, ORDER, RESCALE>), grid, dim3(256), 0, st, pred, a->latents, a->coef, a->B, a->F, a->HW,     \
-                     a->c_latent, a->ld, a->cfg, a->guidance, single, a->video_scale, a->sample_in, a->sample_out, a->hist_out,      \
-                     a->hist_1, a->hist_2, a->hist_3, a->acc_in, a->acc_out, factor)
-  if (a->order == 1) FYC_PNDM_LAUNCH(1);
-  else if (a->order == 2) FYC_PNDM_LAUNCH(2);
-  else if (a->order == 3) FYC_PNDM_LAUNCH(3);
-  else FYC_PNDM_LAUNCH(4);
-#undef FYC_PNDM_LAUNCH
-}
-
-template <typename T>
-static void cfg_pndm_dispatch(const fyc_cfg_pndm_args* a, const CfgRescalePlan* pl, hipStream_t st) {
-  if (pl == nullptr) return cfg_pndm_launch<T, false>(a, nullptr, st);
-  const fyc_cfg_ddim_args s = cfg_pndm_guidance(a);
-  cfg_pndm_launch<T, true>(a, cfg_rescale_factors<T>(&s, a->workspace, a->guidance_rescale, *pl, st), st);
-}
-
-extern "C" int fyc_cfg_pndm_step(const fyc_cfg_pndm_args* a, void* stream) {
-  FYC_REQUIRE(a && a->pred && a->latents && a->coef, "fyc_cfg_pndm_step: null pointer");
-  FYC_REQUIRE(a->B > 0 && a->F > 0 && a->HW > 0 && a->c_latent > 0 && a->ld >= a->c_latent, "fyc_cfg_pndm_step: bad dims");
-  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16 || a->dtype == FYC_F32, "fyc_cfg_pndm_step: bad dtype %d", a->dtype);
-  FYC_REQUIRE(a->order >= 1 && a->order <= 4, "fyc_cfg_pndm_step: order %d (1 .. 4)", a->order);
-  FYC_REQUIRE(a->order < 2 || a->hist_1 != nullptr, "fyc_cfg_pndm_step: order %d needs hist_1", a->order);
-  FYC_REQUIRE(a->order < 3 || a->hist_2 != nullptr, "fyc_cfg_pndm_step: order %d needs hist_2", a->order);
-  FYC_REQUIRE(a->order < 4 || a->hist_3 != nullptr, "fyc_cfg_pndm_step: order 4 needs hist_3");
-  // the latents and the outputs are written while other threads still read the inputs: any overlap of the [n] f32 ranges is refused,
-  // not only equal bases.  The one alias allowed is acc_out == acc_in (element j is read, then written, by the same thread).
-  const int64_t n = (int64_t)a->B * a->c_latent * a->F * a->HW;
-  auto overlaps = [n](const float* p, const float* q) { return p != nullptr && q != nullptr && p < q + n && q < p + n; };
-  FYC_REQUIRE(!overlaps(a->sample_in, a->latents), "fyc_cfg_pndm_step: sample_in aliases latents");
-  const float* const outs[3] = {a->sample_out, a->hist_out, a->acc_out};
-  const char* const out_names[3] = {"sample_out", "hist_out", "acc_out"};
-  const float* const ins[6] = {a->latents, a->hist_1, a->hist_2, a->hist_3, a->sample_in, a->acc_in};
-  const char* const in_names[6] = {"latents", "hist_1", "hist_2", "hist_3", "sample_in", "acc_in"};
-  for (int o = 0; o < 3; ++o) {
-    for (int k = 0; k < 6; ++k) {
-      if (o == 2 && k == 5 && a->acc_out == a->acc_in) continue;
-      FYC_REQUIRE(!overlaps(outs[o], ins[k]), "fyc_cfg_pndm_step: %s aliases %s", out_names[o], in_names[k]);
+  for (int o = 0; o < n_rows; ++o) {
+    for (int k = 0; k < n_cols; ++k) {
+      if (rows[o].name == kAccOut && cols[k].name == kAccIn && rows[o].p == cols[k].p) continue;
+      FYC_REQUIRE(!overlaps(rows[o].p, cols[k].p), "%s: %s aliases %s", c.who, rows[o].name, cols[k].name);
     }
-    for (int k = o + 1; k < 3; ++k) FYC_REQUIRE(!overlaps(outs[o], outs[k]), "fyc_cfg_pndm_step: %s aliases %s", out_names[o], out_names[k]);
+    for (int k = o + 1; k < n_rows; ++k) FYC_REQUIRE(!overlaps(rows[o].p, rows[k].p), "%s: %s aliases %s", c.who, rows[o].name, rows[k].name);
   }
-  FYC_REQUIRE(a->pred_single == nullptr || a->cfg, "fyc_cfg_pndm_step: pred_single needs classifier-free guidance (cfg = 1)");
-  FYC_REQUIRE(a->guidance_rescale >= 0.f && a->guidance_rescale <= 1.f, "fyc_cfg_pndm_step: guidance_rescale %g (0 = off .. 1)", (double)a->guidance_rescale);
-  hipStream_t st = (hipStream_t)stream;
-  CfgRescalePlan pl;
-  const bool rescale = a->guidance_rescale > 0.f;
-  if (rescale) {
-    FYC_REQUIRE(a->cfg, "fyc_cfg_pndm_step: guidance_rescale %g needs classifier-free guidance (cfg = 1)", (double)a->guidance_rescale);
-    const fyc_cfg_ddim_args s = cfg_pndm_guidance(a);
-    FYC_REQUIRE(cfg_rescale_plan(&s, pl), "fyc_cfg_pndm_step: bad dims (F * HW * c_latent = %lld values per sample: 2 .. 2^31)", (long long)a->F * a->HW * a->c_latent);
-    FYC_REQUIRE(a->workspace != nullptr && ((uintptr_t)a->workspace & 7) == 0, "fyc_cfg_pndm_step: workspace is null or not 8-byte aligned");
-    FYC_REQUIRE(a->workspace_bytes >= pl.bytes, "fyc_cfg_pndm_step: workspace_bytes %lld < %lld (fyc_cfg_pndm_workspace_bytes)", (long long)a->workspace_bytes, (long long)pl.bytes);
-  }
-  FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_cfg_pndm_step: fyc_init() not called");
-  if (a->dtype == FYC_BF16) cfg_pndm_dispatch<bf16_t>(a, rescale ? &pl : nullptr, st);
-  else if (a->dtype == FYC_F16) cfg_pndm_dispatch<f16_t>(a, rescale ? &pl : nullptr, st);
-  else cfg_pndm_dispatch<float>(a, rescale ? &pl : nullptr, st);
-  FYC_CHECK_LAUNCH("fyc_cfg_pndm_step");
   return 0;
+}
+
+template <typename T, bool CONVERT, bool RESCALE>
+static void step_launch_order(const StepCall& c, const float* factor, hipStream_t st) {
+  const CfgOperands& g = c.g;
+  const dim3 grid(grid_for((long long)g.B * g.F * g.HW));
+  auto go = [&](auto order) {
+    hipLaunchKernelGGL((cfg_linear_step_kernel<T, decltype(order)::value, CONVERT, RESCALE>), grid, dim3(256), 0, st, (const T*)g.pred, g.latents,
+                       g.coef, g.B, g.F, g.HW, g.c_latent, g.ld, g.cfg, g.guidance, (const T*)g.pred_single, g.video_scale, c.buf, factor);
+  };
+  if (c.order == 1) go(std::integral_constant<int, 1>{});
+  else if (c.order == 2) go(std::integral_constant<int, 2>{});
+  else if (c.order == 3) go(std::integral_constant<int, 3>{});
+  else go(std::integral_constant<int, 4>{});
+}
+
+// the rescale factors if asked for (pl is the plan step_check made), then the step
+static int step_launch(const StepCall& c, const CfgRescalePlan& pl, void* stream) {
+  const bool rescale = c.guidance_rescale > 0.f;
+  FYC_REQUIRE(!(rescale || c.needs_init) || g_fyc_zero_page != nullptr, "%s: fyc_init() not called", c.who);
+  hipStream_t st = (hipStream_t)stream;
+  with_dtype(c.g.dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (rescale) {
+      const float* factor = cfg_rescale_factors<T>(c.g, c.workspace, c.guidance_rescale, pl, st);
+      c.convert ? step_launch_order<T, true, true>(c, factor, st) : step_launch_order<T, false, true>(c, factor, st);
+    } else {
+      c.convert ? step_launch_order<T, true, false>(c, nullptr, st) : step_launch_order<T, false, false>(c, nullptr, st);
+    }
+  });
+  FYC_CHECK_LAUNCH(c.who);
+  return 0;
+}
+
+template <typename A>
+static int64_t step_workspace_bytes(const A* a) {
+  return a ? rescale_workspace_bytes(a->B, a->F, a->HW, a->c_latent, a->ld, a->cfg, a->guidance_rescale) : 0;
+}
+
+extern "C" int64_t fyc_cfg_solver_workspace_bytes(const fyc_cfg_solver_args* a) { return step_workspace_bytes(a); }
+extern "C" int64_t fyc_cfg_sigma_workspace_bytes(const fyc_cfg_sigma_args* a) { return step_workspace_bytes(a); }
+extern "C" int64_t fyc_cfg_pndm_workspace_bytes(const fyc_cfg_pndm_args* a) { return step_workspace_bytes(a); }
+
+// DPM-Solver multistep: m0 = a_x x + a_v v is always stored; fyc_init() only for the guidance rescale
+extern "C" int fyc_cfg_solver_step(const fyc_cfg_solver_args* a, void* stream) {
+  FYC_REQUIRE(a && a->hist_out, "fyc_cfg_solver_step: null pointer");
+  StepCall c = step_call(*a, 3, true, false, "fyc_cfg_solver_step", "fyc_cfg_solver_workspace_bytes");
+  c.buf.hist_out = a->hist_out; c.buf.hist[0] = a->hist_1; c.buf.hist[1] = a->hist_2;
+  const NamedBuffer rows[] = {{"hist_out", a->hist_out}};
+  const NamedBuffer cols[] = {{"latents", a->latents}, {"hist_1", a->hist_1}, {"hist_2", a->hist_2}};
+  CfgRescalePlan pl;
+  if (int rc = step_check(c, pl)) return rc;
+  if (int rc = step_overlap_check(c, rows, cols)) return rc;
+  return step_launch(c, pl, stream);
+}
+
+// sigma-space samplers (Euler, Euler ancestral, LMS): the derivative d = a_x x + a_v v, optionally stored, and optional noise
+extern "C" int fyc_cfg_sigma_step(const fyc_cfg_sigma_args* a, void* stream) {
+  FYC_REQUIRE(a, "fyc_cfg_sigma_step: null pointer");
+  StepCall c = step_call(*a, 4, true, true, "fyc_cfg_sigma_step", "fyc_cfg_sigma_workspace_bytes");
+  c.buf.hist_out = a->hist_out; c.buf.hist[0] = a->hist_1; c.buf.hist[1] = a->hist_2; c.buf.hist[2] = a->hist_3; c.buf.noise = a->noise;
+  const NamedBuffer rows[] = {{"noise", a->noise}, {"hist_out", a->hist_out}};
+  const NamedBuffer cols[] = {{"latents", a->latents}, {"hist_1", a->hist_1}, {"hist_2", a->hist_2}, {"hist_3", a->hist_3}};
+  CfgRescalePlan pl;
+  if (int rc = step_check(c, pl)) return rc;
+  if (int rc = step_overlap_check(c, rows, cols)) return rc;
+  return step_launch(c, pl, stream);
+}
+
+// PNDM (PLMS and Runge-Kutta modes): the update from the latents or the saved sample, the raw guided prediction as history
+extern "C" int fyc_cfg_pndm_step(const fyc_cfg_pndm_args* a, void* stream) {
+  FYC_REQUIRE(a, "fyc_cfg_pndm_step: null pointer");
+  StepCall c = step_call(*a, 4, false, true, "fyc_cfg_pndm_step", "fyc_cfg_pndm_workspace_bytes");
+  c.buf.sample_in = a->sample_in; c.buf.sample_out = a->sample_out; c.buf.acc_in = a->acc_in; c.buf.acc_out = a->acc_out;
+  c.buf.hist_out = a->hist_out; c.buf.hist[0] = a->hist_1; c.buf.hist[1] = a->hist_2; c.buf.hist[2] = a->hist_3;
+  const NamedBuffer sample_in[] = {{"sample_in", a->sample_in}}, latents[] = {{"latents", a->latents}};
+  const NamedBuffer rows[] = {{"sample_out", a->sample_out}, {"hist_out", a->hist_out}, {kAccOut, a->acc_out}};
+  const NamedBuffer cols[] = {{"latents", a->latents}, {"hist_1", a->hist_1}, {"hist_2", a->hist_2}, {"hist_3", a->hist_3}, {"sample_in", a->sample_in}, {kAccIn, a->acc_in}};
+  CfgRescalePlan pl;
+  if (int rc = step_check(c, pl)) return rc;
+  if (int rc = step_overlap_check(c, sample_in, latents)) return rc;      // read where the latents are written
+  if (int rc = step_overlap_check(c, rows, cols)) return rc;
+  return step_launch(c, pl, stream);
 }
 
 extern "C" int fyc_nchw_to_nhwc(const fyc_nchw_in_args* a, void* stream) {

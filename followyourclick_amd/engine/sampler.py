@@ -49,10 +49,38 @@ def resolve_guidance_rescale(value=None) -> float:
 
 
 class DDIMSampler:
+    # What `sample`'s loop does with the caller's eta, generator, use_clipped_model_output and use_graph.  None: DDIM takes them as they are.
+    # A scheduler whose step() takes none of them (the reference's prepare_extra_step_kwargs drops them) and whose buffers change roles per
+    # step, so that nothing is replayed from a captured graph, says here whether it draws one noise tensor per step from the generator.
+    noise_per_step: Optional[bool] = None
+
     def __init__(self, unet: UNet3DEngine, ddim: DDIMConfig):
         self.unet = unet
         self.tables = DDIMTables(ddim)
         self.clip_sample = bool(ddim.clip_sample)
+
+    @staticmethod
+    def _check_rescale(st: dict, guidance_rescale) -> float:
+        phi = check_guidance_rescale(guidance_rescale)
+        if phi > 0 and not st["cfg"]:
+            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        return phi
+
+    @staticmethod
+    def _state_buffers(slot: dict, latents: Tensor, names) -> dict:
+        """the latent-shaped f32 buffers a sampler keeps in the clip's state, by name (a count: 0 .. count - 1): allocated when absent or of
+        another shape or device"""
+        names = range(names) if isinstance(names, int) else names
+        if any(k not in slot or slot[k].shape != latents.shape or slot[k].device != latents.device for k in names):
+            slot.update((k, torch.empty_like(latents)) for k in names)
+        return slot
+
+    @staticmethod
+    def _guidance_kwargs(st: dict, latents: Tensor, pred: Tensor, single: Optional[Tensor], phi: float) -> dict:
+        """the shape and guidance keywords every ops.cfg_*_step takes"""
+        B, CL, F, H, W = latents.shape
+        return dict(B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1], cfg=st["cfg"], guidance=st["guidance"], pred_single=single,
+                    video_scale=st.get("video_scale", 0.0), guidance_rescale=phi)
 
     def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool, start_index: int = 0):
         """-> (timesteps, the host coefficient table [n][.] f32, further per-clip entries of the state `prepare` returns).  start_index = k > 0:
@@ -191,9 +219,7 @@ class DDIMSampler:
                   pred_single=single, video_scale=st.get("video_scale", 0.0),
                   variance_noise=variance_noise, sigma=st["sigma"][i] if variance_noise is not None else 0.0,
                   clipped_model_output=use_clipped_model_output)
-        phi = check_guidance_rescale(guidance_rescale)
-        if phi > 0 and not st["cfg"]:
-            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        phi = self._check_rescale(st, guidance_rescale)
         if phi > 0:             # two more launches (moments, factor) in front of the step; an ops object without the method cannot run it
             o.cfg_ddim_step_rescaled(pred, latents, st["coef"][i], guidance_rescale=phi, **kw)
         else:
@@ -220,6 +246,9 @@ class DDIMSampler:
         scale_condition = False: a sigma-space scheduler's divisor reaches the latents only, not the mask and image channels of the concat
         input (the 2-D inpainting pipeline scales before it concatenates, pipeline_stable_diffusion_inpaint.py:699-703)."""
         u = self.unet
+        if self.noise_per_step is not None:
+            eta, use_clipped_model_output, use_graph = (1.0 if self.noise_per_step else 0.0), False, False
+            generator = generator if self.noise_per_step else None
         latents = latents.to(device=u.device, dtype=torch.float32).contiguous().clone()
         B, CL, F, H, W = latents.shape
         first = None if first_image_latents is None else first_image_latents.to(u.device, torch.float32).reshape(B, CL, H * W).contiguous()
@@ -294,6 +323,8 @@ class SolverSampler(DDIMSampler):
     those pointers change per step nothing is replayed from a captured graph.  eta, generator and use_clipped_model_output are accepted and
     unused, as the reference's prepare_extra_step_kwargs drops them for a scheduler whose step() does not take them; there is no clip_sample."""
 
+    noise_per_step = False
+
     def __init__(self, unet: UNet3DEngine, solver: SolverConfig):
         self.unet = unet
         self.tables = SolverTables(solver)
@@ -303,32 +334,20 @@ class SolverSampler(DDIMSampler):
         k = check_start_index(start_index, num_steps)
         ts = self.tables.timesteps(num_steps)[k:]
         coef_host = self.tables.coefficient_table(num_steps, k)          # (checks every step: a zero-SNR first step the family cannot take)
-        return ts, coef_host, dict(orders=self.tables.plan(num_steps, k), hist=[])
+        return ts, coef_host, dict(orders=self.tables.plan(num_steps, k), hist={})
 
     @torch.no_grad()
     def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
              variance_noise: Optional[Tensor] = None, use_clipped_model_output: bool = False,
              guidance_rescale: float = 0.0) -> None:
         """one solver step, latents (B,4,F,h,w) f32 updated in place; the steps of a clip are taken in order from i = 0 (the history is the state)"""
-        B, CL, F, H, W = latents.shape
-        phi = check_guidance_rescale(guidance_rescale)
-        if phi > 0 and not st["cfg"]:
-            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
-        hist = st["hist"]
-        if len(hist) != 3 or hist[0].shape != latents.shape or hist[0].device != latents.device:
-            hist[:] = [torch.empty_like(latents) for _ in range(3)]
+        phi = self._check_rescale(st, guidance_rescale)
+        hist = self._state_buffers(st["hist"], latents, 3)
         pred, single = self.predict(st, i, latents, first_image_latents, mask)
         order = st["orders"][i]
         self.unet.ops.cfg_solver_step(pred, latents, st["coef"][i], hist_out=hist[i % 3], hist_1=hist[(i - 1) % 3] if order >= 2 else None,
-                                      hist_2=hist[(i - 2) % 3] if order == 3 else None, order=order, B=B, F=F, HW=H * W, c_latent=CL,
-                                      ld=pred.shape[1], cfg=st["cfg"], guidance=st["guidance"], pred_single=single,
-                                      video_scale=st.get("video_scale", 0.0), guidance_rescale=phi)
-
-    @torch.no_grad()
-    def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float, *args, use_graph: Optional[bool] = None,
-               eta: float = 0.0, generator=None, use_clipped_model_output: bool = False, **kwargs) -> Tensor:
-        return super().sample(latents, text_embeddings, num_steps, guidance_scale, *args, use_graph=False, eta=0.0, generator=None,
-                              use_clipped_model_output=False, **kwargs)
+                                      hist_2=hist[(i - 2) % 3] if order == 3 else None, order=order,
+                                      **self._guidance_kwargs(st, latents, pred, single, phi))
 
 
 class SigmaSampler(DDIMSampler):
@@ -345,13 +364,14 @@ class SigmaSampler(DDIMSampler):
         self.tables = SigmaTables(sigma)
         self.clip_sample = False
         self.kind = sigma.kind
+        self.noise_per_step = sigma.kind == "euler_ancestral"      # (as the eta > 0 DDIM path draws it)
 
     def schedule(self, num_steps: int, eta: float, use_clipped_model_output: bool, start_index: int = 0):
         k = check_start_index(start_index, num_steps)
         ts = self.tables.timesteps(num_steps)[k:]
         coef_host = self.tables.coefficient_table(num_steps, k)          # (refuses a schedule over an infinite sigma)
         # (a sliced LMS run: the order of the step's place in the list, cut to the derivatives stored since entry k - SigmaTables.plan)
-        return ts, coef_host, dict(orders=self.tables.plan(num_steps, k), hist=[], input_denom=self.tables.input_denominators(num_steps)[k:])
+        return ts, coef_host, dict(orders=self.tables.plan(num_steps, k), hist={}, input_denom=self.tables.input_denominators(num_steps)[k:])
 
     @torch.no_grad()
     def step(self, st: dict, i: int, latents: Tensor, first_image_latents: Optional[Tensor], mask: Optional[Tensor],
@@ -359,30 +379,16 @@ class SigmaSampler(DDIMSampler):
              guidance_rescale: float = 0.0) -> None:
         """one step, latents (B,4,F,h,w) f32 updated in place; the steps of a clip are taken in order from i = 0 (LMS: the history is the state).
         variance_noise (latents' shape, f32): the noise of an ancestral step, scaled by the step's sigma_up"""
-        B, CL, F, H, W = latents.shape
-        phi = check_guidance_rescale(guidance_rescale)
-        if phi > 0 and not st["cfg"]:
-            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
+        phi = self._check_rescale(st, guidance_rescale)
         if (variance_noise is not None) != (self.kind == "euler_ancestral"):
             raise ValueError(f"the {self.kind} sampler takes {'a' if self.kind == 'euler_ancestral' else 'no'} noise tensor per step")
-        hist, hk = st["hist"], dict(order=1)
+        hk = dict(order=1)
         if self.kind == "lms":
-            if len(hist) != 4 or hist[0].shape != latents.shape or hist[0].device != latents.device:
-                hist[:] = [torch.empty_like(latents) for _ in range(4)]
-            order = st["orders"][i]
+            hist, order = self._state_buffers(st["hist"], latents, 4), st["orders"][i]
             hk = dict(order=order, hist_out=hist[i % 4], hist_1=hist[(i - 1) % 4] if order >= 2 else None,
                       hist_2=hist[(i - 2) % 4] if order >= 3 else None, hist_3=hist[(i - 3) % 4] if order >= 4 else None)
         pred, single = self.predict(st, i, latents, first_image_latents, mask, input_denom=st["input_denom"][i])
-        self.unet.ops.cfg_sigma_step(pred, latents, st["coef"][i], noise=variance_noise, B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1],
-                                     cfg=st["cfg"], guidance=st["guidance"], pred_single=single, video_scale=st.get("video_scale", 0.0),
-                                     guidance_rescale=phi, **hk)
-
-    @torch.no_grad()
-    def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float, *args, use_graph: Optional[bool] = None,
-               eta: float = 0.0, generator=None, use_clipped_model_output: bool = False, **kwargs) -> Tensor:
-        # (DDIMSampler.sample draws one noise tensor per step from `generator` exactly when its eta is positive: the ancestral kind's switch)
-        return super().sample(latents, text_embeddings, num_steps, guidance_scale, *args, use_graph=False,
-                              eta=1.0 if self.kind == "euler_ancestral" else 0.0, generator=generator, use_clipped_model_output=False, **kwargs)
+        self.unet.ops.cfg_sigma_step(pred, latents, st["coef"][i], noise=variance_noise, **hk, **self._guidance_kwargs(st, latents, pred, single, phi))
 
 
 class PNDMSampler(DDIMSampler):
@@ -394,6 +400,8 @@ class PNDMSampler(DDIMSampler):
     use_first_frame_condition `predict` pins frame 0 before the input build, so the saved sample is the pinned one, as in the reference.
     Nothing is replayed from a captured graph; eta, generator and use_clipped_model_output are accepted and unused, as the reference's
     prepare_extra_step_kwargs drops them for this scheduler; there is no clip_sample."""
+
+    noise_per_step = False
 
     def __init__(self, unet: UNet3DEngine, pndm: PNDMConfig):
         self.unet = unet
@@ -412,30 +420,16 @@ class PNDMSampler(DDIMSampler):
              guidance_rescale: float = 0.0) -> None:
         """evaluation i of the timestep list, latents (B,4,F,h,w) f32 updated in place; the evaluations of a clip are taken in order from
         i = 0 (the histories, the saved sample and the accumulator are the state)"""
-        B, CL, F, H, W = latents.shape
-        phi = check_guidance_rescale(guidance_rescale)
-        if phi > 0 and not st["cfg"]:
-            raise ValueError(f"guidance_rescale = {phi} needs classifier-free guidance (guidance_scale > 1)")
-        buf = st["buffers"]
-        if "sample" not in buf or buf["sample"].shape != latents.shape or buf["sample"].device != latents.device:
-            buf.update(hist=[torch.empty_like(latents) for _ in range(4)], sample=torch.empty_like(latents), acc=torch.empty_like(latents))
+        phi = self._check_rescale(st, guidance_rescale)
+        buf = self._state_buffers(st["buffers"], latents, (0, 1, 2, 3, "sample", "acc"))      # (the plan's slots: a history 0 .. 3 or "acc")
         ev = st["plan"][i]
-        slot = lambda s: buf["acc"] if s == "acc" else buf["hist"][s]      # noqa: E731
-        hists = [slot(s) for s in ev.hist] + [None] * (4 - ev.order)
+        hists = [buf[s] for s in ev.hist] + [None] * (4 - ev.order)
         pred, single = self.predict(st, i, latents, first_image_latents, mask)
         self.unet.ops.cfg_pndm_step(pred, latents, st["coef"][i], sample_in=buf["sample"] if ev.sample_in else None,
                                     sample_out=buf["sample"] if ev.sample_out else None,
-                                    hist_out=None if ev.hist_out is None else buf["hist"][ev.hist_out], hist_1=hists[0], hist_2=hists[1],
+                                    hist_out=None if ev.hist_out is None else buf[ev.hist_out], hist_1=hists[0], hist_2=hists[1],
                                     hist_3=hists[2], order=ev.order, acc_in=buf["acc"] if ev.acc_in else None,
-                                    acc_out=buf["acc"] if ev.acc_out else None, B=B, F=F, HW=H * W, c_latent=CL, ld=pred.shape[1],
-                                    cfg=st["cfg"], guidance=st["guidance"], pred_single=single, video_scale=st.get("video_scale", 0.0),
-                                    guidance_rescale=phi)
-
-    @torch.no_grad()
-    def sample(self, latents: Tensor, text_embeddings: Tensor, num_steps: int, guidance_scale: float, *args, use_graph: Optional[bool] = None,
-               eta: float = 0.0, generator=None, use_clipped_model_output: bool = False, **kwargs) -> Tensor:
-        return super().sample(latents, text_embeddings, num_steps, guidance_scale, *args, use_graph=False, eta=0.0, generator=None,
-                              use_clipped_model_output=False, **kwargs)
+                                    acc_out=buf["acc"] if ev.acc_out else None, **self._guidance_kwargs(st, latents, pred, single, phi))
 
 
 def make_sampler(unet: UNet3DEngine, scheduler_config) -> DDIMSampler:

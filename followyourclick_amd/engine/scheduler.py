@@ -41,6 +41,29 @@ def alpha_add_noise_coefficients(alphas_cumprod: torch.Tensor, t) -> tuple:
     return float(a_t ** 0.5), float((1 - a_t) ** 0.5)
 
 
+def betas_from_config(cfg, who: str) -> torch.Tensor:
+    """the f32 betas of a scheduler config: trained_betas, or the linear / scaled_linear schedule, then the zero-terminal-SNR rescale if asked
+    for.  who: the tables class, named where the schedule is refused"""
+    n = cfg.num_train_timesteps
+    if cfg.trained_betas is not None:
+        betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
+    elif cfg.beta_schedule == "linear":
+        betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
+    elif cfg.beta_schedule == "scaled_linear":
+        betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
+    else:
+        raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for {who}")
+    return rescale_zero_terminal_snr(betas) if cfg.rescale_betas_zero_snr else betas
+
+
+class AlphaAddNoise:
+    """add_noise of the schedulers whose latents live in alpha space (DDIM, DPM-Solver, PNDM), from their alphas_cumprod table"""
+
+    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
+        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
+        return alpha_add_noise_coefficients(self.alphas_cumprod, t)
+
+
 def check_start_index(start_index, entries: int) -> int:
     """the first entry of the scheduler's timestep list a sliced run takes (what `strength` selects): 0 .. entries - 1"""
     k = int(start_index)
@@ -49,20 +72,10 @@ def check_start_index(start_index, entries: int) -> int:
     return k
 
 
-class DDIMTables:
+class DDIMTables(AlphaAddNoise):
     def __init__(self, cfg: DDIMConfig):
         self.cfg = cfg
-        n = cfg.num_train_timesteps
-        if cfg.trained_betas is not None:
-            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
-        elif cfg.beta_schedule == "linear":
-            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
-        elif cfg.beta_schedule == "scaled_linear":
-            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for DDIMTables")
-        if cfg.rescale_betas_zero_snr:
-            betas = rescale_zero_terminal_snr(betas)
+        betas = betas_from_config(cfg, "DDIMTables")
         self.betas = betas
         self.alphas = 1.0 - betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
@@ -119,12 +132,8 @@ class DDIMTables:
         ts = self.timesteps(num_inference_steps).tolist()
         return torch.tensor([self.step_coefficients(t, num_inference_steps, eta) for t in ts], dtype=torch.float32)
 
-    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
-        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
-        return alpha_add_noise_coefficients(self.alphas_cumprod, t)
 
-
-class SolverTables:
+class SolverTables(AlphaAddNoise):
     """DPM-Solver multistep on the host (reference diffusers/schedulers/scheduling_dpmsolver_multistep.py; arXiv:2206.00927, arXiv:2211.01095).
 
     alpha_t, sigma_t and lambda_t are the reference's f32 op sequence (:165-170), bit-identical tables.  Every update of the family is linear in
@@ -139,19 +148,9 @@ class SolverTables:
 
     def __init__(self, cfg: SolverConfig):
         self.cfg = cfg
-        n = cfg.num_train_timesteps
         if cfg.thresholding:
             raise NotImplementedError("thresholding=True (dynamic thresholding, a per-sample quantile of x0) is not implemented for SolverTables")
-        if cfg.trained_betas is not None:
-            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
-        elif cfg.beta_schedule == "linear":
-            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
-        elif cfg.beta_schedule == "scaled_linear":
-            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for SolverTables")
-        if cfg.rescale_betas_zero_snr:
-            betas = rescale_zero_terminal_snr(betas)
+        betas = betas_from_config(cfg, "SolverTables")
         if cfg.algorithm_type not in ("dpmsolver", "dpmsolver++"):
             raise NotImplementedError(f"{cfg.algorithm_type} is not implemented for SolverTables")
         if cfg.solver_type not in ("midpoint", "heun"):
@@ -276,10 +275,6 @@ class SolverTables:
         return torch.tensor([self.step_coefficients(ts, start_index + j, o) for j, o in enumerate(self.plan(num_inference_steps, start_index))],
                             dtype=torch.float64).float()
 
-    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
-        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
-        return alpha_add_noise_coefficients(self.alphas_cumprod, t)
-
 
 SIGMA_KINDS = ("euler", "euler_ancestral", "lms")
 
@@ -302,21 +297,11 @@ class SigmaTables:
 
     def __init__(self, cfg: SigmaConfig):
         self.cfg = cfg
-        n = cfg.num_train_timesteps
         if cfg.kind not in SIGMA_KINDS:
             raise ValueError(f"kind given as {cfg.kind!r} must be one of {SIGMA_KINDS}")
-        if cfg.trained_betas is not None:
-            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
-        elif cfg.beta_schedule == "linear":
-            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
-        elif cfg.beta_schedule == "scaled_linear":
-            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for SigmaTables")
+        betas = betas_from_config(cfg, "SigmaTables")
         if cfg.prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"prediction_type given as {cfg.prediction_type} must be one of `epsilon`, or `v_prediction`")
-        if cfg.rescale_betas_zero_snr:
-            betas = rescale_zero_terminal_snr(betas)
         self.betas = betas
         self.alphas = 1.0 - betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
@@ -431,7 +416,7 @@ PNDMEval = namedtuple("PNDMEval", ["counter", "timestep", "prev_timestep", "orde
 PLMS_WEIGHTS = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}      # Adams-Bashforth (:323-335)
 
 
-class PNDMTables:
+class PNDMTables(AlphaAddNoise):
     """PNDM on the host, PLMS mode (skip_prk_steps, what Stable Diffusion 1.x ships) and Runge-Kutta mode (reference diffusers/schedulers/
     scheduling_pndm.py; arXiv:2202.09778).
 
@@ -453,19 +438,9 @@ class PNDMTables:
 
     def __init__(self, cfg: PNDMConfig):
         self.cfg = cfg
-        n = cfg.num_train_timesteps
-        if cfg.trained_betas is not None:
-            betas = torch.tensor(cfg.trained_betas, dtype=torch.float32)
-        elif cfg.beta_schedule == "linear":
-            betas = torch.linspace(cfg.beta_start, cfg.beta_end, n, dtype=torch.float32)
-        elif cfg.beta_schedule == "scaled_linear":
-            betas = torch.linspace(cfg.beta_start ** 0.5, cfg.beta_end ** 0.5, n, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{cfg.beta_schedule} is not implemented for PNDMTables")
+        betas = betas_from_config(cfg, "PNDMTables")
         if cfg.prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"prediction_type given as {cfg.prediction_type} must be one of `epsilon` or `v_prediction`")
-        if cfg.rescale_betas_zero_snr:
-            betas = rescale_zero_terminal_snr(betas)
         self.betas = betas
         self.alphas = 1.0 - betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
@@ -557,7 +532,3 @@ class PNDMTables:
         if not torch.isfinite(tab).all():
             raise ValueError(f"the PNDM schedule of {num_inference_steps} steps has a non-finite coefficient")
         return tab
-
-    def add_noise_coefficients(self, t, num_inference_steps: int = None) -> tuple:
-        """(c_x, c_n) of add_noise at timestep t: x_t = c_x x_0 + c_n noise"""
-        return alpha_add_noise_coefficients(self.alphas_cumprod, t)

@@ -586,17 +586,35 @@ class HipOps:
         self._call("fyc_cfg_ddim_step", a)
 
     @staticmethod
+    def _fill_cfg_common(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_single, video_scale, who, shaped=()) -> None:
+        """the fields every cfg step's arguments start with; `shaped`: (name, tensor or None) pairs that must have the latents' size"""
+        for name, t in shaped:
+            if t is not None and t.numel() != latents.numel():
+                raise ValueError(f"{who}: {name} must have the latents' shape")
+        if pred_single is not None and pred_single.dtype != pred.dtype:
+            raise TypeError(f"{who}: pred_single dtype differs from pred")
+        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
+        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
+        a.pred_single, a.video_scale = _p(pred_single), video_scale
+
+    def _rescale_workspace(self, key, query: str, args, device: torch.device) -> None:
+        """args.workspace / .workspace_bytes <- the moments workspace of the guidance rescale, if `query` (asked once per key) wants one: this
+        object's one buffer (a fixed address under a captured graph), grown on demand"""
+        need = self._ws_need.get(key)
+        if need is None:
+            need = self._ws_need[key] = int(getattr(self.lib, query)(C.byref(args)))
+        if need > 0:
+            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != device:
+                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=device)
+            args.workspace, args.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+
+    @staticmethod
     def _fill_cfg_ddim(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_type, clip_sample, pred_single, video_scale,
                        variance_noise, sigma, clipped_model_output) -> None:
-        if variance_noise is not None and variance_noise.numel() != latents.numel():
-            raise ValueError("cfg_ddim_step: variance_noise must have the latents' shape")
+        HipOps._fill_cfg_common(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_single, video_scale, "cfg_ddim_step",
+                                [("variance_noise", variance_noise)])
         a.variance_noise, a.sigma, a.clipped_model_output = _f32(variance_noise, "variance_noise"), float(sigma), int(clipped_model_output)
-        if pred_single is not None and pred_single.dtype != pred.dtype:
-            raise TypeError("cfg_ddim_step: pred_single dtype differs from pred")
-        a.pred_single, a.video_scale = _p(pred_single), video_scale
-        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
-        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance = B, F, HW, c_latent, ld, int(cfg), guidance
-        a.pred_type, a.clip_sample, a.dtype = pred_type, int(clip_sample), _dt(pred)
+        a.pred_type, a.clip_sample = pred_type, int(clip_sample)
 
     def cfg_ddim_step_rescaled(self, pred: Tensor, latents: Tensor, coef: Tensor, *, guidance_rescale: float, B: int, F: int, HW: int,
                                c_latent: int, ld: int, cfg: bool, guidance: float, pred_type: int, clip_sample: bool,
@@ -610,14 +628,8 @@ class HipOps:
         self._fill_cfg_ddim(r.step, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_type, clip_sample, pred_single,
                             video_scale, variance_noise, sigma, clipped_model_output)
         r.guidance_rescale = float(guidance_rescale)
-        key = ("cfg_rescale", B, F, HW, c_latent, ld, r.guidance_rescale > 0, bool(cfg))
-        need = self._ws_need.get(key)
-        if need is None:
-            need = self._ws_need[key] = int(self.lib.fyc_cfg_ddim_rescale_workspace_bytes(C.byref(r)))
-        if need > 0:
-            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
-                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
-            r.workspace, r.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._rescale_workspace(("cfg_rescale", B, F, HW, c_latent, ld, r.guidance_rescale > 0, bool(cfg)), "fyc_cfg_ddim_rescale_workspace_bytes", r,
+                                pred.device)
         self._call("fyc_cfg_ddim_step_rescaled", r)
 
     def cfg_solver_step(self, pred: Tensor, latents: Tensor, coef: Tensor, *, hist_out: Tensor, hist_1: Optional[Tensor] = None,
@@ -630,25 +642,12 @@ class HipOps:
         self.ensure_init(pred.device)
         if coef.numel() < 8:
             raise ValueError(f"cfg_solver_step: coef holds {coef.numel()} values, the kernel's table row has 8")
-        for name, h in (("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2)):
-            if h is not None and h.numel() != latents.numel():
-                raise ValueError(f"cfg_solver_step: {name} must have the latents' shape")
-        if pred_single is not None and pred_single.dtype != pred.dtype:
-            raise TypeError("cfg_solver_step: pred_single dtype differs from pred")
         a = L.CfgSolverArgs()
-        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
-        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
-        a.pred_single, a.video_scale = _p(pred_single), video_scale
+        self._fill_cfg_common(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_single, video_scale, "cfg_solver_step",
+                              [("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2)])
         a.hist_out, a.hist_1, a.hist_2, a.order = _f32(hist_out, "hist_out"), _f32(hist_1, "hist_1"), _f32(hist_2, "hist_2"), int(order)
         a.guidance_rescale = float(guidance_rescale)
-        key = ("cfg_solver", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg))
-        need = self._ws_need.get(key)
-        if need is None:
-            need = self._ws_need[key] = int(self.lib.fyc_cfg_solver_workspace_bytes(C.byref(a)))
-        if need > 0:
-            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
-                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
-            a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._rescale_workspace(("cfg_solver", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg)), "fyc_cfg_solver_workspace_bytes", a, pred.device)
         self._call("fyc_cfg_solver_step", a)
 
     def cfg_sigma_step(self, pred: Tensor, latents: Tensor, coef: Tensor, *, hist_out: Optional[Tensor] = None, hist_1: Optional[Tensor] = None,
@@ -662,26 +661,13 @@ class HipOps:
         self.ensure_init(pred.device)
         if coef.numel() < 8:
             raise ValueError(f"cfg_sigma_step: coef holds {coef.numel()} values, the kernel's table row has 8")
-        for name, h in (("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2), ("hist_3", hist_3), ("noise", noise)):
-            if h is not None and h.numel() != latents.numel():
-                raise ValueError(f"cfg_sigma_step: {name} must have the latents' shape")
-        if pred_single is not None and pred_single.dtype != pred.dtype:
-            raise TypeError("cfg_sigma_step: pred_single dtype differs from pred")
         a = L.CfgSigmaArgs()
-        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
-        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
-        a.pred_single, a.video_scale = _p(pred_single), video_scale
+        self._fill_cfg_common(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_single, video_scale, "cfg_sigma_step",
+                              [("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2), ("hist_3", hist_3), ("noise", noise)])
         a.hist_out, a.hist_1, a.hist_2, a.hist_3 = _f32(hist_out, "hist_out"), _f32(hist_1, "hist_1"), _f32(hist_2, "hist_2"), _f32(hist_3, "hist_3")
         a.order, a.noise = int(order), _f32(noise, "noise")
         a.guidance_rescale = float(guidance_rescale)
-        key = ("cfg_sigma", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg))
-        need = self._ws_need.get(key)
-        if need is None:
-            need = self._ws_need[key] = int(self.lib.fyc_cfg_sigma_workspace_bytes(C.byref(a)))
-        if need > 0:
-            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
-                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
-            a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._rescale_workspace(("cfg_sigma", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg)), "fyc_cfg_sigma_workspace_bytes", a, pred.device)
         self._call("fyc_cfg_sigma_step", a)
 
     def cfg_pndm_step(self, pred: Tensor, latents: Tensor, coef: Tensor, *, sample_in: Optional[Tensor] = None, sample_out: Optional[Tensor] = None,
@@ -696,28 +682,15 @@ class HipOps:
         self.ensure_init(pred.device)
         if coef.numel() < 6:
             raise ValueError(f"cfg_pndm_step: coef holds {coef.numel()} values, the kernel's table row has 6")
-        for name, h in (("sample_in", sample_in), ("sample_out", sample_out), ("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2),
-                        ("hist_3", hist_3), ("acc_in", acc_in), ("acc_out", acc_out)):
-            if h is not None and h.numel() != latents.numel():
-                raise ValueError(f"cfg_pndm_step: {name} must have the latents' shape")
-        if pred_single is not None and pred_single.dtype != pred.dtype:
-            raise TypeError("cfg_pndm_step: pred_single dtype differs from pred")
         a = L.CfgPndmArgs()
-        a.pred, a.latents, a.coef = _p(pred), _f32(latents, "latents"), _f32(coef, "coef")
-        a.B, a.F, a.HW, a.c_latent, a.ld, a.cfg, a.guidance, a.dtype = B, F, HW, c_latent, ld, int(cfg), guidance, _dt(pred)
-        a.pred_single, a.video_scale = _p(pred_single), video_scale
+        self._fill_cfg_common(a, pred, latents, coef, B, F, HW, c_latent, ld, cfg, guidance, pred_single, video_scale, "cfg_pndm_step",
+                              [("sample_in", sample_in), ("sample_out", sample_out), ("hist_out", hist_out), ("hist_1", hist_1), ("hist_2", hist_2),
+                               ("hist_3", hist_3), ("acc_in", acc_in), ("acc_out", acc_out)])
         a.sample_in, a.sample_out = _f32(sample_in, "sample_in"), _f32(sample_out, "sample_out")
         a.hist_out, a.hist_1, a.hist_2, a.hist_3 = _f32(hist_out, "hist_out"), _f32(hist_1, "hist_1"), _f32(hist_2, "hist_2"), _f32(hist_3, "hist_3")
         a.order, a.acc_in, a.acc_out = int(order), _f32(acc_in, "acc_in"), _f32(acc_out, "acc_out")
         a.guidance_rescale = float(guidance_rescale)
-        key = ("cfg_pndm", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg))
-        need = self._ws_need.get(key)
-        if need is None:
-            need = self._ws_need[key] = int(self.lib.fyc_cfg_pndm_workspace_bytes(C.byref(a)))
-        if need > 0:
-            if self._rescale_ws is None or self._rescale_ws.numel() < need or self._rescale_ws.device != pred.device:
-                self._rescale_ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
-            a.workspace, a.workspace_bytes = self._rescale_ws.data_ptr(), self._rescale_ws.numel()
+        self._rescale_workspace(("cfg_pndm", B, F, HW, c_latent, ld, a.guidance_rescale > 0, bool(cfg)), "fyc_cfg_pndm_workspace_bytes", a, pred.device)
         self._call("fyc_cfg_pndm_step", a)
 
     def unet_input_scaled(self, latents: Tensor, mask: Optional[Tensor], first: Optional[Tensor], x: Tensor, *, denom: float, scale_cond: bool,

@@ -20,6 +20,8 @@ STRUCTS = {
     "fyc_pack_conv3x3_args": "PackConv3x3Args", "fyc_pack_geglu_args": "PackGegluArgs",
     "fyc_temporal_block_args": "TemporalBlockArgs", "fyc_ff_block_args": "FFBlockArgs",
     "fyc_panel_linear_args": "PanelLinearArgs",
+    "fyc_cfg_ddim_rescale_args": "CfgDdimRescaleArgs", "fyc_cfg_solver_args": "CfgSolverArgs", "fyc_cfg_sigma_args": "CfgSigmaArgs",
+    "fyc_cfg_pndm_args": "CfgPndmArgs", "fyc_unet_input_scaled_args": "UnetInputScaledArgs",
 }
 
 
