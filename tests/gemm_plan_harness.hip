@@ -15,9 +15,10 @@
 // Second mode (tests/test_gemm_cases.py): `gemm_plan_harness <file>` (`-` = stdin) plans the cases of that file instead of the grid, one per
 // line: a name without blanks, then key=value fields (tests/gemm_cases.py::harness_line writes them; an unknown key is an error, exit 4).
 //   scalars:   dtype mode M N K lda ldw ldo ldr ldrb rpb tile batch stride_a stride_w stride_o cs_rows
-//              Hout Wout Hin Win Cin stride pad t3_frames t3_rows
-//   operands:  bias rowbias residual chan = 1 (present) / 0; residual = 2: the residual IS the output (in-place add)
+//              Hout Wout Hin Win Cin stride pad t3_frames t3_rows epilogue act ln_nparts k_split lda2 seg_cols heads tokens
+//   operands:  bias rowbias residual chan a2 = 1 (present) / 0; residual = 2: the residual IS the output (in-place add); ln = 1: ln_stats and ln_colsum
 //   offsets:   out_off rb_off res_off = bytes added to the made-up 256-byte aligned address of that operand
+//   segments:  seg_tr seg_ld seg_off = comma-separated seg_transposed / seg_ld / byte offset of seg_out, one entry per segment of the HEADS epilogue
 //   tuning:    tune=<key>:<value>, may repeat; reset after the case
 //   answer:    <name> | <launch, as above> | <executed cfg> <executed rows>x<columns> | <rc> [message]
 // Without an argument the output is the table above, byte for byte.
@@ -223,8 +224,26 @@ bool parse_case(const std::string& line, Case& c, std::string& why) {
       c.tuning.push_back({atoi(vs.substr(0, colon).c_str()), atoi(vs.substr(colon + 1).c_str())});
       continue;
     }
+    if (k == "seg_tr" || k == "seg_ld" || k == "seg_off") {      // comma-separated, one entry per segment
+      int s = 0;
+      for (size_t i = 0; i <= vs.size() && s < 3; ++s) {
+        size_t j = vs.find(',', i);
+        if (j == std::string::npos) j = vs.size();
+        const long long e = atoll(vs.substr(i, j - i).c_str());
+        if (k == "seg_tr") a.seg_transposed[s] = (int)e;
+        else if (k == "seg_ld") a.seg_ld[s] = (int)e;
+        else a.seg_out[s] = (char*)fake(P_SEG + s) + e;
+        i = j + 1;
+      }
+      continue;
+    }
     const long long v = atoll(vs.c_str());
-    if (k == "dtype") a.dtype = (int)v; else if (k == "mode") a.mode = (int)v;
+    if (k == "epilogue") a.epilogue = (int)v; else if (k == "act") a.act = (int)v;
+    else if (k == "ln") { a.ln_stats = v ? (const float*)fake(P_LNS) : nullptr; a.ln_colsum = v ? (const float*)fake(P_LNC) : nullptr; a.ln_eps = 1e-5f; }
+    else if (k == "ln_nparts") a.ln_nparts = (int)v;
+    else if (k == "a2") a.a2 = v ? fake(P_A2) : nullptr; else if (k == "k_split") a.k_split = (int)v; else if (k == "lda2") a.lda2 = (int)v;
+    else if (k == "seg_cols") a.seg_cols = (int)v; else if (k == "heads") a.heads = (int)v; else if (k == "tokens") a.tokens = (int)v;
+    else if (k == "dtype") a.dtype = (int)v; else if (k == "mode") a.mode = (int)v;
     else if (k == "M") a.M = (int)v; else if (k == "N") a.N = (int)v; else if (k == "K") a.K = (int)v;
     else if (k == "lda") a.lda = (int)v; else if (k == "ldw") a.ldw = (int)v; else if (k == "ldo") a.ldo = (int)v;
     else if (k == "ldr") a.ldr = (int)v; else if (k == "ldrb") a.ldrb = (int)v; else if (k == "rpb") a.rows_per_batch = (int)v;

@@ -121,6 +121,37 @@ profiles/row_panel_bound_coverage.txt.
     kernel does), and the reference's own rounded weights are within r sum w |v| of the exact ones.  The attention output is rounded to T on both sides: charged by the boundary
     test with e = rest + r sum_j w_j |v_j|, which in practice charges every element.  Output projection over 8 heads x 64 k-slots, bias and residual:
         out: ulp_T(ref) + (512 + 8) u (|x| + |O_T| |Wo|^T + |b_out|) + charge_O |Wo|^T.
+
+The other epilogues of fyc_gemm (csrc/gemm_kernel.h: GEGLU, head split, LINEAR with an activation, the folded LayerNorm in each of them, dual-source K, the unsplit frame-axis
+convolution).  The bounds are computed in tests/gemm_cases.py::analysis beside the reference of EmuOps(acc=float64) - exact-erf GELU, the exact fold, x sigmoid(1.702 x); never a copy
+of the kernel's polynomial - and handed to compare() as `bound` with lines=True; u = 2^-24, the constant is 1, ulp_T(ref) is added for the store, no element is exempt.
+  Pre-activation: pre = acc + bias with acc an f32 sum of K products (of two sources, of three gathered taps: the operand's indexing does not change the count):
+        E = (K + 8) u S,  S = |a| |W|^T + |bias|,  as element_bound has it.
+  Fold: pre = rs (acc - mu cs) + bias.  The narrow and the LDS-staged forms (:938, :1062, :1081, :1186) round mu cs, the difference, the product with rs and the sum with the bias; the
+    pack-first forms (:434, :645, :777) round nm = -rs mu, the inner fma(nm, cs, bias) and the outer fma(acc, rs, .), the head split also rs scale and scale * (.): at most five
+    roundings, each on a partial sum no larger than S = rs (|a| |W|^T + |mu cs|) + |bias|, and the K roundings of acc come through rs: E = (K + 8) u S again, with this S.  With
+    |mean| / std = 4 the term |mu cs| is several times the output: the cancellation is in S, not assumed away.  Stored {mean, rstd} pairs are the same f32 numbers on both sides.
+    ln_nparts (ln_row, :272-277): n - 1 f32 additions per sum, inv = 1.0f / K (u) and one product each (u): dmu = (n - 1) u sum |s_i| / K + 2 u |mu|;  dvar = (n + 1) u q / K +
+    2 |mu| dmu + u mu^2, the subtraction and + eps and rsqrtf at its documented 1 ulp charged as norm_cases.norm_rho charges rstd: drs = rs rho.  These are distances from the
+    EXACT statistics of the f32 partials; the reference (EmuOps.gemm) evaluates them in f32 too, in torch's order, and its own distance from the exact ones is computed and added.
+        E += drs |acc - mu cs| + rs dmu |cs|.
+  LINEAR (lnfold, dualk, t3) and HEADS: out = (pre + res) scale: the residual and the scale are two more of the K + 8 roundings, ulp_T(ref) + (K + 8) u |scale| (S + |res|) (+ |scale|
+    times the ln_nparts term).  The head split only moves elements: each segment is a window of its own with this bound.
+  GEGLU, 16-bit wide forms (geglu_pair, csrc/fyc_common.h:221): h = v (g Phi_p(g)), exactly the gate of fyc_ff_block: row_panel_cases.PHI_ERR, phi_rounding and DG are reused,
+        e = dv |g Phi(g)| + |v| (DG dg + |g| (PHI_ERR + rnd(g))) + DG dv dg + 3 u |h|,  dv, dg = E of the value and the gate column.
+  gelu_erf_f (fyc_common.h:190; the narrow GEGLU, f32, and act = 1): GELU_AS_ERR = max |gelu_erf_f - x Phi(x)| of the Abramowitz-Stegun form itself, evaluated in f64 with the
+    source's f32 constants on a grid of 2^21 points over |x| <= 12 against torch.special.erf: 2.12e-7 (beyond 12 both sides are x or 0).  Its f32 evaluation is a running first-order
+    bound that follows the source operation by operation (gemm_cases.gelu_as): z = |g| c (u), fma(p, z, 1) (u), rcp (1 ulp = 2 u), four Horner fma (u each), poly t (u), z z (u),
+    __expf = exp2(x log2e) - the product (u |x|), log2e as an f32 constant (0.25 u |x|), the instruction (2 u) -, the product with it (u), 2 - e (u), the last product (u).
+        GEGLU: e = dv |gelu(g)| + |v| (DG dg + GELU_AS_ERR + rnd_as(g)) + DG dv dg + u |h|;        act = 1: e_y = DG E + GELU_AS_ERR + rnd_as(pre).
+  Quick-GELU (activate, :187): y = x / (1 + __expf(-1.702f x)).  a = 1.702 x; exp(-a) is off by r = |a| (2.25 u + |1.702f / 1.702 - 1|) + 2 u relative - the rounded product, the
+    product and the constant inside __expf, the kernel's f32 constant against the reference's 1.702, the instruction - and moves y by |x| E / (1 + E)^2 r; the addition and the
+    division (correctly rounded) are u |y| each.  Slope DQ = 1.10 >= |d/dx x sigmoid(1.702 x)| (1.0998 on a grid, as DG = 1.13 >= 1.1290):  e_y = DQ E + that.
+  After the activation: out = (y + res) scale, two roundings:  ulp_T(ref) + |scale| (e_y + 2 u (|y| + |res|)).
+  A condition on the INPUTS of the GEGLU cases: gates centred on +1.5.  In f16 the polynomial's 1.4e-4 on Phi alone puts a row or column of mostly negative gates at the line
+    tolerance of 5e-4 (gemm_cases.epilogue_operands has the arithmetic); the per-element bound holds for either sign and 7 % of the gates stay negative.
+A torch model of every form stays inside these bounds, every declared single-site defect leaves them or trips the guard, and the slopes and approximation errors are evaluated on
+grids (tests/test_gemm_epilogue_cases.py); what the MI355X measured is part 4 of profiles/gemm_epilogue_coverage.txt.
 """
 import math
 from collections import namedtuple

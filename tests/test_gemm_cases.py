@@ -5,6 +5,7 @@ The GPU tests (tests/test_gemm_epilogues_gpu.py) parametrise from the same list,
 its name says: that is what had happened to the 16-bit sweeps of test_gemm_plain / test_gemm_conv, whose arguments are pinned here too."""
 import os
 import subprocess
+from dataclasses import replace
 
 import pytest
 
@@ -59,26 +60,95 @@ def test_case_launches_what_it_declares(recorded, case):
     if case.want_wide and case.tile in (8, 10) and not (case.rowbias and case.rpb % 128 != 0):
         assert r["cfg"] == case.tile, r["line"]      # (with row-bias groups to stage, the 128-byte twins 6 / 1 run: gemm_cases.py)
     fam = {"f32": "f32", "bf16": "bf16_", "f16": "f16_"}[case.dt]
-    assert r["fam"].startswith(fam) and r["fam"].endswith({G.PLAIN: ("plain", "f32"), G.CONV: ("conv", "f32"), G.UP2: ("conv", "f32"), G.T3: ("t3",)}[case.mode]), r["line"]
+    ends = ("act", "f32") if case.act else {G.PLAIN: ("plain", "f32"), G.CONV: ("conv", "f32"), G.UP2: ("conv", "f32"), G.T3: ("t3",)}[case.mode]
+    assert r["fam"].startswith(fam) and r["fam"].endswith(ends), r["line"]
+    if case.group == "geglu" and case.want_wide and case.tile in G.GEGLU_REPLACED:
+        assert r["asked_cfg"] == r["cfg"] == G.GEGLU_REPLACED[case.tile], r["line"]      # (the planner replaces the tile: gemm_plan.h::geglu_tile)
+    if case.group == "act" and case.want_wide:
+        assert r["cfg"] == G.ACT_WIDE_TILES.get(r["asked_cfg"], 2), r["line"]             # (the family builds 1, 2 and 6: the entry folds the planned tile)
 
 
 @pytest.mark.parametrize("mode,tiles,extra", [(G.PLAIN, PLAIN_TILES, G.EXTRA_PLAIN_RINGS), (G.CONV, CONV_TILES, []), (G.UP2, CONV_TILES, [])])
 def test_every_tile_of_the_sweeps_is_executed_wide(recorded, mode, tiles, extra):
     """across the wide, unsplit cases of a mode the executed (tile config, ring depth) are exactly the sweep's list (tile 0 being the automatic
     choice) and the f16 subset's (F16_TILES has (1, 2) and (2, 2), which CONV_TILES leaves out), plus in PLAIN mode the two deeper rings of the 128x64 linears"""
-    executed = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in CASES if c.mode == mode and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
+    sweep = [c for c in CASES if c.group in G.LINEAR_GROUPS]      # (the groups of the other epilogues: test_new_groups_execute_exactly_their_declared_wide_tiles)
+    executed = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in sweep if c.mode == mode and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
     want = {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles + F16_TILES} | set(extra)
     assert executed == want, (sorted(executed - want), sorted(want - executed))
-    bf16 = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in CASES if c.mode == mode and c.dt == "bf16" and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
+    bf16 = {(recorded[c.name]["cfg"], recorded[c.name]["ring"]) for c in sweep if c.mode == mode and c.dt == "bf16" and recorded[c.name]["wide"] == 1 and recorded[c.name]["splitk"] <= 1}
     assert {(t if t else G.AUTO_TILE, r if t else 2) for t, r in tiles} <= bf16
     for t in (8, 10):      # and the 64-byte K-tile configs by cases that ASKED for them
-        assert any(c.tile == t and recorded[c.name]["cfg"] == t and recorded[c.name]["wide"] == 1 for c in CASES if c.mode == mode), t
+        assert any(c.tile == t and recorded[c.name]["cfg"] == t and recorded[c.name]["wide"] == 1 for c in sweep if c.mode == mode), t
 
 
 def test_every_group_and_dtype_has_cases():
     have = {(c.group, c.dt) for c in CASES}
-    want = {(g, dt) for g in ("plain", "conv", "pixel", "stripes") for dt in ("bf16", "f16", "f32")} | {(g, dt) for g in ("narrow", "alias", "splitk") for dt in ("bf16", "f16")}
+    want = ({(g, dt) for g in ("plain", "conv", "pixel", "stripes") + G.EPILOGUE_GROUPS for dt in ("bf16", "f16", "f32")} |
+            {(g, dt) for g in ("narrow", "alias", "splitk") for dt in ("bf16", "f16")})
     assert have == want
+    assert {c.group for c in CASES} == set(G.LINEAR_GROUPS) | set(G.EPILOGUE_GROUPS)
+
+
+# the wide tiles each new group declares (the issue's lists; tile 0 = the automatic choice at that shape), after the replacements the planner and the act entries make
+WIDE_TILES = {
+    "geglu": {1, 2, 3, 4, 5, 7, 8, 10},                 # 0 -> 1 at N = 672; 6 and 11 -> 5
+    "heads": {1, 2, 5, 6, 11},                          # 0 -> 1 at N = 600 / 384, 2 at N = 400 / 200 / 256 / 128
+    "act": {1, 2, 6},                                   # what the family builds
+    "lnfold": {1, 2, 5, 6},
+    "dualk": {1, 2, 5, 6},
+    "t3": {(t if t else G.AUTO_TILE) for t, _ in CONV_TILES + F16_TILES},
+}
+
+
+@pytest.mark.parametrize("group", G.EPILOGUE_GROUPS)
+def test_new_groups_execute_exactly_their_declared_wide_tiles(recorded, group):
+    cases = G.by_group(group)
+    executed = {recorded[c.name]["cfg"] for c in cases if recorded[c.name]["wide"] == 1}
+    assert executed == WIDE_TILES[group], (sorted(executed - WIDE_TILES[group]), sorted(WIDE_TILES[group] - executed))
+    assert {c.want_cfg for c in cases if c.want_wide} == WIDE_TILES[group]
+    for dt in ("bf16", "f16"):      # both 16-bit types reach the narrow form as well, f32 has no other
+        assert any(recorded[c.name]["wide"] == 0 for c in cases if c.dt == dt) or group in ("dualk", "t3"), (group, dt)
+    assert all(recorded[c.name]["wide"] == 0 for c in cases if c.dt == "f32")
+    assert not any(recorded[c.name]["splitk"] > 1 for c in cases)
+
+
+def test_forms_chosen_inside_launch():
+    """pre, fast1 and heads_pk are decided inside gemm_kernel.h::launch, where the harness does not see them: the conditions are restated in gemm_cases.pre_staged (and its head) and
+    the cases meant for a form must satisfy them"""
+    new = G.by_group(*G.EPILOGUE_GROUPS)
+    for c in new:
+        keys = dict(c.tuning)
+        if c.want_pre:
+            cfg = c.want_cfg
+            assert c.want_wide == 1 and G.k_tiles(c, cfg) >= 2 and c.ln <= 1 and (c.ln == 0 or c.M % 2 == 0) and keys.get(G.TUNE_NO_PRESTAGE, 0) == 0, c.name
+        if c.group == "lnfold" and (c.M % 2 == 1 or c.ln > 1):
+            assert not c.want_pre, c.name                                   # an odd M and ln_nparts load in the epilogue without any key
+        if c.group == "heads" and c.want_wide:
+            assert keys.get(G.TUNE_HEADS_PACKED) in (1, 2), c.name          # never left to the M <= 8192 default
+            assert c.want_form == ("packed" if keys[G.TUNE_HEADS_PACKED] == 1 and not keys.get(G.TUNE_GENERIC_PASS1) else "staged"), c.name
+        if c.group == "geglu" and c.want_wide:
+            assert c.want_form == ("staged" if keys.get(G.TUNE_GENERIC_PASS1) else "packed"), c.name
+        if not c.want_wide:
+            assert c.want_form == "narrow" and c.want_cfg in (1, 2), c.name
+    # the wide problems of these four groups have a key-12 twin on the automatic tile, and a twin differs from its case by that key alone
+    by_name = {c.name: c for c in new}
+    twins = [c for c in new if c.name.endswith("-k12")]
+    assert {c.group for c in twins} == {"geglu", "heads", "act", "lnfold"}
+    for t in twins:
+        c = by_name[t.name[:-4]]
+        assert c.want_pre and not t.want_pre and c.tile == t.tile == 0
+        assert replace(t, name=c.name, tuning=c.tuning, want_pre=True) == c and t.tuning == c.tuning + ((G.TUNE_NO_PRESTAGE, 1),), t.name
+    for c in new:      # every wide problem (operands and shape) of the four groups is covered by a twin
+        if c.group in ("geglu", "heads", "act", "lnfold") and c.want_wide and c.want_pre and c.tile == 0 and not dict(c.tuning).get(G.TUNE_GENERIC_PASS1):
+            assert c.name + "-k12" in by_name, c.name
+    # the other keyed cases: the same problem as an unkeyed (or otherwise keyed) case of the group
+    problems = {}
+    for c in new:
+        problems.setdefault(G.problem_key(replace(c, want_wide=0)), []).append(c)
+    for c in new:
+        if c.tuning:
+            assert len(problems[G.problem_key(replace(c, want_wide=0))]) >= 2, c.name
 
 
 def test_narrow_and_split_cases_are_what_they_say(recorded):

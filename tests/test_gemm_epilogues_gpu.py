@@ -4,6 +4,10 @@ elements in front, two rows behind, the pad columns [N, ldo) - compared with the
 per-row and per-column relative L2 at the project's tolerances, every element within one unit of the storage type plus the f32 accumulation bound,
 and nothing outside the output touched.
 
+The GEGLU, head-split, activation, LayerNorm-fold, dual-source-K and unsplit T3 cases (one test per group, below the helpers) run the same way with the bounds of
+gemm_cases.analysis (derivation: the head of tests/kernel_compare.py; CPU proof: tests/test_gemm_epilogue_cases.py): every HEADS segment in a guarded buffer of its own,
+every form behind a tuning key (6, 7, 12, 13, 15) set and reset around the launch, and the key-12 twins also bit for bit against the pre-staged launch.
+
 FYC_EPILOGUE_FIGURES=<file>: append the figures of every comparison to that file (profiles/gemm_epilogue_coverage.txt was made from it)."""
 import os
 
@@ -58,6 +62,95 @@ def check(c, ops, got_buf, ref_buf, S):
 def _run(hip, c):  # noqa: F811
     ops, ref_buf, S = reference(c)
     return check(c, ops, launch(hip, c, ops), ref_buf, S)
+
+
+# ---- the other epilogues (tests/gemm_cases.py: EPILOGUE_GROUPS; bounds: the head of tests/kernel_compare.py; CPU proof: tests/test_gemm_epilogue_cases.py) -------------
+_epi_cache = {}
+
+
+def epilogue_reference(c):
+    """operands, reference buffers of EmuOps(acc=float64) and per-window bounds of a case's PROBLEM: computed once, shared by its tiles and keys, never modified"""
+    key = G.problem_key(c)
+    if key not in _epi_cache:
+        ops = G.operands(c)
+        _epi_cache[key] = (ops,) + G.epilogue_reference(c, ops)
+    return _epi_cache[key]
+
+
+def launch_epilogue(hip, c, ops, tuning=None):  # noqa: F811
+    """one launch into fresh copies of the guarded buffers (one per HEADS segment); returns them (GPU)"""
+    bufs = [b.cuda() for b in ops.bufs]
+    a, w, out, kw = G.gemm_kwargs(c, ops, bufs if c.heads is not None else bufs[0], to=lambda t: t.cuda())
+    tuning = c.all_tuning if tuning is None else tuning
+    for k, v in tuning:
+        hip.set_tuning(k, v)
+    try:
+        hip.gemm(a, w, out, **kw)
+        torch.cuda.synchronize()
+    finally:
+        for k, _ in tuning:
+            hip.set_tuning(k, 0)
+    return bufs
+
+
+def _run_epilogue(hip, c):  # noqa: F811
+    ops, ref_bufs, bounds = epilogue_reference(c)
+    got = [b.cpu() for b in launch_epilogue(hip, c, ops)]
+    figs = G.judge(c, ops, got, ref_bufs, bounds)
+    if FIGURES:
+        with open(FIGURES, "a") as f:
+            for fig in figs:
+                f.write(f"{c.group} {c.dt} {fig['tag'].replace(' ', '/')} {fig['global_rel']:.3e} {fig['row_rel']:.3e} {fig['column_rel']:.3e} {fig['elem_ratio']:.4f}\n")
+    if dict(c.tuning).get(G.TUNE_NO_PRESTAGE) == 1:
+        # pre-staged against self-loaded epilogue inputs: the same values into the same expressions (pre_ln_row / ln_row, the column constants) - bit for bit
+        twin = tuple(kv for kv in c.all_tuning if kv[0] != G.TUNE_NO_PRESTAGE)
+        pre = [b.cpu() for b in launch_epilogue(hip, c, ops, tuning=twin)]
+        for s, (x, y) in enumerate(zip(got, pre)):
+            assert torch.equal(x.view(torch.int16 if x.element_size() == 2 else torch.int32), y.view(torch.int16 if y.element_size() == 2 else torch.int32)), \
+                f"{c.name}: buffer {s} differs between the pre-staged and the self-loading launch"
+
+
+GEGLU_CASES, HEADS_CASES, ACT_CASES = G.by_group("geglu"), G.by_group("heads"), G.by_group("act")
+LNFOLD_CASES, DUALK_CASES, T3_CASES = G.by_group("lnfold"), G.by_group("dualk"), G.by_group("t3")
+
+
+@pytest.mark.parametrize("case", GEGLU_CASES, ids=G.case_ids(GEGLU_CASES))
+def test_geglu_epilogue_every_form(hip, case):  # noqa: F811
+    """M = 300, N = 672 (336 outputs), K = 136, every pitch wider than its row, with and without a folded LayerNorm: the pack-first form on every tile it is built for (6 and 11
+    replaced by 5), the LDS-staged form (key 13), the narrow per-lane form with the Abramowitz-Stegun gate (key 6; an output one element off 16 bytes), f32"""
+    _run_epilogue(hip, case)
+
+
+@pytest.mark.parametrize("case", HEADS_CASES, ids=G.case_ids(HEADS_CASES))
+def test_heads_epilogue_every_form(hip, case):  # noqa: F811
+    """q | k | V^T, k | V^T and q alone into guarded segment buffers of their own: d = 40 (16-column blocks straddle heads, batch elements straddle row tiles) and d = 64 on the
+    wide tiles, pack-first (key 15 = 1) and LDS-staged (key 15 = 2, key 13) forms, the narrow form (d = 12 with 77 tokens, key 7, f32); the pad columns [tokens, ld) of V^T
+    and everything around a segment must stay as they were"""
+    _run_epilogue(hip, case)
+
+
+@pytest.mark.parametrize("case", ACT_CASES, ids=G.case_ids(ACT_CASES))
+def test_activation_epilogue(hip, case):  # noqa: F811
+    """erf-GELU and quick-GELU between bias and residual on the three tiles the family builds, narrow through an odd output pitch, f32"""
+    _run_epilogue(hip, case)
+
+
+@pytest.mark.parametrize("case", LNFOLD_CASES, ids=G.case_ids(LNFOLD_CASES))
+def test_layernorm_fold_linear_epilogue(hip, case):  # noqa: F811
+    """rows with |mean| / std up to 4: stored {mean, rstd} pairs (packed; narrow next to a residual; an odd M that loads them in the epilogue) and three partial sums per row"""
+    _run_epilogue(hip, case)
+
+
+@pytest.mark.parametrize("case", DUALK_CASES, ids=G.case_ids(DUALK_CASES))
+def test_dual_source_k(hip, case):  # noqa: F811
+    """A = [a | a2] with separate pitches: the switch after one 64-element K tile, and on the border of the second"""
+    _run_epilogue(hip, case)
+
+
+@pytest.mark.parametrize("case", T3_CASES, ids=G.case_ids(T3_CASES))
+def test_t3_unsplit_every_tile(hip, case):  # noqa: F811
+    """5 clips x 3 frames x 20 rows between NaN guard rows: a tap read across a clip border or past either end shows as a wrong or a non-finite element"""
+    _run_epilogue(hip, case)
 
 
 PLAIN_CASES, NARROW_CASES = G.by_group("plain"), G.by_group("narrow")

@@ -118,6 +118,8 @@ def test_gemm_conv(hip, emu, dt, tile_ring, mode, stride, frames, H, W, Cin, Cou
     close(o_h, o_e, f"conv {dt} mode={mode} s={stride} {frames}x{H}x{W} {Cin}->{Cout}", RTOL[dt])
 
 
+# (GEGLU, HEADS, activation, LayerNorm fold and dual-source K below are judged by one global relative L2 here; per element, per form and in guarded buffers they are the
+# groups geglu / heads / act / lnfold / dualk of tests/gemm_cases.py, launched by tests/test_gemm_epilogues_gpu.py)
 @pytest.mark.parametrize("dt", ["bf16", "f32", "f16"])
 def test_gemm_geglu(hip, emu, dt):
     T = DT[dt]

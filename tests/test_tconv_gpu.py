@@ -66,6 +66,7 @@ def _guarded_output(M, N, T):
 @pytest.mark.parametrize("dt,tile_ring", [("bf16", t) for t in CONV_TILES] + [("f16", (0, 0)), ("f32", (0, 0))])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_t3_matches_the_specification(hip, shape, dt, tile_ring):
+    """one global relative L2 per case; per element and on every tile of the 16-bit types: the group t3 of tests/gemm_cases.py (tests/test_gemm_epilogues_gpu.py)"""
     clips, F, H, W, Cin, Cout = shape
     T, kw = DT[dt], _kw(shape)
     x, w, bias, res, ref = _problem(shape, dt)
