@@ -4,8 +4,11 @@
 namespace fycg {
 int run_f16_act(const GemmP& p, int batch, int cfg, hipStream_t st) {
   if (!p.wide) return dispatch_cfg<f16_t, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, false>(cfg, 2, p, batch, st);
-  if (cfg == 6 || cfg == 5) return launch<f16_t, 128, 320, 2, 4, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, 2, 128, true>(p, batch, st);
-  if (cfg == 1 || cfg == 3 || cfg == 7) return launch<f16_t, 128, 128, 2, 2, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, 2, 128, true>(p, batch, st);
-  return launch<f16_t, 128, 64, 2, 2, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, 2, 128, true>(p, batch, st);
+  switch (gemm_executed_cfg(GEMM_FAM_ACT, true, cfg, p.N)) {      // the planned tile folded onto the three (written out: the kernels keep their order in the object)
+    case 6: return launch<f16_t, 6, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, 2, true>(p, batch, st);
+    case 1: return launch<f16_t, 1, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, 2, true>(p, batch, st);
+    case 2: return launch<f16_t, 2, FYC_GEMM_PLAIN, EPI_LINEAR_ACT, 2, true>(p, batch, st);
+  }
+  FYC_FAIL(-2, "fyc_gemm: tile config %d not built for an activation", cfg);
 }
 }  // namespace fycg

@@ -25,61 +25,16 @@
 // f32 parity mode uses the same kernel with v_mfma_f32_16x16x4_f32 (exact f32, 1/16 rate); its opt-in f32x3 product rule (Mma<f32x3_t>)
 // splits the f32 operands into bf16 halves in registers and runs three v_mfma_f32_16x16x32_bf16 per block and K tile.
 #pragma once
-#include <mutex>
+#include <atomic>
 #include <type_traits>
+#include <utility>
 
-#include "fyc_common.h"
+#include "gemm_plan.h"      // GemmP, the tile table, the launch decisions: the host side of this family
+#include "lds_attr.h"
 
 namespace fycg {
 
 constexpr int FYC_MAX_DEVICES = 64;
-
-// Internal kernel mode beside the public FYC_GEMM_* values (never a value of fyc_gemm_args::mode; host: conv_up_phases.hip): nearest-2x upsampling + 3x3
-// convolution as four 2x2 convolutions of the LOW-resolution input, one per output phase (py, px) = parity of the output pixel.  On the upsampled image every
-// input pixel appears 2x2 times, so the three filter rows an output pixel (2y + py, 2x + px) touches collapse onto two input rows (py = 0: row y - 1 with
-// W[ky=0], row y with W[1] + W[2]; py = 1: row y with W[0] + W[1], row y + 1 with W[2]), columns alike: K = 4 * Cin with weights pre-summed at pack time
-// instead of 9 * Cin.  Rows of the problem are VIRTUAL, ordered [group][phase = 2 py + px][row in group]; a group is up_rows consecutive input pixels (whole
-// frames: one statistics sample of the consuming GroupNorm), up_rows % BM == 0, so a row tile has one phase and lies in one group.  The A gather is the CONV3X3
-// one with 4 taps whose top-left is (y - 1 + py, x - 1 + px) on the Hin x Win image (zero padding maps onto itself); the weights are [4 phases][N][ldw], and the
-// epilogue stores virtual row m at the output pixel's row ((frame * 2 Hin + 2 y + py) * 2 Win + 2 x + px).
-constexpr int GEMM_MODE_UP_PHASES = 16;
-
-struct GemmP {
-  const char* a; const char* a2; const char* w; const float* bias; const float* rowbias; const char* residual; char* out;
-  char* seg_out[3]; int seg_transposed[3]; int seg_ld[3];
-  int M, N, K, lda, ldw, ldo, ldr, ldrb, k_split, lda2;
-  long long stride_a, stride_w, stride_o;
-  int mode, epilogue;
-  int Hout, Wout, Hin, Win, Cin, conv_stride, conv_pad;
-  int rows_per_batch, seg_cols, heads, tokens, head_dim;
-  float out_scale;
-  int act;    // FYC_ACT_* (LINEAR epilogue)
-  const float* ln_stats; const float* ln_colsum;   // folded LayerNorm (see fyc.h): acc := rstd*(acc - mean*colsum[n])
-  int ln_nparts; float ln_eps;                     // ln_nparts > 0: ln_stats holds [M][ln_nparts] partial {sum, sum sq} (row_parts of the producer)
-  // statistics of the OUTPUT for the GroupNorm / LayerNorm that consumes it (LINEAR epilogue), see fyc.h
-  float* chan_parts; int cs_rows, cs_slots;        // [tiles_m][cs_slots][N][2] = {sum, sum sq} of the stored values per (row tile, sample slot, channel)
-  float* row_parts; int row_nparts;                // [M][row_nparts][2] = per row, per column tile {sum, sum sq}
-  int tiles_m, tiles_n;
-  int strip;  // > 0: tiles are walked in column strips of this many tiles (row-major inside a strip), see tile_coords
-  int up_exact2; float up_sh, up_sw;   // nearest-upsample source mapping
-  int colc;   // bias / colsum / tile-uniform rowbias may be fetched 16 B at a time and staged through LDS once per tile
-  int rb_tile; // rowbias row is the same for every row of a tile (rows_per_batch % BM == 0): folded into the staged bias
-  int rb_slots; // bf16 LINEAR wide epilogue: a tile touches up to this many rowbias rows (rows_per_batch % 16 == 0), staged through LDS next to the bias
-  int splitk; int t3_frames; float* ws;   // t3_frames: CONV_T3, frames per clip.  split-K (small M, long K): `splitk` work items per output tile, raw f32 partials to ws[splitk][M][N]
-  int stagger; // 8-wave tiles: the upper half of the waves issues its DMAs between its two MFMA k-steps (fyc_set_tuning key 5 = 1: off)
-  int wide;   // bf16 linear epilogue may use 16-B row accesses (N, ldo, ldr multiples of 8; bias/rowbias 16-B aligned)
-  const char* zero;
-  int res_acc;   // bf16 LINEAR wide epilogue: the residual tile is loaded INTO the accumulators before the K loop (see epilogue_linear_packed)
-  float inv_seg_cols, inv_head_dim;   // HEADS epilogue: reciprocals for fdiv_small (host: fyc_gemm)
-  int fast1;   // packed LINEAR epilogue: specialised pass 1 (fyc_set_tuning key 13 = 1: the generic one, A/B)
-  int heads_pk; // head-split epilogue: the pack-first form (epilogue_heads_packed) - M <= 8192 only, see launch()
-  int pre;     // round 6: the epilogue's per-row / per-column inputs are already in LDS (issue_consts in fyc_gemm_kernel), see pre_bytes()
-  int phase_delay; int t3_rows;   // t3_rows: CONV_T3, rows per frame (H*W).  phase_delay: round 6 (A/B, fyc_set_tuning key 11): every other block of an XCD starts this many x 1024 cycles late, see fyc_gemm_kernel
-  unsigned long long* trace;   // timing builds (-DFYC_TRACE, tools/gemm_phase_probe.py): per-block s_memtime stamps; nullptr otherwise
-};
-// (t3_frames / t3_rows sit in the two alignment holes the struct had: its size and every kernel-argument offset of the older modes stay put)
-// (GEMM_MODE_UP_PHASES adds no field either: t3_rows holds its rows per group, up_sw the reciprocal 1 / Win of its output row map)
-static_assert(sizeof(GemmP) == 392, "GemmP grew: the kernel-argument offsets of every instantiation move");
 
 // timing builds: waves 0 and 4 of a block append the shader clock to their list ([block][2][128] u64, zeroed by the host; the
 // count lives in a register so that a stamp is one store and no load)
@@ -179,10 +134,6 @@ __device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// internal epilogue id: LINEAR with the pointwise activation p.act compiled in.  A separate instantiation so that the
-// hot-path LINEAR kernels do not carry the GELU code (it costs the 256x320 tile 80 B/lane of scratch).
-constexpr int EPI_LINEAR_ACT = 3;
-
 __device__ __forceinline__ float activate(float x, int act) {
   return act == FYC_ACT_GELU ? gelu_erf_f(x) : x / (1.0f + __expf(-1.702f * x));
 }
@@ -211,7 +162,6 @@ template <int RB> __device__ __forceinline__ int swz_key(int row) {
 // the arrays of a slot in wave-row order.  (Round 3 used LDS float atomics here: the order the waves arrived in moved the last
 // bits of the GroupNorm statistics from run to run.)  The per-row sums (row_parts, off in the engine) still use LDS atomics.
 constexpr int STAT_SLOTS = 4;
-constexpr int RB_SLOTS = 4;     // rowbias rows a tile may touch in the packed LINEAR epilogue (GemmP::rb_slots)
 template <int WGM> constexpr int stat_arrays() { return WGM + STAT_SLOTS - 1; }
 template <int BM, int BN, int WGM> constexpr int stat_bytes() { return (stat_arrays<WGM>() * BN * 2 + BM * 2) * 4; }
 
@@ -317,7 +267,6 @@ __device__ __forceinline__ void stage_col_constants(const GemmP& p, float* colc,
 // in front of a tile's K loop, behind a barrier (every wave has left the previous tile's epilogue), the waves fetch, by global_load_lds,
 //   [BM] {mean, rstd} | [BN] bias | [BN] LayerNorm column sums | [<= RB_SLOTS][BN] row-bias rows
 // into a region behind the ring; the vmcnt(0) + barrier of the tile's first K-loop iteration retires them.  No global load and no vmcnt wait is left in those epilogues.
-template <int BM, int BN> constexpr int pre_bytes() { return BM * 8 + (2 + RB_SLOTS) * BN * 4; }
 template <int BM> __device__ __forceinline__ void pre_ln_row(const char* pre, int row_in_tile, float& mu, float& rs) {
   const float2 ms = *reinterpret_cast<const float2*>(pre + row_in_tile * 8);
   mu = ms.x; rs = ms.y;
@@ -1707,119 +1656,77 @@ __global__ void __launch_bounds__(WGM* WGN * 64) fyc_gemm_kernel(const GemmP p) 
   }  // tile stream
 }
 
-// rowbias rows (batch elements) a row tile of bm rows can touch; 0 = more than the packed LINEAR epilogue stages (fyc_gemm() then takes the narrow epilogue)
-inline int rowbias_slots(int bm, int rpb) {
-  if (rpb <= 0 || rpb % 16 != 0) return 0;
-  const int n = (bm % rpb == 0) ? bm / rpb : (bm - 1) / rpb + 2;
-  return n <= RB_SLOTS ? n : 0;
-}
 
-template <typename T, int BM, int BN, int WGM, int WGN, int MODE, int EPI, int NS, int RB = 128, bool WIDE = false, typename P = T>
-int launch(const GemmP& p, int batch, hipStream_t st) {
-  constexpr bool PRE_BUILT = WIDE && NS == 2;
-  constexpr int smem = NS * (BM + BN) * RB + (PRE_BUILT ? pre_bytes<BM, BN>() : 0);
-  static_assert(smem <= 160 * 1024, "LDS budget");
-  auto kern = fyc_gemm_kernel<T, BM, BN, WGM, WGN, MODE, EPI, NS, RB, WIDE, P>;
+// ---- host: launch and dispatch.  Every decision is gemm_plan.h's: the tile table (which instantiations exist, their geometry), gemm_executed_cfg (what a
+// planned config runs as) and gemm_launch_plan (the GemmP fields of a launch, LDS bytes, grid).  What is left here is the HIP side of it. -------------------
+
+// compute units of the current device, queried once per device (one process may drive several GPUs from several threads: two threads that meet on a new device
+// both ask, and store the same answer); 256 where none answers
+inline int device_cu_count() {
+  static std::atomic<int> n_cu[FYC_MAX_DEVICES] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  // per-device one-time setup (attribute + CU count), guarded: one process may drive several GPUs from several threads
-  static std::mutex mu;
-  static bool attr_done[FYC_MAX_DEVICES] = {};
-  static int n_cu_dev[FYC_MAX_DEVICES] = {};
-  int n_cu = 256;
-  if (dev >= 0 && dev < FYC_MAX_DEVICES) {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!attr_done[dev]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      hipDeviceProp_t pr;
-      n_cu_dev[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-      attr_done[dev] = true;
-    }
-    n_cu = n_cu_dev[dev];
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+  if (dev < 0 || dev >= FYC_MAX_DEVICES) return 256;
+  int n = n_cu[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    hipDeviceProp_t pr;
+    n = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+    n_cu[dev].store(n, std::memory_order_relaxed);
   }
+  return n;
+}
+
+// tile config ID of the table, ring depth NS, wide or narrow epilogue EPI, product rule P
+template <typename T, int ID, int MODE, int EPI, int NS, bool WIDE, typename P = T>
+int launch(const GemmP& p, int batch, hipStream_t st) {
+  constexpr GemmGeom g = {gemm_tile(ID), NS, WIDE, EPI, MODE, (int)sizeof(T)};
+  constexpr int smem = gemm_lds_bytes(g);
+  static_assert(gemm_built(g), "an instantiation the tile table does not list");
+  static_assert(smem <= 160 * 1024, "LDS budget");
+  auto kern = fyc_gemm_kernel<T, g.t.bm, g.t.bn, g.t.wgm, g.t.wgn, MODE, EPI, NS, g.t.rb, WIDE, P>;
+  static rp::LdsAttr attr;                          // one per instantiation
+  if (int rc = attr.set("fyc_gemm", smem, kern)) return rc;
+  const GemmLaunch d = gemm_launch_plan(p, g, g_fyc_tuning, device_cu_count(), batch);
   GemmP q = p;
-  q.tiles_m = (p.M + BM - 1) / BM;
-  q.tiles_n = (p.N + BN - 1) / BN;
-  q.rb_tile = (p.colc && p.rowbias != nullptr && p.rows_per_batch % BM == 0) ? 1 : 0;
-  q.rb_slots = (WIDE && EPI == FYC_EPI_LINEAR && p.rowbias != nullptr && !q.rb_tile) ? rowbias_slots(BM, p.rows_per_batch) : 0;
-  // epilogue inputs by DMA under the K loop: 2-deep-ring wide epilogues with at least two K tiles per output tile; the row statistics as
-  // stored {mean, rstd} pairs, two rows per 16-byte lane (M even, 16-byte aligned); row-bias rows only where the packed LINEAR epilogue
-  // stages them (fyc_set_tuning key 12 = 1 restores the loads in the epilogue: A/B)
-  {
-    constexpr int BK = (RB / 16) * (16 / (int)sizeof(T));
-    const int kt = (p.K + BK - 1) / BK;
-    const bool rb_ok = p.rowbias == nullptr || (EPI == FYC_EPI_LINEAR && (q.rb_tile || q.rb_slots > 0));
-    q.pre = (PRE_BUILT && g_fyc_tuning[FYC_TUNE_NO_PRESTAGE] != 1 && kt >= 2 && !(q.splitk > 1) && p.ln_nparts == 0 && rb_ok && p.wide &&
-             (p.ln_stats == nullptr || (p.M % 2 == 0 && ((uintptr_t)p.ln_stats % 16) == 0))) ? 1 : 0;
-  }
-  q.fast1 = g_fyc_tuning[FYC_TUNE_GENERIC_PASS1] == 1 ? 0 : 1;
-  // pack-first head-split epilogue: in the pipeline it wins at the 16x16 level only (8192x3840x1280 0.588 -> 0.562 ms per DDIM step, 8192x1280x1280
-  // 0.235 -> 0.212) and LOSES at the 64x64 / 32x32 levels (131072x960x320 0.970 -> 1.051, 32768x1920x640 0.666 -> 0.756: profiles/r06_gemm_epilogue_ab.txt
-  // part 4) - key 15 = 1 forces it on, 2 off
-  q.heads_pk = g_fyc_tuning[FYC_TUNE_HEADS_PACKED] == 1 ? 1 : g_fyc_tuning[FYC_TUNE_HEADS_PACKED] == 2 ? 0 : (p.M <= 8192 ? 1 : 0);
-  q.stagger = g_fyc_tuning[FYC_TUNE_NO_STAGGER] == 1 ? 0 : 1;
-  q.phase_delay = g_fyc_tuning[FYC_TUNE_PHASE_DELAY] > 0 ? g_fyc_tuning[FYC_TUNE_PHASE_DELAY] : 0;
-  q.res_acc = (WIDE && EPI == FYC_EPI_LINEAR && p.residual != nullptr && p.ln_stats == nullptr && !(q.splitk > 1)) ? 1 : 0;
+  q.tiles_m = d.tiles_m; q.tiles_n = d.tiles_n; q.rb_tile = d.rb_tile; q.rb_slots = d.rb_slots; q.pre = d.pre; q.fast1 = d.fast1; q.heads_pk = d.heads_pk;
+  q.stagger = d.stagger; q.phase_delay = d.phase_delay; q.res_acc = d.res_acc; q.strip = d.strip;
 #ifdef FYC_TRACE
   q.trace = g_fyc_trace;
 #endif
-  q.strip = (q.tiles_n > 4 && g_fyc_tuning[FYC_TUNE_GEMM_STRIP] >= 0) ? (g_fyc_tuning[FYC_TUNE_GEMM_STRIP] > 0 ? g_fyc_tuning[FYC_TUNE_GEMM_STRIP] : (q.tiles_n >= 16 ? 8 : 4)) : 0;   // measured: profiles/r01_gemm_strip_order.txt
-  // persistent grid: as many blocks as stay resident (LDS-limited), each walks a strided tile list
-  int occ = (160 * 1024) / smem;
-  const int wave_cap = 32 / (WGM * WGN);
-  if (occ > wave_cap) occ = wave_cap;
-  if (occ < 1) occ = 1;
-  long long resident = (long long)n_cu * occ / (batch > 0 ? batch : 1);
-  if (resident < n_cu) resident = n_cu;
-  const long long ntiles = (long long)q.tiles_m * q.tiles_n * (q.splitk > 1 ? q.splitk : 1);
-  dim3 grid((unsigned)(ntiles < resident ? ntiles : resident), 1, batch);
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), smem, st, q);
+  hipLaunchKernelGGL(kern, dim3(d.grid, 1, batch), dim3(g.t.wgm * g.t.wgn * 64), smem, st, q);
   FYC_CHECK_LAUNCH("fyc_gemm");
   return 0;
 }
 
-// tile configurations: id -> (BM, BN, WGM, WGN)
-//   1: 128x128, 4 waves   2: 128x64, 4 waves   3: 256x128, 8 waves   4: 256x64, 4 waves
-//   5: 256x320, 8 waves   6: 128x320, 8 waves  7: 256x256, 8 waves   8 / 10: 128x320 / 128x128 with 64-byte K tiles
-// All use the 2-deep ring (deeper rings measured no gain, profiles/r01_gemm_tile_sweep*.txt); config 1 is also built 3-deep so
-// that the counted-wait ring logic stays exercised (tests).  The narrow epilogue (WIDE = false: f32 parity mode and bf16
-// problems whose shapes / alignment rule out 16-byte accesses) only exists for configs 1 and 2.
+// row I of the tile table, counted from its END (hipcc emits the kernels of a translation unit in the reverse of the order a pack expansion names them in: this
+// way they come out in table order), with an NS-deep ring: launched if it is built for (T, MODE, EPI, WIDE) and is the one asked for
+template <typename T, int MODE, int EPI, bool WIDE, typename P, int I, int NS>
+bool launch_if(int cfg, int ns, const GemmP& p, int batch, hipStream_t st, int& rc) {
+  constexpr GemmTile t = GEMM_TILES[GEMM_N_TILES - 1 - I];
+  if constexpr (gemm_built(GemmGeom{t, NS, WIDE, EPI, MODE, (int)sizeof(T)})) {
+    if (cfg == t.id && ns == NS) {
+      rc = launch<T, t.id, MODE, EPI, NS, WIDE, P>(p, batch, st);
+      return true;
+    }
+  }
+  return false;
+}
+template <typename T, int MODE, int EPI, bool WIDE, typename P, int... I>
+int dispatch_tiles(int cfg, int ns, const GemmP& p, int batch, hipStream_t st, std::integer_sequence<int, I...>) {
+  int rc = 0;
+  if (((launch_if<T, MODE, EPI, WIDE, P, I, 4>(cfg, ns, p, batch, st, rc) || launch_if<T, MODE, EPI, WIDE, P, I, 3>(cfg, ns, p, batch, st, rc) ||
+        launch_if<T, MODE, EPI, WIDE, P, I, 2>(cfg, ns, p, batch, st, rc)) || ...))
+    return rc;
+  if (EPI == FYC_EPI_GEGLU && gemm_tile(cfg).geglu > 0) FYC_FAIL(-2, "fyc_gemm: tile config %d gives a wave an odd number of column blocks: not built for GEGLU", cfg);
+  FYC_FAIL(-2, "fyc_gemm: tile config %d not built", cfg);
+}
+
+// `cfg` / `ns`: the PLANNED tile config and ring depth.  The instantiations of (T, MODE, EPI, WIDE) are the rows of the tile table built for them (gemm_plan.h::GEMM_TILES).
 template <typename T, int MODE, int EPI, bool WIDE, typename P = T>
 int dispatch_cfg(int cfg, int ns, const GemmP& p, int batch, hipStream_t st) {
-  if constexpr (!WIDE) {
-    if (cfg != 1 && cfg != 2) cfg = (p.N % 128 == 0 || p.N > 512) ? 1 : 2;
-    if (cfg == 1) return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 128, false, P>(p, batch, st);
-    return launch<T, 128, 64, 2, 2, MODE, EPI, 2, 128, false, P>(p, batch, st);
-  } else {
-    switch (cfg) {
-      case 1: if (ns == 3) return launch<T, 128, 128, 2, 2, MODE, EPI, 3, 128, true>(p, batch, st);
-              return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 128, true>(p, batch, st);
-      case 2: if constexpr (MODE == FYC_GEMM_PLAIN) {   // deeper rings for the latency-bound small-M linears (8x8 latent level): see gemm.hip::choose
-                if (ns == 4) return launch<T, 128, 64, 2, 2, MODE, EPI, 4, 128, true>(p, batch, st);
-                if (ns == 3) return launch<T, 128, 64, 2, 2, MODE, EPI, 3, 128, true>(p, batch, st);
-              }
-              return launch<T, 128, 64, 2, 2, MODE, EPI, 2, 128, true>(p, batch, st);
-      case 3: return launch<T, 256, 128, 4, 2, MODE, EPI, 2, 128, true>(p, batch, st);
-      case 4: return launch<T, 256, 64, 4, 1, MODE, EPI, 2, 128, true>(p, batch, st);
-      // N = 320*k (every layer width of SD-1.5): 320-wide tiles read the A panel once per 320 columns
-      case 5: return launch<T, 256, 320, 4, 2, MODE, EPI, 2, 128, true>(p, batch, st);
-      case 6: if constexpr (EPI == FYC_EPI_GEGLU) FYC_FAIL(-2, "fyc_gemm: tile config 6 gives a wave an odd number of column blocks: not built for GEGLU");
-              else return launch<T, 128, 320, 2, 4, MODE, EPI, 2, 128, true>(p, batch, st);
-      case 7: return launch<T, 256, 256, 2, 4, MODE, EPI, 2, 128, true>(p, batch, st);
-      // 64-byte K tiles: half the LDS per stage -> two independent 4-wave blocks per CU with 64x160 wave tiles (8)
-      case 8: return launch<T, 128, 320, 2, 2, MODE, EPI, 2, 64, true>(p, batch, st);
-      case 10: return launch<T, 128, 128, 2, 2, MODE, EPI, 2, 64, true>(p, batch, st);
-      // round 6: 128x160 over 2x2 waves (64x80 per wave, the wave tile of config 6) with 72 KB of ring: TWO independent workgroups per CU,
-      // so one's epilogue / first fill runs under the other's K loop - for the short-K problems whose 128x320 tiles spend as long in the
-      // epilogue as in the K loop (profiles/r06_gemm_two_workgroups_ab.txt)
-      case 11: if constexpr (EPI == FYC_EPI_GEGLU) FYC_FAIL(-2, "fyc_gemm: tile config 11 gives a wave an odd number of column blocks: not built for GEGLU");
-               else return launch<T, 128, 160, 2, 2, MODE, EPI, 2, 128, true>(p, batch, st);
-      // (12 / 13 / 14 were the 32x32x16 main-loop twins of 5 / 7 / 3, 8-12 % slower on every shape, profiles/r06_gemm_mi32_ab.txt: retired, never built)
-    }
-    FYC_FAIL(-2, "fyc_gemm: tile config %d not built", cfg);
-  }
+  constexpr int family = (EPI == EPI_LINEAR_ACT && sizeof(T) == 2) ? GEMM_FAM_ACT : MODE == FYC_GEMM_CONV_T3 ? GEMM_FAM_T3 : MODE == FYC_GEMM_PLAIN ? GEMM_FAM_PLAIN : GEMM_FAM_CONV;
+  return dispatch_tiles<T, MODE, EPI, WIDE, P>(gemm_executed_cfg(family, WIDE, cfg, p.N), gemm_executed_ns(family, WIDE, ns), p, batch, st,
+                                               std::make_integer_sequence<int, GEMM_N_TILES>{});
 }
 
 template <typename T, int MODE, int EPI>
@@ -1829,27 +1736,5 @@ int dispatch_ns(int ns, int cfg, const GemmP& p, int batch, hipStream_t st) {
   }
   return dispatch_cfg<T, MODE, EPI, false>(cfg, ns, p, batch, st);
 }
-
-// one translation unit per (dtype, family) keeps the build parallel
-int run_bf16_plain(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
-int run_bf16_conv(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
-int run_bf16_act(const GemmP& p, int batch, int cfg, hipStream_t st);   // LINEAR + activation: tile configs 1, 2, 6
-int run_f32(const GemmP& p, int batch, int cfg, hipStream_t st);
-// f32 storage, split-bf16 products (f32x3_t): gemm_f32x3.hip, gemm_f32x3_t3.hip.  fyc_gemm reaches them through run_f32 / run_f32_t3 with CFG_F32X3 OR-ed into
-// `cfg` (like the ring depth in fyc_gemm_args::tile): the product rule is no part of the plan, and the entry points of a (dtype, family) stay one per family
-constexpr int CFG_F32X3 = 0x100;
-int run_f32x3(const GemmP& p, int batch, int cfg, hipStream_t st);
-int run_f32x3_t3(const GemmP& p, int batch, int cfg, hipStream_t st);
-// f16 storage (FYC_F16): the same kernels on v_mfma_f32_16x16x32_f16
-int run_f16_plain(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
-int run_f16_conv(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
-int run_f16_act(const GemmP& p, int batch, int cfg, hipStream_t st);
-// 3-tap convolution along the frame axis (FYC_GEMM_CONV_T3): gemm_{bf16,f16,f32}_t3.hip
-int run_bf16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
-int run_f16_t3(const GemmP& p, int batch, int cfg, int ns, hipStream_t st);
-int run_f32_t3(const GemmP& p, int batch, int cfg, hipStream_t st);
-// nearest-2x upsample + 3x3 as four 2x2 phase convolutions (GEMM_MODE_UP_PHASES; entry: conv_up_phases.hip): conv_up_phases_{bf16,f16}.hip
-int run_bf16_up_phases(const GemmP& p, int cfg, int ns, hipStream_t st);
-int run_f16_up_phases(const GemmP& p, int cfg, int ns, hipStream_t st);
 
 }  // namespace fycg

@@ -1,13 +1,12 @@
 // What the register-resident row-panel kernels share (ff_block.hip, temporal_block_rr.hip, panel_linear.hip, and the LDS-tile
 // temporal_block.hip that dispatches into the second): the asm-issued LDS-DMA statements, the MFMA overloads and the fragment
 // read, the cross-lane reductions that are safe next to those DMAs, and the host side of a launch with more than 64 KB of dynamic
-// LDS.  The rules below have this one home; a kernel of the family takes them from here instead of copying them.
+// LDS (lds_attr.h, which the GEMM family shares).  The rules below have this one home; a kernel of the family takes them from here instead of copying them.
 // (The two-pass LayerNorm statistics on the operand registers stay written out in ff_block.hip and temporal_block_rr.hip:
 // as a function here, hipcc orders the operands of their ~160 additions the other way round.  Same sums, other code.)
 #pragma once
-#include <mutex>
-
 #include "fyc_common.h"
+#include "lds_attr.h"      // rp::LdsAttr: the dynamic-LDS attribute, once per device
 
 namespace rp {
 
@@ -70,39 +69,6 @@ __device__ __forceinline__ float rows_sum(float v) { return swap32_sum(swap16_su
 __device__ __forceinline__ float rows_max(float v) { return swap32_max(swap16_max(v)); }   // (fyc_common.h: the plain fmaxf form is miscompiled)
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-// Dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize on the kernel once per device; one process may drive
-// several GPUs from several threads.  One object per launch site, as a function-local static (so a templated launcher keeps one
-// per instantiation): `if (int rc = attr.set("fyc_x", LDS_BYTES, kernel<a>, kernel<b>)) return rc;`
-class LdsAttr {
- public:
-  template <typename... K>
-  int set(const char* name, int bytes, K*... kernels) {
-    const void* ks[] = {reinterpret_cast<const void*>(kernels)...};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    return set_on(dev, name, bytes, ks, (int)sizeof...(K),
-                  [](const void* k, int b) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, b); });
-  }
-  // the logic behind set(), with the device index and the attribute call handed in (tests/lds_attr_harness.hip passes fakes).
-  // A device index outside [0, MAX_DEV) is served, but not remembered: its attribute is set at every launch.
-  template <typename Setter>
-  int set_on(int dev, const char* name, int bytes, const void* const* kernels, int n, Setter setter) {
-    const bool tracked = dev >= 0 && dev < MAX_DEV;
-    std::lock_guard<std::mutex> lk(mu_);
-    if (tracked && done_[dev]) return 0;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < n && e == hipSuccess; ++i) e = setter(kernels[i], bytes);
-    if (e != hipSuccess) FYC_FAIL(-3, "%s: %d bytes of dynamic LDS refused: %s", name, bytes, hipGetErrorString(e));
-    if (tracked) done_[dev] = true;            // only after success: a failed call is retried at the next launch
-    return 0;
-  }
-
- private:
-  static constexpr int MAX_DEV = 64;
-  std::mutex mu_;
-  bool done_[MAX_DEV] = {};
-};
-
 // Does a kernel that needs `bytes` of LDS fit this process's device (one GPU per process)?  The LDS per CU is queried once per
 // process; when no device answered (0) the answer is yes and the launch reports what is wrong.  A device / partition mode with
 // less LDS makes the *_supported entry points say no, and the caller keeps the unfused schedule.

@@ -20,12 +20,12 @@ The intent is written down from the rules of csrc/gemm_plan.h as a reader unders
 The groups geglu, heads, act, lnfold, dualk and t3 (EPILOGUE_GROUPS) carry the rest of fyc_gemm: the GEGLU and head-split epilogues, LINEAR with an activation, the folded
 LayerNorm, dual-source K and the unsplit frame-axis convolution.  Their rules, as read from the sources:
   * tile 0 at M < 4096: 128x128 (1) for N a multiple of 128 or above 512 (672, 600, 384), else 128x64 (2) (auto_tile);
-  * GEGLU pairs value and gate blocks inside a wave: configs 6 and 11 give a wave an odd number of blocks and the planner runs 5 instead (gemm_plan.h::geglu_tile);
-  * the activation family builds the tiles 1, 2 and 6 only, and its entry folds every planned tile onto one of them (gemm_bf16_act.hip); it takes no ring depth;
+  * GEGLU pairs value and gate blocks inside a wave: configs 6 and 11 give a wave an odd number of blocks and the planner runs 5 instead (gemm_plan.h::GEMM_TILES, column `geglu`);
+  * the activation family builds the tiles 1, 2 and 6 only, and every planned tile is folded onto one of them (gemm_plan.h::gemm_executed_cfg); it takes no ring depth;
   * HEADS is wide when head_dim % 8 == 0, tokens % 16 == 0, the V^T pitch % 8 == 0 and the segments are 16-byte aligned, unless key 6 or key 7 is set;
-  * a residual next to a fold makes the LINEAR epilogue narrow (gemm_plan.h:111);
-  * keys 6 (no wide epilogue) and 7 (no wide head split) act in the planner and are seen by the harness.  Keys 12, 13 and 15 act inside gemm_kernel.h::launch (:1754-1761),
-    where the harness does not look - restated here and asserted for the cases by tests/test_gemm_cases.py::test_forms_chosen_inside_launch:
+  * a residual next to a fold makes the LINEAR epilogue narrow (gemm_plan.h::plan_gemm, `packed && ...`);
+  * keys 6 (no wide epilogue) and 7 (no wide head split) act in the planner and are seen by the harness.  Keys 12, 13 and 15 act in gemm_plan.h::gemm_launch_plan
+    (the decisions of one launch: the harness calls it for the launch it recorded) - restated here, and tests/test_gemm_cases.py compares the restatement with the library for every case:
         pre      epilogue inputs by DMA under the K loop: a wide launch with a 2-deep ring, at least two K tiles (64 elements each for 16-bit types, 32 on configs 8 / 10), no
                  split-K, no ln_nparts, statistics (if any) as 16-byte aligned stored pairs of an EVEN number of rows, a row bias only where the packed LINEAR epilogue
                  stages it, and key 12 != 1 (pre_staged)
@@ -100,7 +100,7 @@ class Case:
     want_ring: int = 2               # -1: the f32 and the activation entries take none
     want_wide: int = 0
     want_split: bool = False
-    want_form: str = ""              # the form chosen inside launch() (head of the file), for the new groups: "packed", "staged", "narrow"
+    want_form: str = ""              # the epilogue form the launch decisions select (head of the file), for the new groups: "packed", "staged", "narrow"
     want_pre: bool = False           # meant to take its epilogue inputs pre-staged under the K loop
 
     @property
@@ -208,12 +208,12 @@ def _splitk_cases():
 LINEAR_GROUPS = ("plain", "narrow", "conv", "pixel", "alias", "stripes", "splitk")      # judged by kernel_compare.element_bound through bound_terms()
 EPILOGUE_GROUPS = ("geglu", "heads", "act", "lnfold", "dualk", "t3")                    # judged by epilogue_bound() below
 TUNE_NO_WIDE, TUNE_NO_WIDE_HEADS, TUNE_NO_PRESTAGE, TUNE_GENERIC_PASS1, TUNE_HEADS_PACKED = 6, 7, 12, 13, 15
-ACT_WIDE_TILES = {1: 1, 3: 1, 7: 1, 5: 6, 6: 6}      # csrc/gemm_bf16_act.hip, gemm_f16_act.hip: what a planned tile runs as, wide; everything else 128x64 (2)
-GEGLU_REPLACED = {6: 5, 11: 5}                        # gemm_plan.h::geglu_tile: a wave of these owns an odd number of column blocks
+ACT_WIDE_TILES = {1: 1, 3: 1, 7: 1, 5: 6, 6: 6}      # gemm_plan.h::gemm_executed_cfg, activation family: what a planned tile runs as, wide; everything else 128x64 (2)
+GEGLU_REPLACED = {6: 5, 11: 5}                        # gemm_plan.h::GEMM_TILES, column `geglu`: a wave of these owns an odd number of column blocks
 
 
 def auto_tile(M, N):
-    """gemm_plan.h:68-92 for M < 4096, 16-bit"""
+    """gemm_plan.h::plan_gemm, "tile config and ring depth", for M < 4096, 16-bit"""
     assert M < 4096
     if N % 320 == 0:
         return 5 if N >= 5120 else 1 if N >= 2560 else 2
@@ -221,7 +221,7 @@ def auto_tile(M, N):
 
 
 def narrow_tile(cfg, N):
-    """gemm_kernel.h::dispatch_cfg, !WIDE: only configs 1 and 2 are built"""
+    """gemm_plan.h::gemm_executed_cfg, !wide: only configs 1 and 2 are built narrow"""
     return cfg if cfg in (1, 2) else 1 if (N % 128 == 0 or N > 512) else 2
 
 
@@ -232,7 +232,7 @@ def k_tiles(c, cfg):
 
 
 def pre_staged(c):
-    """gemm_kernel.h::launch, q.pre - restated: a wide 2-deep-ring launch with at least two K tiles, unsplit, whose statistics (if any) are stored pairs of an even number
+    """gemm_plan.h::gemm_launch_plan, q.pre - restated: a wide 2-deep-ring launch with at least two K tiles, unsplit, whose statistics (if any) are stored pairs of an even number
     of rows (16-byte aligned: the harness and the tests pass aligned tables), no row bias outside the packed LINEAR epilogue, and key 12 not set"""
     return bool(c.want_wide == 1 and c.want_ring in (2, -1) and not c.want_split and k_tiles(c, c.want_cfg) >= 2 and c.ln <= 1 and (c.ln == 0 or c.M % 2 == 0) and
                 (not c.rowbias or c.epilogue == LINEAR) and dict(c.tuning).get(TUNE_NO_PRESTAGE, 0) != 1)
@@ -350,7 +350,7 @@ def _lnfold_cases():
         for tile in (0, 5):      # an odd M: the statistics cannot come as 16-byte pairs, the epilogue loads them itself
             out.append(Case(name=f"lnfold-{dt}-m301-t{tile}", dt=dt, M=301, ln=1, tile=tile, **base, **_want(dt, 301, 328, tile)))
             out.append(Case(name=f"lnfold-{dt}-parts3-t{tile}", dt=dt, M=300, ln=3, tile=tile, **base, **_want(dt, 300, 328, tile)))
-        # a residual next to the fold: planned narrow (gemm_plan.h:111)
+        # a residual next to the fold: planned narrow (gemm_plan.h::plan_gemm)
         out.append(Case(name=f"lnfold-{dt}-res", dt=dt, M=300, ln=1, residual=1, out_scale=0.75, **base, **_want(dt, 300, 328, 0, narrow=True)))
     for M, ln in ((300, 1), (301, 1), (300, 3)):
         out.append(Case(name=f"lnfold-f32-m{M}-ln{ln}", dt="f32", M=M, ln=ln, residual=1, out_scale=0.75, **base, **_want("f32", M, 328, 0)))
@@ -380,8 +380,8 @@ def _t3_cases():
     return out
 
 
-CASES = (_plain_cases() + _conv_cases() + _alias_cases() + _stripe_cases() + _splitk_cases() +
-         _finish(_geglu_cases() + _heads_cases() + _act_cases() + _lnfold_cases() + _dualk_cases() + _t3_cases()))
+CASES = _finish(_plain_cases() + _conv_cases() + _alias_cases() + _stripe_cases() + _splitk_cases() +
+                _geglu_cases() + _heads_cases() + _act_cases() + _lnfold_cases() + _dualk_cases() + _t3_cases())
 assert len({c.name for c in CASES}) == len(CASES)
 BY_NAME = {c.name: c for c in CASES}
 
@@ -567,7 +567,7 @@ def bound_terms(c, ops_):
 
 
 def tile_shape(cfg):
-    """(rows, columns) of a tile config (csrc/gemm_kernel.h::dispatch_cfg), for compare's report"""
+    """(rows, columns) of a tile config (csrc/gemm_plan.h::GEMM_TILES), for compare's report"""
     bm = 256 if cfg in (3, 4, 5, 7, 12, 13, 14) else 128
     bn = {2: 64, 4: 64, 5: 320, 6: 320, 8: 320, 12: 320, 7: 256, 13: 256, 11: 160}.get(cfg, 128)
     return bm, bn
@@ -755,7 +755,7 @@ GELU_AS_ERR = gelu_as_error()      # what the bounds use; never a number copied 
 
 
 def quick_gelu(x):
-    """x sigmoid(1.702 x) in f64 -> (value, first-order bound of activate()'s f32 evaluation, csrc/gemm_kernel.h:187: the product -1.702f x (u |a|), __expf (u |a| + 0.25 u |a| +
+    """x sigmoid(1.702 x) in f64 -> (value, first-order bound of activate()'s f32 evaluation, csrc/gemm_kernel.h::activate: the product -1.702f x (u |a|), __expf (u |a| + 0.25 u |a| +
     EXP_U u, as in gelu_as), 1 + E (u), the division (u; HIP divides f32 correctly rounded), and 1.702f against the reference's 1.702 (|a| |1.702f / 1.702 - 1|))"""
     x = x.double()
     a = QUICK_C * x
@@ -767,7 +767,7 @@ def quick_gelu(x):
 
 def fold_terms(c, ops_):
     """(mu, rs, dmu, drs) per row, f64 [M][1]: the statistics the REFERENCE folds with and how far the kernel's may lie from them.  Stored pairs: both sides read the same f32
-    numbers.  ln_nparts (csrc/gemm_kernel.h:272-277): a chain of n - 1 f32 additions per sum, inv = 1.0f / K and a product each, mu * mu, the subtraction, + eps, rsqrtf - against
+    numbers.  ln_nparts (csrc/gemm_kernel.h::ln_row): a chain of n - 1 f32 additions per sum, inv = 1.0f / K and a product each, mu * mu, the subtraction, + eps, rsqrtf - against
     the exact values of the same f32 partials; the reference's own f32 evaluation (EmuOps.gemm) is measured against them as well and added"""
     if c.ln == 1:
         st = ops_.ln_stats.double()
@@ -897,7 +897,7 @@ DEFECTS = {
 
 def model(c, ops_, defect=None):
     """the guarded buffers after a torch model of the form the case declares (want_form, want_wide) ran: the f32 matrix product, the fold as the source has it - two packed
-    FMAs in the packed forms (gemm_kernel.h:434, :645, :777), a product and a difference elsewhere (:938, :1062, :1186) -, the polynomial or the Abramowitz-Stegun gate, the
+    FMAs in the packed forms (gemm_kernel.h::epilogue_linear_packed, epilogue_heads_packed, epilogue_geglu_packed), a product and a difference elsewhere (the three forms of gemm_epilogue itself) -, the polynomial or the Abramowitz-Stegun gate, the
     residual and the scale in the source's order, one rounding to the storage type.  `defect`: one of DEFECTS, planted at a single site"""
     from row_panel_cases import fma32, geglu32
     T = DT[c.dt]
@@ -908,7 +908,7 @@ def model(c, ops_, defect=None):
     packed = c.want_form == "packed"
     if c.ln:
         mu, rs = fold_terms(c, ops_)[:2]
-        if c.ln > 1:      # the kernel's own chain (gemm_kernel.h:272-277)
+        if c.ln > 1:      # the kernel's own chain (gemm_kernel.h::ln_row)
             parts = ops_.ln_stats.reshape(c.M, c.ln, 2)
             t = parts[:, 0].clone()
             for i in range(1, c.ln):

@@ -20,7 +20,10 @@
 //   offsets:   out_off rb_off res_off = bytes added to the made-up 256-byte aligned address of that operand
 //   segments:  seg_tr seg_ld seg_off = comma-separated seg_transposed / seg_ld / byte offset of seg_out, one entry per segment of the HEADS epilogue
 //   tuning:    tune=<key>:<value>, may repeat; reset after the case
-//   answer:    <name> | <launch, as above> | <executed cfg> <executed rows>x<columns> | <rc> [message]
+//   answer:    <name> | <launch, as above> | <executed cfg> <executed rows>x<columns> | <rc> [message] | <decisions>
+//   executed:  GemmPlan::run_cfg / run_bm / run_bn of the plan the call executed (0 0x0: nothing was launched)
+//   decisions: pre fast1 heads_pk res_acc rb_tile rb_slots strip lds grid, as key=value: what gemm_plan.h::gemm_launch_plan decides for the recorded launch
+//              on a device of 256 compute units (no device answers here); `-` where nothing was launched or the executed tile is one the table does not build
 // Without an argument the output is the table above, byte for byte.
 #include <stdlib.h>
 
@@ -28,15 +31,17 @@
 #include <string>
 #include <vector>
 
-#include "../followyourclick_amd/csrc/gemm_kernel.h"
+#include "../followyourclick_amd/csrc/gemm_plan.h"
 
 using fycg::GemmP;
 
 namespace {
 struct Rec { const char* fam; int cfg, ns, wide, colc, splitk, cs_slots, batch, calls; };
 Rec g_rec;
+GemmP g_rec_p;      // the arguments of the recorded launch
 int record(const char* fam, const GemmP& p, int batch, int cfg, int ns) {
   g_rec = Rec{fam, cfg, ns, p.wide, p.colc, p.splitk, p.cs_slots, batch, g_rec.calls + 1};
+  g_rec_p = p;
   return 0;
 }
 }  // namespace
@@ -169,30 +174,12 @@ std::vector<Case> grid() {
   return out;
 }
 
-// (rows, columns) of the tile a recorded launch executes: gemm_kernel.h::dispatch_cfg and the act entries
-void executed_tile(const Rec& r, int N, int& bm, int& bn) {
-  const std::string fam = r.fam;
-  int cfg = r.cfg;
-  if (fam.find("act") != std::string::npos && r.wide) cfg = (cfg == 6 || cfg == 5) ? 6 : (cfg == 1 || cfg == 3 || cfg == 7) ? 1 : 2;
-  else if (!r.wide && cfg != 1 && cfg != 2) cfg = (N % 128 == 0 || N > 512) ? 1 : 2;
-  switch (cfg) {
-    case 2: bm = 128; bn = 64; break;
-    case 3: case 14: bm = 256; bn = 128; break;
-    case 4: bm = 256; bn = 64; break;
-    case 5: case 12: case 21: bm = 256; bn = 320; break;
-    case 6: case 8: case 22: case 31: bm = 128; bn = 320; break;
-    case 7: case 13: case 23: bm = 256; bn = 256; break;
-    case 11: bm = 128; bn = 160; break;
-    default: bm = 128; bn = 128; break;
-  }
-}
-
-// the tile config a recorded launch executes: the !WIDE rewrite of gemm_kernel.h::dispatch_cfg (and the act entries' own folding)
-int executed_cfg(const Rec& r, int N) {
-  const std::string fam = r.fam;
-  if (fam.find("act") != std::string::npos && r.wide) return (r.cfg == 6 || r.cfg == 5) ? 6 : (r.cfg == 1 || r.cfg == 3 || r.cfg == 7) ? 1 : 2;
-  if (!r.wide && r.cfg != 1 && r.cfg != 2) return (N % 128 == 0 || N > 512) ? 1 : 2;
-  return r.cfg;
+// the plan fyc_gemm executed for `a` (the call succeeded: the plan does)
+fycg::GemmPlan executed_plan(const fyc_gemm_args& a) {
+  fycg::GemmPlan pl;
+  char err[512];
+  (void)fycg::plan_gemm(&a, (a.chan_parts != nullptr ? fycg::GEMM_STATS_CHAN : 0) | (a.row_parts != nullptr ? fycg::GEMM_STATS_ROW : 0), false, pl, err);
+  return pl;
 }
 
 // ---- second mode: the cases of a file ---------------------------------------------------------------------------------------------
@@ -288,11 +275,24 @@ int run_file(FILE* f) {
     if (rc == -3 && g_rec.calls == 1 && g_rec.splitk > 1 && msg.find("fyc_gemm split-K finish") == 0) { rc = 0; msg.clear(); }   // (no device: see the head of the file)
     (void)hipGetLastError();
     if (msg.size() > 160) msg.resize(160);
-    int bm = 0, bn = 0;
-    if (rc == 0 && g_rec.calls == 1) executed_tile(g_rec, a.N, bm, bn);
-    else ++bad;
-    printf("%s | %s %d %d %d %d %d %d %d | %d %dx%d | %d%s%s\n", c.name.c_str(), g_rec.fam, g_rec.cfg, g_rec.ns, g_rec.wide, g_rec.colc, g_rec.splitk, g_rec.cs_slots,
-           g_rec.batch, executed_cfg(g_rec, a.N), bm, bn, rc, msg.empty() ? "" : " ", msg.c_str());
+    fycg::GemmPlan pl = {};
+    std::string decided = "-";
+    if (rc == 0 && g_rec.calls == 1) {
+      pl = executed_plan(a);
+      const fycg::GemmGeom g = {fycg::gemm_tile(pl.run_cfg), pl.run_ns, pl.wide != 0, g_rec_p.act != FYC_ACT_NONE ? fycg::EPI_LINEAR_ACT : g_rec_p.epilogue, g_rec_p.mode,
+                                fycg::gemm_is16(pl.dtype) ? 2 : 4};
+      if (fycg::gemm_built(g)) {
+        const fycg::GemmLaunch d = fycg::gemm_launch_plan(g_rec_p, g, g_fyc_tuning, 256, g_rec.batch);
+        char buf[192];
+        snprintf(buf, sizeof(buf), "pre=%d fast1=%d heads_pk=%d res_acc=%d rb_tile=%d rb_slots=%d strip=%d lds=%d grid=%u", d.pre, d.fast1, d.heads_pk, d.res_acc, d.rb_tile,
+                 d.rb_slots, d.strip, d.smem, d.grid);
+        decided = buf;
+      }
+    } else {
+      ++bad;
+    }
+    printf("%s | %s %d %d %d %d %d %d %d | %d %dx%d | %d%s%s | %s\n", c.name.c_str(), g_rec.fam, g_rec.cfg, g_rec.ns, g_rec.wide, g_rec.colc, g_rec.splitk, g_rec.cs_slots,
+           g_rec.batch, pl.run_cfg, pl.run_bm, pl.run_bn, rc, msg.empty() ? "" : " ", msg.c_str(), decided.c_str());
     for (auto& kv : c.tuning) fyc_set_tuning(kv.first, 0);
   }
   fflush(stdout);
@@ -337,8 +337,8 @@ int main(int argc, char** argv) {
     if (msg.size() > 100) msg.resize(100);
     std::string flags;
     if (rc == 0 && g_rec.calls == 1) {
-      int bm = 0, bn = 0;
-      executed_tile(g_rec, a.N, bm, bn);
+      const fycg::GemmPlan pl = executed_plan(a);
+      const int bm = pl.run_bm, bn = pl.run_bn;
       const bool split = g_rec.splitk > 1;
       if (a.chan_parts != nullptr) {
         fyc_gemm_args q = a;

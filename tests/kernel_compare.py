@@ -127,11 +127,11 @@ convolution).  The bounds are computed in tests/gemm_cases.py::analysis beside t
 of the kernel's polynomial - and handed to compare() as `bound` with lines=True; u = 2^-24, the constant is 1, ulp_T(ref) is added for the store, no element is exempt.
   Pre-activation: pre = acc + bias with acc an f32 sum of K products (of two sources, of three gathered taps: the operand's indexing does not change the count):
         E = (K + 8) u S,  S = |a| |W|^T + |bias|,  as element_bound has it.
-  Fold: pre = rs (acc - mu cs) + bias.  The narrow and the LDS-staged forms (:938, :1062, :1081, :1186) round mu cs, the difference, the product with rs and the sum with the bias; the
-    pack-first forms (:434, :645, :777) round nm = -rs mu, the inner fma(nm, cs, bias) and the outer fma(acc, rs, .), the head split also rs scale and scale * (.): at most five
+  Fold: pre = rs (acc - mu cs) + bias.  The narrow and the LDS-staged forms (the LINEAR, GEGLU and HEADS branches of gemm_epilogue) round mu cs, the difference, the product with rs and the sum with the bias; the
+    pack-first forms (epilogue_linear_packed, epilogue_heads_packed, epilogue_geglu_packed) round nm = -rs mu, the inner fma(nm, cs, bias) and the outer fma(acc, rs, .), the head split also rs scale and scale * (.): at most five
     roundings, each on a partial sum no larger than S = rs (|a| |W|^T + |mu cs|) + |bias|, and the K roundings of acc come through rs: E = (K + 8) u S again, with this S.  With
     |mean| / std = 4 the term |mu cs| is several times the output: the cancellation is in S, not assumed away.  Stored {mean, rstd} pairs are the same f32 numbers on both sides.
-    ln_nparts (ln_row, :272-277): n - 1 f32 additions per sum, inv = 1.0f / K (u) and one product each (u): dmu = (n - 1) u sum |s_i| / K + 2 u |mu|;  dvar = (n + 1) u q / K +
+    ln_nparts (ln_row): n - 1 f32 additions per sum, inv = 1.0f / K (u) and one product each (u): dmu = (n - 1) u sum |s_i| / K + 2 u |mu|;  dvar = (n + 1) u q / K +
     2 |mu| dmu + u mu^2, the subtraction and + eps and rsqrtf at its documented 1 ulp charged as norm_cases.norm_rho charges rstd: drs = rs rho.  These are distances from the
     EXACT statistics of the f32 partials; the reference (EmuOps.gemm) evaluates them in f32 too, in torch's order, and its own distance from the exact ones is computed and added.
         E += drs |acc - mu cs| + rs dmu |cs|.
@@ -144,7 +144,7 @@ of the kernel's polynomial - and handed to compare() as `bound` with lines=True;
     bound that follows the source operation by operation (gemm_cases.gelu_as): z = |g| c (u), fma(p, z, 1) (u), rcp (1 ulp = 2 u), four Horner fma (u each), poly t (u), z z (u),
     __expf = exp2(x log2e) - the product (u |x|), log2e as an f32 constant (0.25 u |x|), the instruction (2 u) -, the product with it (u), 2 - e (u), the last product (u).
         GEGLU: e = dv |gelu(g)| + |v| (DG dg + GELU_AS_ERR + rnd_as(g)) + DG dv dg + u |h|;        act = 1: e_y = DG E + GELU_AS_ERR + rnd_as(pre).
-  Quick-GELU (activate, :187): y = x / (1 + __expf(-1.702f x)).  a = 1.702 x; exp(-a) is off by r = |a| (2.25 u + |1.702f / 1.702 - 1|) + 2 u relative - the rounded product, the
+  Quick-GELU (activate): y = x / (1 + __expf(-1.702f x)).  a = 1.702 x; exp(-a) is off by r = |a| (2.25 u + |1.702f / 1.702 - 1|) + 2 u relative - the rounded product, the
     product and the constant inside __expf, the kernel's f32 constant against the reference's 1.702, the instruction - and moves y by |x| E / (1 + E)^2 r; the addition and the
     division (correctly rounded) are u |y| each.  Slope DQ = 1.10 >= |d/dx x sigmoid(1.702 x)| (1.0998 on a grid, as DG = 1.13 >= 1.1290):  e_y = DQ E + that.
   After the activation: out = (y + res) scale, two roundings:  ulp_T(ref) + |scale| (e_y + 2 u (|y| + |res|)).

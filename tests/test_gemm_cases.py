@@ -1,6 +1,7 @@
 """Which kernel every case of tests/gemm_cases.py launches, proven without a GPU: the cases are written in the line format of
 tests/gemm_plan_harness.hip's second mode (the planner and fyc_gemm linked with recording stubs, as in tests/test_gemm_plan.py) and the
-recorded launch - the tile config after the narrow-epilogue rewrite, ring depth, wide, split or not - must equal the intent the case declares.
+recorded launch - the tile config after the narrow-epilogue rewrite, ring depth, wide, split or not - must equal the intent the case declares, and so
+must what csrc/gemm_plan.h::gemm_launch_plan decides for that launch (pre-staged epilogue inputs, the epilogue form).
 The GPU tests (tests/test_gemm_epilogues_gpu.py) parametrise from the same list, so a case there cannot silently run another kernel than
 its name says: that is what had happened to the 16-bit sweeps of test_gemm_plain / test_gemm_conv, whose arguments are pinned here too."""
 import os
@@ -39,10 +40,13 @@ def recorded(tmp_path_factory):
     assert r.returncode == 0 and len(lines) == len(cases), (r.returncode, r.stderr[-2000:], lines[-3:])
     out = {}
     for c, ln in zip(cases, lines):
-        name, launch, executed, rc = ln.split(" | ")
+        name, launch, executed, rest = ln.split(" | ", 3)
+        rc, decided = rest.rsplit(" | ", 1)
         assert name == c.name, (name, c.name)
         fam, cfg, ns, wide, colc, splitk, cs_slots, batch = launch.split()
-        out[c.name] = dict(fam=fam, asked_cfg=int(cfg), cfg=int(executed.split()[0]), ring=int(ns), wide=int(wide), splitk=int(splitk), rc=int(rc.split()[0]), line=ln)
+        decided = None if decided == "-" else {k: int(v) for k, v in (f.split("=") for f in decided.split())}      # gemm_launch_plan's answer for the recorded launch
+        out[c.name] = dict(fam=fam, asked_cfg=int(cfg), cfg=int(executed.split()[0]), ring=int(ns), wide=int(wide), splitk=int(splitk), rc=int(rc.split()[0]), decided=decided,
+                           line=ln)
     return out
 
 
@@ -63,9 +67,26 @@ def test_case_launches_what_it_declares(recorded, case):
     ends = ("act", "f32") if case.act else {G.PLAIN: ("plain", "f32"), G.CONV: ("conv", "f32"), G.UP2: ("conv", "f32"), G.T3: ("t3",)}[case.mode]
     assert r["fam"].startswith(fam) and r["fam"].endswith(ends), r["line"]
     if case.group == "geglu" and case.want_wide and case.tile in G.GEGLU_REPLACED:
-        assert r["asked_cfg"] == r["cfg"] == G.GEGLU_REPLACED[case.tile], r["line"]      # (the planner replaces the tile: gemm_plan.h::geglu_tile)
+        assert r["asked_cfg"] == r["cfg"] == G.GEGLU_REPLACED[case.tile], r["line"]      # (the planner replaces the tile: gemm_plan.h::GEMM_TILES, column `geglu`)
     if case.group == "act" and case.want_wide:
         assert r["cfg"] == G.ACT_WIDE_TILES.get(r["asked_cfg"], 2), r["line"]             # (the family builds 1, 2 and 6: the entry folds the planned tile)
+    assert r["decided"] is not None and r["decided"]["pre"] == int(case.want_pre), r["line"]      # what the library decides, against gemm_cases.pre_staged
+    if case.want_form:
+        assert form_of(case, r) == case.want_form, r["line"]
+
+
+def form_of(case, r):
+    """the epilogue form the kernel takes (csrc/gemm_kernel.h::gemm_epilogue) for what the library decided: wide, the epilogue, fast1 and heads_pk"""
+    d = r["decided"]
+    if not r["wide"]:
+        return "narrow"
+    if case.act:
+        return "staged"
+    if case.epilogue == G.HEADS:
+        return "packed" if d["fast1"] and d["heads_pk"] else "staged"
+    if case.epilogue == G.GEGLU:
+        return "packed" if d["fast1"] else "staged"
+    return "packed"
 
 
 @pytest.mark.parametrize("mode,tiles,extra", [(G.PLAIN, PLAIN_TILES, G.EXTRA_PLAIN_RINGS), (G.CONV, CONV_TILES, []), (G.UP2, CONV_TILES, [])])
@@ -113,12 +134,17 @@ def test_new_groups_execute_exactly_their_declared_wide_tiles(recorded, group):
     assert not any(recorded[c.name]["splitk"] > 1 for c in cases)
 
 
-def test_forms_chosen_inside_launch():
-    """pre, fast1 and heads_pk are decided inside gemm_kernel.h::launch, where the harness does not see them: the conditions are restated in gemm_cases.pre_staged (and its head) and
-    the cases meant for a form must satisfy them"""
+def test_forms_chosen_inside_launch(recorded):
+    """pre, fast1 and heads_pk are decided by gemm_plan.h::gemm_launch_plan, which the harness calls for the recorded launch: the conditions are restated in
+    gemm_cases.pre_staged (and its head), the cases meant for a form must satisfy them, and the library must decide what the restatement says"""
     new = G.by_group(*G.EPILOGUE_GROUPS)
     for c in new:
         keys = dict(c.tuning)
+        r = recorded[c.name]
+        assert r["decided"] is not None and r["decided"]["pre"] == int(c.want_pre) and form_of(c, r) == c.want_form, r["line"]
+        assert r["decided"]["fast1"] == (0 if keys.get(G.TUNE_GENERIC_PASS1) == 1 else 1), r["line"]
+        if keys.get(G.TUNE_HEADS_PACKED) in (1, 2):
+            assert r["decided"]["heads_pk"] == (1 if keys[G.TUNE_HEADS_PACKED] == 1 else 0), r["line"]
         if c.want_pre:
             cfg = c.want_cfg
             assert c.want_wide == 1 and G.k_tiles(c, cfg) >= 2 and c.ln <= 1 and (c.ln == 0 or c.M % 2 == 0) and keys.get(G.TUNE_NO_PRESTAGE, 0) == 0, c.name

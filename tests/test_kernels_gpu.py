@@ -57,7 +57,7 @@ def _dt_tiles(tiles):
 
 # NOT a tile sweep for the 16-bit types, whatever the parameters look like: rows_per_batch = 50 is neither a multiple of the row-tile height nor
 # of 16, so the packed LINEAR epilogue cannot stage the row-bias groups and csrc/gemm_plan.h plans every bf16 / f16 case NARROW (wide = 0) - and the narrow
-# per-lane epilogue only exists for tile configs 1 / 2 (gemm_kernel.h::dispatch_cfg rewrites the rest).  All (tile, ring) pairs below run 128x128 or
+# per-lane epilogue only exists for tile configs 1 / 2 (gemm_plan.h::gemm_executed_cfg rewrites the rest).  All (tile, ring) pairs below run 128x128 or
 # 128x64 with the per-lane epilogue and a 2-deep ring.  The test stays as the narrow epilogue's check on six shapes; the packed epilogue on the tiles it
 # names is tests/test_gemm_epilogues_gpu.py, and tests/test_gemm_cases.py pins on the CPU what both launch.
 @pytest.mark.parametrize("dt,tile_ring", _dt_tiles(PLAIN_TILES))
