@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 EXTRA = os.environ.get("FYC_BUILD_EXTRA", "").split()
 LIB = os.path.abspath(os.environ.get("FYC_BUILD_LIB") or os.path.join(HERE, "libfyc_hip.so"))
 OBJ = os.path.join(HERE, "_obj") if not (EXTRA or os.environ.get("FYC_BUILD_LIB")) else LIB + ".obj"
-SOURCES = ["api.hip", "gemm.hip", "gemm_bf16_plain.hip", "gemm_bf16_conv.hip", "gemm_bf16_act.hip", "gemm_f16_plain.hip", "gemm_f16_conv.hip", "gemm_f16_act.hip", "gemm_f32.hip", "gemm_bf16_t3.hip", "gemm_f16_t3.hip", "gemm_f32_t3.hip", "gemm_f32x3.hip", "gemm_f32x3_t3.hip", "conv_up_phases.hip", "gemm_bf16_up.hip", "gemm_f16_up.hip", "attention.hip", "attention_small.hip", "attention_medium.hip", "attention_large.hip", "attention_small_f16.hip", "attention_medium_f16.hip", "attention_large_f16.hip", "attention_f32x3.hip", "attention_wide.hip", "attention_wide_f16.hip", "attention_wide_f32x3.hip", "temporal_attn.hip", "temporal_attn_f32x3.hip", "temporal_block.hip", "temporal_block_rr.hip", "ff_block.hip", "panel_linear.hip", "norm.hip", "elementwise.hip", "image_edit.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_bf16_plain.hip", "gemm_bf16_conv.hip", "gemm_bf16_act.hip", "gemm_f16_plain.hip", "gemm_f16_conv.hip", "gemm_f16_act.hip", "gemm_f32.hip", "gemm_bf16_t3.hip", "gemm_f16_t3.hip", "gemm_f32_t3.hip", "gemm_f32x3.hip", "gemm_f32x3_t3.hip", "conv_up_phases.hip", "gemm_bf16_up.hip", "gemm_f16_up.hip", "attention.hip", "attention_small.hip", "attention_medium.hip", "attention_large.hip", "attention_small_f16.hip", "attention_medium_f16.hip", "attention_large_f16.hip", "attention_f32x3.hip", "attention_wide.hip", "attention_wide_f16.hip", "attention_wide_f32x3.hip", "temporal_attn.hip", "temporal_attn_long.hip", "temporal_attn_f32x3.hip", "temporal_block.hip", "temporal_block_rr.hip", "ff_block.hip", "panel_linear.hip", "norm.hip", "elementwise.hip", "image_edit.hip"]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified register file and every
 # kernel here fits in 256 registers), which removes the v_accvgpr_read/write traffic around the
 # softmax rescale and the epilogues (312 -> 0 such moves in the attention main loop).

@@ -220,6 +220,7 @@ OPS = {
     "fyc_ff_block": FFBlockArgs, "fyc_panel_linear": PanelLinearArgs, "fyc_repeat": RepeatArgs,
     "fyc_conv_up_phases": ConvUpPhasesArgs, "fyc_cfg_sigma_step": CfgSigmaArgs, "fyc_unet_input_scaled": UnetInputScaledArgs,
     "fyc_cfg_pndm_step": CfgPndmArgs,
+    "fyc_temporal_attention_long": TAttnArgs,
     "fyc_posterior_latents": PosteriorLatentsArgs, "fyc_inpaint_prepare": InpaintPrepareArgs, "fyc_renoise_blend": RenoiseBlendArgs,
 }
 MISC = ["fyc_version", "fyc_last_error", "fyc_init", "fyc_device_caps", "fyc_set_tuning", "fyc_gemm_row_parts", "fyc_gemm_stat_layout", "fyc_gemm_workspace_bytes", "fyc_gn_stats_workspace", "fyc_temporal_block_supported", "fyc_temporal_block_wstream_bytes",

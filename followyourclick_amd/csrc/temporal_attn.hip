@@ -6,12 +6,13 @@
 // pure index arithmetic here: one wave64 owns one (clip b, pixel p, head h) task and gathers the
 // F rows of that pixel (row stride P*3C) straight into MFMA operand registers.
 //
-// 16-bit path (v_mfma_f32_16x16x32_bf16 / _f16: template parameter T), F <= 64:
+// 16-bit path (v_mfma_f32_16x16x32_bf16 / _f16: template parameter T), F <= 64 (longer clips: temporal_attn_long.hip, one workgroup per task):
 //   S^T = K Q^T (rows = key frames, cols = query frames), full softmax in registers (all keys of a
 //   query are in 4 lanes x 4..16 regs), O^T = V^T P^T with the keys as the 32 MFMA k-slots (two such
 //   MFMAs per output tile for F > 32).
-// f32 path: scalar reference-precision kernel (parity mode only); with f32_products = FYC_PRODUCTS_SPLIT_BF16 the matrix-instruction kernel of
-// temporal_attn_f32x3.hip (f32 storage, every product from three bf16 matrix instructions).
+// f32 path: scalar reference-precision kernel (parity mode only; F <= 256, its score array sized 64 or 256 by the clip); with f32_products =
+// FYC_PRODUCTS_SPLIT_BF16 and F <= 64 the matrix-instruction kernel of temporal_attn_f32x3.hip (f32 storage, every product from three bf16 matrix
+// instructions).  There is no split-product kernel for longer clips: they run the exact kernel, which is more accurate than the tier asks.
 //
 // ROPE (template parameter; rope_cos / rope_sin of fyc_tattn_args, f32 [F][d/2]): q and k are rotated per
 // frame before the score product - x'[c] = x[c] cos[f][c mod h] -/+ x[c +/- h] sin[f][c mod h], h = d/2, the
@@ -21,34 +22,6 @@
 #include "temporal_attn.h"   // TAttnP, fyc_tattn_f32x3_launch
 
 namespace {
-
-// rotate_half on the 8 head channels dd .. dd+7 of one frame's q or k row (`row` = the head's first channel of that row).  h = d/2 is
-// a multiple of 4, so each 4-channel run of the fragment lies wholly below or above h and its partner run starts h channels away: at
-// d = 8 inside this fragment, at d = 40 across two others.  The partners come from a second, 8-byte load of the same row (same cache
-// lines, no HBM traffic).  Lanes outside the problem read the zero page for values, partners and tables alike and keep their zeros.
-template <typename T>
-__device__ __forceinline__ typename Pair16<T>::Vec8 rope8(typename Pair16<T>::Vec8 x, const T* row, int dd, int hh, const float* ct,
-                                                          const float* st, bool ok, const T* zero) {
-  const u32x4 xb = __builtin_bit_cast(u32x4, x);
-  u32x4 xo;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int c0 = dd + 4 * r;
-    const bool low = c0 < hh;
-    const int cp = low ? c0 + hh : c0 - hh, cm = low ? c0 : c0 - hh;
-    float xp[4];
-    ElemIO<T>::ld4(ok ? row + cp : zero, xp);
-    const f32x4 cs = *reinterpret_cast<const f32x4*>(ok ? ct + cm : reinterpret_cast<const float*>(zero));
-    const f32x4 sn = *reinterpret_cast<const f32x4*>(ok ? st + cm : reinterpret_cast<const float*>(zero));
-    const float xv[4] = {Pair16<T>::lo(xb[2 * r]), Pair16<T>::hi(xb[2 * r]), Pair16<T>::lo(xb[2 * r + 1]), Pair16<T>::hi(xb[2 * r + 1])};
-    float y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) y[i] = xv[i] * cs[i] + (low ? -xp[i] : xp[i]) * sn[i];
-    xo[2 * r] = Pair16<T>::pack(y[0], y[1]);
-    xo[2 * r + 1] = Pair16<T>::pack(y[2], y[3]);
-  }
-  return __builtin_bit_cast(typename Pair16<T>::Vec8, xo);
-}
 
 // V^T operand of output tile t for key-tile pair pp, gathered from the wave's LDS tile (layout: at the tile's declaration)
 template <typename T, int DP, int NFT>
@@ -217,8 +190,9 @@ __global__ void __launch_bounds__(256) tattn_bf16_kernel(const TAttnP p) {
   }
 }
 
-// parity-mode kernel: one thread per (b, pixel, head, query frame); f32 throughout.
-template <bool ROPE>
+// parity-mode kernel: one thread per (b, pixel, head, query frame); f32 throughout.  MAXF >= F: the scores of a query (64: the kernel as it
+// was, in registers; 256: clips of 65 .. 256 frames, the array in scratch - speed is not a goal of this mode)
+template <bool ROPE, int MAXF>
 __global__ void __launch_bounds__(256) tattn_f32_kernel(const TAttnP p) {
   const long long total = (long long)p.clips * p.pixels * p.heads * p.frames;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -232,7 +206,7 @@ __global__ void __launch_bounds__(256) tattn_f32_kernel(const TAttnP p) {
   const float* base = reinterpret_cast<const float*>(p.qkv) + ((long long)b * F * p.pixels + pix) * ld + h * p.d;
   const long long fs = (long long)p.pixels * ld;
   const float* q = base + fq * fs;
-  float sc[64];
+  float sc[MAXF];
   float mx = -INFINITY;
   for (int fk = 0; fk < F; ++fk) {
     const float* k = base + fk * fs + C;
@@ -288,31 +262,52 @@ int launch_d(const TAttnP& p, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
-  FYC_REQUIRE(a && a->qkv && a->o, "fyc_temporal_attention: null pointer");
-  FYC_REQUIRE_F32_PRODUCTS("fyc_temporal_attention", a);
-  FYC_REQUIRE(g_fyc_zero_page != nullptr, "fyc_temporal_attention: fyc_init() not called");
-  FYC_REQUIRE(a->clips > 0 && a->frames > 0 && a->pixels > 0 && a->heads > 0, "fyc_temporal_attention: bad sizes");
-  FYC_REQUIRE(a->frames <= 64, "fyc_temporal_attention: frames=%d > 64 unsupported", a->frames);
-  FYC_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), "fyc_temporal_attention: rope_cos and rope_sin must both be set or both be NULL");
-  FYC_REQUIRE((((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) & 15) == 0, "fyc_temporal_attention: rope tables must be 16-byte aligned");
-  FYC_REQUIRE(a->d % 8 == 0 && a->d >= 8 && a->d <= 160, "fyc_temporal_attention: head dim %d", a->d);
-  TAttnP p;
+// the checks both entry points share (behind the null and f32_products checks) and the parameter block they fill; `fn` names the entry point in the messages
+static int tattn_params(const fyc_tattn_args* a, const char* fn, TAttnP& p) {
+  FYC_REQUIRE(g_fyc_zero_page != nullptr, "%s: fyc_init() not called", fn);
+  FYC_REQUIRE(a->clips > 0 && a->frames > 0 && a->pixels > 0 && a->heads > 0, "%s: bad sizes", fn);
+  FYC_REQUIRE(a->frames <= 256, "%s: frames=%d > 256 unsupported", fn, a->frames);
+  FYC_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), "%s: rope_cos and rope_sin must both be set or both be NULL", fn);
+  FYC_REQUIRE((((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin) & 15) == 0, "%s: rope tables must be 16-byte aligned", fn);
+  FYC_REQUIRE(a->d % 8 == 0 && a->d >= 8 && a->d <= 160, "%s: head dim %d", fn, a->d);
   p.qkv = a->qkv; p.o = a->o; p.clips = a->clips; p.frames = a->frames; p.pixels = a->pixels; p.heads = a->heads; p.d = a->d;
   p.scale = a->scale; p.zero = (const char*)g_fyc_zero_page;
   p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin;
+  return 0;
+}
+
+extern "C" int fyc_temporal_attention(const fyc_tattn_args* a, void* stream) {
+  FYC_REQUIRE(a && a->qkv && a->o, "fyc_temporal_attention: null pointer");
+  FYC_REQUIRE_F32_PRODUCTS("fyc_temporal_attention", a);
+  TAttnP p;
+  if (const int rc = tattn_params(a, "fyc_temporal_attention", p)) return rc;
   const bool rope = a->rope_cos != nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (a->dtype == FYC_F32) {
-    if (a->f32_products == FYC_PRODUCTS_SPLIT_BF16) return fyc_tattn_f32x3_launch(p, st);      // temporal_attn_f32x3.hip
+    if (a->f32_products == FYC_PRODUCTS_SPLIT_BF16 && p.frames <= 64) return fyc_tattn_f32x3_launch(p, st);      // temporal_attn_f32x3.hip
     const long long total = (long long)p.clips * p.pixels * p.heads * p.frames;
+    FYC_REQUIRE(total + 255 < (256ll << 31), "fyc_temporal_attention(f32): %lld queries exceed the grid", total);
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (rope) hipLaunchKernelGGL(tattn_f32_kernel<true>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(tattn_f32_kernel<false>, grid, dim3(256), 0, st, p);
+    if (p.frames > 64) {      // (the split-product tier too: no split-product kernel covers these clips)
+      if (rope) hipLaunchKernelGGL((tattn_f32_kernel<true, 256>), grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((tattn_f32_kernel<false, 256>), grid, dim3(256), 0, st, p);
+    } else if (rope) hipLaunchKernelGGL((tattn_f32_kernel<true, 64>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((tattn_f32_kernel<false, 64>), grid, dim3(256), 0, st, p);
     FYC_CHECK_LAUNCH("fyc_temporal_attention(f32)");
     return 0;
   }
   FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16, "fyc_temporal_attention: bad dtype");
+  if (p.frames > 64) return fyc_tattn_long_launch(p, a->dtype, st);      // temporal_attn_long.hip
   if (rope) return a->dtype == FYC_F16 ? launch_d<f16_t, true>(p, st) : launch_d<bf16_t, true>(p, st);
   return a->dtype == FYC_F16 ? launch_d<f16_t, false>(p, st) : launch_d<bf16_t, false>(p, st);
+}
+
+extern "C" int fyc_temporal_attention_long(const fyc_tattn_args* a, void* stream) {
+  FYC_REQUIRE(a && a->qkv && a->o, "fyc_temporal_attention_long: null pointer");
+  FYC_REQUIRE_F32_PRODUCTS("fyc_temporal_attention_long", a);
+  TAttnP p;
+  if (const int rc = tattn_params(a, "fyc_temporal_attention_long", p)) return rc;
+  FYC_REQUIRE(a->dtype == FYC_BF16 || a->dtype == FYC_F16, "fyc_temporal_attention_long: FYC_BF16 / FYC_F16 tensors only (dtype %d)", a->dtype);
+  FYC_REQUIRE(a->frames > 16, "fyc_temporal_attention_long: frames=%d: the long-clip kernel starts at 17 frames", a->frames);
+  return fyc_tattn_long_launch(p, a->dtype, (hipStream_t)stream);
 }

@@ -287,8 +287,11 @@ class UNet3DEngine(EngineBase):
 
     def _rope(self, d: int, F: int) -> Tuple[Tensor, Tensor]:
         """(cos, sin) device tables of the rotary temporal attention, built once per (head dim, clip length)"""
-        if F > 64:
-            raise ValueError(f"video_length {F}: the rotary temporal attention covers clips of up to 64 frames")
+        # the clip length is the backend's to give: 256 frames with the long-clip kernel (HipOps on a library that has it), 64 for a backend
+        # that does not say (a library from before that kernel, an op emulator written against it)
+        limit = getattr(self.ops, "temporal_attention_max_frames", 64)
+        if F > limit:
+            raise ValueError(f"video_length {F}: the rotary temporal attention covers clips of up to {limit} frames")
         cache = self.__dict__.setdefault("_rope_tables", {})
         if (d, F) not in cache:
             cache[(d, F)] = tuple(t.to(self.device) for t in rope_tables(d, F))

@@ -83,6 +83,8 @@ class HipOps:
     def __init__(self):
         self.lib = L.load()
         self.abi_version = int(self.lib.fyc_version())        # (differs from _lib.FYC_VERSION only for an A/B library, FYC_LIB_PATH)
+        # longest clip temporal_attention() takes (UNet3DEngine._rope asks): 256 frames with the long-clip kernel, 64 for an A/B library from before it
+        self.temporal_attention_max_frames = 256 if hasattr(self.lib, "fyc_temporal_attention_long") else 64
         self._zero = None
         self._ws = None              # scratch for split-K GEMMs: one buffer, grown on demand (all work is on one stream)
         self._ws_need = {}           # (shape, flags) -> split-K scratch bytes (fyc_gemm_workspace_bytes), see gemm()
@@ -337,10 +339,15 @@ class HipOps:
         self._call("fyc_repeat", a)
 
     def temporal_attention(self, qkv: Tensor, o: Tensor, *, clips: int, frames: int, pixels: int, heads: int, d: int,
-                           scale: float, rope: Optional[Tuple[Tensor, Tensor]] = None, products: Optional[str] = None) -> None:
+                           scale: float, rope: Optional[Tuple[Tensor, Tensor]] = None, products: Optional[str] = None,
+                           kernel: Optional[str] = None) -> None:
         """rope = (cos, sin): f32 device tables [frames][d/2]; q and k are rotated per frame before the score product (include/fyc.h).
         products: None = this instance's f32_products (the switch gemm() reads), else "exact" / "split" (f32 tensors only: "split" with 16-bit tensors
-        raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode)"""
+        raises; with 16-bit tensors and None the field stays 0 whatever the instance's mode)
+        kernel: None = fyc_temporal_attention (frames <= 256; the long-clip kernel above 64 frames); "long" = fyc_temporal_attention_long, the
+        long-clip kernel for any 16 < frames <= 256 (16-bit tensors only)"""
+        if kernel not in (None, "long"):
+            raise ValueError(f"temporal_attention: kernel {kernel!r}: expected None or 'long'")
         f32_products = resolve_f32_products("temporal_attention", qkv.dtype, products, self.f32_products)
         self.ensure_init(qkv.device)
         a = L.TAttnArgs()
@@ -353,7 +360,7 @@ class HipOps:
                     raise ValueError(f"temporal_attention: rope tables must be contiguous f32 [{frames}][{d // 2}] tensors on {qkv.device}")
             a.rope_cos, a.rope_sin = cos.data_ptr(), sin.data_ptr()
         a.f32_products = f32_products
-        self._call("fyc_temporal_attention", a)
+        self._call("fyc_temporal_attention_long" if kernel == "long" else "fyc_temporal_attention", a)
 
     def _tblock_args(self, x, out, w_qkv, colsum, bias, pe_bias, w_out, b_out, clips, frames, pixels, heads, d, scale, eps):
         a = L.TemporalBlockArgs()

@@ -245,7 +245,10 @@ int fyc_attention_masked(const fyc_attn_mask_args* a, void* stream);
  * For every (clip b, pixel p, head h): softmax over the F frames (motion_module.py:371-464 with
  * mm_attn_cross.py:148-177).  qkv is the token-major output of the fused to_q|to_k|to_v GEMM,
  * [(b f p)][3C]; o is token-major [(b f p)][C].  The '(b f) d c -> (b d) f c' transposes of the
- * reference are index arithmetic here.  frames <= 64, d a multiple of 8 up to 160.
+ * reference are index arithmetic here.  frames <= 256, d a multiple of 8 up to 160.  Up to 64 frames one wave runs a (clip, pixel, head)
+ * task with its operands in registers; above, FYC_BF16 / FYC_F16 tensors run the long-clip kernel (one workgroup per task, K and V^T staged in
+ * LDS by blocks of 64 key frames, running-maximum softmax) and FYC_F32 tensors the exact scalar kernel whatever f32_products says: there is no
+ * split-product kernel for these clips, FYC_PRODUCTS_SPLIT_BF16 is then answered with exact products.
  *
  * Products of FYC_F32 operands (version 306, f32_products; hi(x) = RNE_bf16(x), lo(x) = RNE_bf16(x - hi(x)) as for fyc_gemm).  FYC_PRODUCTS_EXACT (0, the
  * default): the scalar f32 kernel, every product an f32 product.  FYC_PRODUCTS_SPLIT_BF16 (1): one wave per (clip, pixel, head) on v_mfma_f32_16x16x32_bf16:
@@ -273,6 +276,9 @@ typedef struct {
   int32_t f32_products;
 } fyc_tattn_args;
 int fyc_temporal_attention(const fyc_tattn_args* a, void* stream);
+/* (version 308, added entry point) the long-clip kernel for any 16 < frames <= 256, FYC_BF16 / FYC_F16 only (FYC_F32 is refused): what
+ * fyc_temporal_attention launches above 64 frames, callable below them for a comparison with the register-resident kernel. */
+int fyc_temporal_attention_long(const fyc_tattn_args* a, void* stream);
 
 /* ---- normalisation -----------------------------------------------------------------------
  * GroupNorm statistics over `rows_per_sample` rows x (C/groups) channels:
